@@ -35,6 +35,13 @@ node check of SURVEY.md 8e -- its partial (lsg_jobs_partial) is all-gathered ove
 product of the N partials gets one final exponentiation (lsg_final_*), and the ticket is
 resolved with that verdict (lsg_wait_jobs_node).
 Launch: python bench.py [--gpus N --steps K --warmup W --workload jobs]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  --full adds what
+takes runs of its own after the timed region: the unloaded latency (packages one at a time),
+the probes of the GPU's mad / Fp-multiplication peaks with the roofline figures derived from
+them, and the CPU baseline (oracle/c; --no-cpu-baseline leaves that leg out); without it those
+fields of the line are null.  --dump-outputs DIR writes what the last timed step returned to
+its caller (DIR/verdicts.npy, DIR/counters.npy).
 """
 import argparse
 import collections
@@ -309,7 +316,7 @@ def run_node_workload(args):
         raise SystemExit("bench_node.js failed:\n" + r.stdout[-2000:] + r.stderr[-4000:])
     nb = json.loads(r.stdout.strip().splitlines()[-1])
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from lodestar_amd._native import Context
         ctx = Context(local)
         wl = Workload(ctx, "jobs", 0, 4096, 1)
@@ -370,7 +377,13 @@ def main():
     ap.add_argument("--validators", type=int, default=N_VALIDATORS,
                     help="block workload: pubkey table rows (validator v holds key v mod 1024)")
     ap.add_argument("--packages", type=int, default=None, help="distinct packages cycled through")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the unloaded latency, the GPU's mad / Fp-multiplication "
+                         "peaks (roofline, whole_path_mad_frac) and the CPU baseline; off: those fields are null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy: verdicts (float32, one "
+                         "(status, err_code) row per job) and counters (float64: batch_retries, batch_sigs_success)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--waits", choices=["thread", "inline"], default="thread",
                     help="one GPU: wait each ticket on its own thread (as the Node host) or inline")
     ap.add_argument("--node-max-sigs", type=int, default=32768, help="node workload: maxSigsPerPackage")
@@ -505,6 +518,7 @@ def main():
         return ft
 
     stats_acc = collections.Counter()
+    last_out = {}  # what the last package of the timed region returned (--dump-outputs)
     node_ms = collections.Counter()  # host time per node check: partial ready, all-gather, node FE + wait
     submit_wall = []  # wall time of each lsg_submit_jobs call (lock wait + staging + enqueue)
 
@@ -540,6 +554,8 @@ def main():
                               "submit_us": st["submit_us"], "packages": 1})
             if capture and len(times) < KT_SAMPLE:
                 times.append(ctx.last_kernel_times())
+            if capture:
+                last_out.update(res=res, n_jobs=t[1], st=st)
             done += 1
 
         # node checks are pipelined: package k's partial is exchanged and its node
@@ -626,6 +642,8 @@ def main():
                                   "submit_us": st["submit_us"], "packages": 1})
                 if capture and len(times) < KT_SAMPLE:
                     times.append(ctx.last_kernel_times())
+                if capture:
+                    last_out.update(res=res, n_jobs=t[1], st=st)
                 room.release()
 
         threads = [threading.Thread(target=guard(f), daemon=True) for f in (exchanger, resolver)]
@@ -685,6 +703,8 @@ def main():
                                   "submit_us": st["submit_us"], "packages": 1})
                 if capture and len(times) < KT_SAMPLE:
                     times.append(ctx.last_kernel_times())
+                if capture:
+                    last_out.update(res=res, n_jobs=t[1], st=st)
                 if seq < n_pkgs:
                     submit()
         return lat, times
@@ -715,14 +735,25 @@ def main():
         te = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if rehearse else f"cuda:{local}")
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
         elapsed = float(te.item())
-    # unloaded latency: one package at a time, each alone on the GPU
-    lat1, _ = run(3, 1)
+    if args.dump_outputs and rank == 0:
+        # the last timed package as its caller received it: per-job (status, err_code), and the
+        # counters of lsg_wait_jobs' stats that do not depend on timing
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        st = last_out["st"]
+        np.save(os.path.join(args.dump_outputs, "verdicts.npy"),
+                np.frombuffer(last_out["res"], dtype=np.int32, count=2 * last_out["n_jobs"]).reshape(-1, 2).astype(np.float32))
+        np.save(os.path.join(args.dump_outputs, "counters.npy"),
+                np.array([st["batch_retries"], st["batch_sigs_success"]], dtype=np.float64))
+    # unloaded latency: one package at a time, each alone on the GPU (--full)
+    lat1 = run(3, 1)[0] if args.full else None
 
     # kernel-level roofline for the dominant kernel, from HIP events recorded on the streams
-    # the kernels ran on, averaged over the timed packages
+    # the kernels ran on, averaged over the timed packages (--full: the peaks are probed)
     opc = json.load(open(os.path.join(ROOT, "bench", "opcount.json")))
-    probe_fp, _probe_mad = ctx.probe_fp_mul_rate()
-    peak_mad = ctx.probe_mad_peak()  # measured v_mad_u64_u32 issue rate of this GPU (k_probe_mad)
+    probe_fp, peak_mad = None, None
+    if args.full:
+        probe_fp, _probe_mad = ctx.probe_fp_mul_rate()
+        peak_mad = ctx.probe_mad_peak()  # measured v_mad_u64_u32 issue rate of this GPU (k_probe_mad)
     agg, calls = {}, {}
     for pkg_times in ktimes:
         for name, ms in pkg_times:
@@ -738,12 +769,14 @@ def main():
     dom = max(per_set, key=per_set.get) if per_set else "k_miller_fused"
     # one launch covers the package's sets
     muls = sum(opc["stage_fp_muls"][st] for st in stage_of[dom]) * (n_sets // n_dev)  # device 0's launch
-    achieved = muls * opc["mads_per_fp_mul"] / (agg[dom] / max(calls[dom], 1) * 1e-3) / 1e12
-    peak = peak_mad / 1e12
-    roof = {"bound": "valu", "kernel": dom, "achieved": round(achieved, 3), "peak": round(peak, 3),
-            "unit": "Tmad/s (v_mad_u64_u32)", "frac": round(achieved / peak, 4),
-            "traffic": pmc_traffic(dom, n_sets // n_dev), "alone": pmc_alone(dom, n_sets // n_dev),
-            "kernel_ms": round(agg[dom] / max(calls[dom], 1), 3), "work_per_launch_fp_muls": muls}
+    roof = None
+    if args.full:
+        achieved = muls * opc["mads_per_fp_mul"] / (agg[dom] / max(calls[dom], 1) * 1e-3) / 1e12
+        peak = peak_mad / 1e12
+        roof = {"bound": "valu", "kernel": dom, "achieved": round(achieved, 3), "peak": round(peak, 3),
+                "unit": "Tmad/s (v_mad_u64_u32)", "frac": round(achieved / peak, 4),
+                "traffic": pmc_traffic(dom, n_sets // n_dev), "alone": pmc_alone(dom, n_sets // n_dev),
+                "kernel_ms": round(agg[dom] / max(calls[dom], 1), 3), "work_per_launch_fp_muls": muls}
     total_sets = n_sets * world * args.steps  # (n_sets spans all devices of a --devices context)
     value = total_sets / elapsed
     # whole-path work per set: the per-set stages with the bucket-MSM signature sum (groups of
@@ -778,7 +811,7 @@ def main():
     node_mads = value * per_set_muls * opc["mads_per_fp_mul"]
     if rank == 0:
         cpu = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             if args.workload in ("jobs", "adversarial", "gossip", "single", "committees"):
                 sets = [s for job, _ in wl.packages[0][0] for s in job]
                 if args.workload == "adversarial":
@@ -816,7 +849,7 @@ def main():
                        "parallelism": (f"devices{args.devices}x{local} (one context, one GPU: duplicate ids)" if args.devices_same
                                        else f"devices{args.devices} (one context, RCCL exchange)") if args.devices else f"shard{world}"},
             "p50_batch_latency_ms": round(1e3 * statistics.median(lat), 3),
-            "p50_unloaded_latency_ms": round(1e3 * statistics.median(lat1), 3),
+            "p50_unloaded_latency_ms": round(1e3 * statistics.median(lat1), 3) if lat1 else None,
             "pipeline_depth": args.depth, "distinct_packages": len(prepared),
             "coalesce": {"max_sets": args.coalesce, "inflight": args.coalesce_inflight} if args.coalesce else None,
             "allocations_in_timed_region": allocs, "timed_window_monotonic_ns": [w0, w1],
@@ -831,7 +864,7 @@ def main():
             "node_check_host_ms_per_package": ({k: round(v / node_ms["n"], 3) for k, v in node_ms.items() if k != "n"}
                                                if node_ms["n"] else None),
             "roofline": roof,
-            "whole_path_mad_frac": round(node_mads / (peak_mad * world * n_dev), 4),
+            "whole_path_mad_frac": round(node_mads / (peak_mad * world * n_dev), 4) if peak_mad else None,
             "kernel_ms": {k: round(v, 3) for k, v in agg.items()},
             "probe_lane_fp_mul_per_s": probe_fp,
             "cpu_baseline": cpu,

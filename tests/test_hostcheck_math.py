@@ -35,7 +35,8 @@ def _build(backend):
     newest = max(os.path.getmtime(p) for p in hdrs + [SRC])
     if os.path.exists(lib) and os.path.getmtime(lib) >= newest:
         return lib
-    subprocess.check_call(["hipcc", "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-shared"] + defs +
+    from lodestar_amd.build import hipcc  # (as build(): PATH, else the ROCm install's own)
+    subprocess.check_call([hipcc(), "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-shared"] + defs +
                           ["-I", os.path.join(ROOT, "lodestar_amd", "csrc"), SRC, "-o", lib])
     return lib
 

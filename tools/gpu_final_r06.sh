@@ -24,12 +24,12 @@ for part in "$@"; do
     core)
       run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 180 --timeout-method thread
       run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()"
-      for k in 1 2 3; do run "bench_$k" 400 python -u bench.py; done
+      for k in 1 2 3; do run "bench_$k" 400 python -u bench.py --full; done
       for k in 1 2 3; do run "bench_node_$k" 400 python -u bench.py --workload node --no-cpu-baseline; done
       LSG_NODE_CPUPROF=$PWD/$out/node.cpuprofile run bench_node_prof 400 python -u bench.py --workload node --no-cpu-baseline
       python3 tools/node_prof_summary.py $out/node.cpuprofile 30 > $out/node_prof.txt ;;
     workloads)
-      for w in block gossip sync adversarial committees single; do run "bench_$w" 400 python -u bench.py --workload $w --no-cpu-baseline; done ;;
+      for w in block gossip sync adversarial committees single; do run "bench_$w" 400 python -u bench.py --full --workload $w --no-cpu-baseline; done ;;
     prof)
       run rocprof 400 rocprofv3 --kernel-trace --stats -d $out/prof -o run -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline
       run pmc 900 bash tools/gpu_pmc.sh ;;

@@ -10,7 +10,7 @@ R=${AB_ROUND:-r05}
 one() {  # tag workload lib
   local out="gpurun_out/${R}_ab_${AB_TAG}_${2}_$1"
   echo "== $1 $2 ($(date +%T))"
-  env LSG_LIB=$3 $4 timeout -k 10 300 python -u bench.py --workload "$2" --no-cpu-baseline ${AB_ARGS:-} > "$out.json" 2> "$out.err"
+  env LSG_LIB=$3 $4 timeout -k 10 300 python -u bench.py --full --workload "$2" --no-cpu-baseline ${AB_ARGS:-} > "$out.json" 2> "$out.err"
   local rc=$?
   python3 -c "import json; d=json.loads(open('$out.json').read().splitlines()[-1]); r=d['roofline']; print(d['value'], d['p50_batch_latency_ms'], d['p50_unloaded_latency_ms'], r['kernel'], r['kernel_ms'], d['whole_path_mad_frac'])" || true
   if [ $rc -ne 0 ]; then tail -5 "$out.err"; echo "== FAILED rc=$rc"; exit $rc; fi

@@ -10,7 +10,7 @@ for w in ${SW_WORKLOADS:-gossip sync}; do
     for f in ${SW_INFLIGHT:-4 8}; do
       out="gpurun_out/r05_small_${w}_slp${slp}_f${f}"
       echo "== $w slp=$slp inflight=$f ($(date +%T))"
-      LSG_LIB=lodestar_amd/liblodestar_bls_ab.so LSG_SLP_ITEMS=$slp timeout -k 10 300 python -u bench.py --workload "$w" \
+      LSG_LIB=lodestar_amd/liblodestar_bls_ab.so LSG_SLP_ITEMS=$slp timeout -k 10 300 python -u bench.py --full --workload "$w" \
         --coalesce-inflight "$f" --no-cpu-baseline > "$out.json" 2> "$out.err" || { tail -5 "$out.err"; exit 1; }
       python3 -c "import json; d=json.loads(open('$out.json').read().splitlines()[-1]); print(d['value'], d['p50_batch_latency_ms'], d['whole_path_mad_frac'])"
     done

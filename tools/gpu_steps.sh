@@ -31,11 +31,11 @@ for step in "$@"; do
     test) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 180 --timeout-method thread ;;
     test-*) run "pytest_${step#test-}" 600 python -u -m pytest tests -m gpu -x -v --timeout 180 --timeout-method thread -k "${step#test-}" ;;
     smoke) run smoke 300 python -u -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 400 python -u bench.py ;;
+    bench) run bench 400 python -u bench.py --full ;;
     bench-short) run bench_short 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline ;;
-    bench-*) w=${step#bench-}; run "bench_$w" 400 python -u bench.py --workload "$w" --no-cpu-baseline ;;
-    depth-*) a=${step#depth-}; w=${a%%:*}; d=${a#*:}; run "bench_${w}_d$d" 400 python -u bench.py --workload "$w" --depth "$d" --no-cpu-baseline ;;
-    co-*) a=${step#co-}; w=${a%%:*}; r=${a#*:}; d=${r%%:*}; f=${r#*:}; run "bench_${w}_d${d}_f$f" 400 python -u bench.py --workload "$w" --depth "$d" --coalesce-inflight "$f" --no-cpu-baseline ;;
+    bench-*) w=${step#bench-}; run "bench_$w" 400 python -u bench.py --full --workload "$w" --no-cpu-baseline ;;
+    depth-*) a=${step#depth-}; w=${a%%:*}; d=${a#*:}; run "bench_${w}_d$d" 400 python -u bench.py --full --workload "$w" --depth "$d" --no-cpu-baseline ;;
+    co-*) a=${step#co-}; w=${a%%:*}; r=${a#*:}; d=${r%%:*}; f=${r#*:}; run "bench_${w}_d${d}_f$f" 400 python -u bench.py --full --workload "$w" --depth "$d" --coalesce-inflight "$f" --no-cpu-baseline ;;
     devices1) run bench_devices1 400 python -u bench.py --devices 1 --steps 20 --warmup 5 --no-cpu-baseline ;;
     devhost-*) n=${step#devhost-}; run "bench_devhost_$n" 400 python -u bench.py --devices "$n" --devices-same --depth 3 --steps 12 --warmup 3 --packages 2 --no-cpu-baseline ;;
     node) run bench_node 400 python -u bench.py --workload node --no-cpu-baseline ;;
