@@ -16,6 +16,7 @@
  *   lsg_sig_decode         <- maybeBatch.ts:23,36 Signature.fromBytes(bytes, affine, true)
  *   lsg_aggregate_signatures <- opPools Signature.aggregate
  *   lsg_*signing_roots     <- util/signingRoot.ts:7-13 computeSigningRoot
+ *   lsg_verify_deposits    <- block/processDeposit.ts:47-66 (KeyValidate + verify per deposit)
  *   lsg_submit_jobs /      <- the asynchronous lsg_submit / lsg_wait pair of SURVEY.md 8b:
  *   lsg_wait_jobs             one BlsWorkReq[] package in flight per pipeline slot
  *   lsg_init_devices       <- the node-wide pool (chain.ts:195-198, multithread/poolSize.ts:7):
@@ -80,6 +81,21 @@ extern "C" {
  * by coalescing and runs on its slot's high-priority streams: its kernels are dispatched ahead
  * of the packages in flight.  Verdicts are unaffected. */
 #define LSG_JOB_PRIORITY 2u
+/* The job's sets carry their own, untrusted public keys (deposits, processDeposit.ts:57;
+ * BLS-to-execution changes, signatureSets/blsToExecutionChange.ts:32): every byte key (48 or 96
+ * bytes) of every set of the job is run through KeyValidate on the device, inside the package's
+ * pipeline -- decode, not infinity (BLST_PK_IS_INFINITY), in the r-torsion subgroup
+ * (BLST_POINT_NOT_IN_GROUP); the codes of lsg_pubkey_validate, BLST_INVALID_SIZE for another
+ * length.  A key that fails is its SET's error, routed like a signature that does not decode:
+ * the job resolves to LSG_ERROR with the code (inside a set the key's code beats the
+ * signature's, in an aggregate set the first bad key in order gives it; inside a job the first
+ * set in order that has an error does), the set stays out of every RLC group, the other jobs
+ * keep their verdicts, lsg_stats.key_error stays 0 and the batch counters count the set as a
+ * per-set error.  Keys named by table index (LSG_PK_INDEX) are left alone.  Honoured wherever
+ * jobs go: lsg_submit_jobs / lsg_wait_jobs / lsg_verify_jobs, coalesced packages, every device
+ * of a multi-device context, the node protocol.  A package with no such job launches, stages
+ * and allocates exactly what it did without the flag. */
+#define LSG_JOB_VALIDATE_KEYS 4u
 
 typedef struct lsg_ctx lsg_ctx;
 typedef uint64_t lsg_ticket; /* handle of an in-flight submission */
@@ -305,6 +321,31 @@ int lsg_signing_roots(lsg_ctx* ctx, const uint8_t* roots32, size_t n, const uint
                       uint8_t* out32);
 int lsg_attestation_signing_roots(lsg_ctx* ctx, const uint8_t* data128, size_t n, const uint8_t* domain32,
                                   uint32_t domain_stride, uint8_t* out32);
+/* The deposit kind (block/processDeposit.ts:49-54 computeSigningRoot(ssz.phase0.DepositMessage, ..)):
+ * msgs88 = n SSZ-serialized DepositMessage (88 bytes each: pubkey 48, withdrawalCredentials 32,
+ * amount u64 little-endian).  The caller supplies the domain: computeDomain(DOMAIN_DEPOSIT,
+ * GENESIS_FORK_VERSION, ZERO_HASH) is one constant per network. */
+int lsg_deposit_signing_roots(lsg_ctx* ctx, const uint8_t* msgs88, size_t n, const uint8_t* domain32,
+                              uint32_t domain_stride, uint8_t* out32);
+
+/* processDeposit.ts:47-66 for n deposits in one device pass, synchronous, any n.  data184 = n
+ * SSZ-serialized DepositData (184 bytes each: pubkey 48, withdrawalCredentials 32, amount u64,
+ * signature 96).  valid[i] = 1 exactly when the reference would go on to add the validator:
+ * PublicKey.fromBytes(pubkey, affine, true), Signature.fromBytes(sig, affine, true) and verify
+ * over the DepositMessage signing root all pass.  err[i] = 0 when key and signature both passed
+ * validation (whether or not the signature then verified), else the BLST_* code of the first
+ * failing step: key, then signature.  The signing roots are computed on the device and (on a
+ * single-device context) stay there as the messages; each deposit is one single-set batchable
+ * job with LSG_JOB_VALIDATE_KEYS, run through the package machinery -- one RLC check first,
+ * then the chunk and per-job fallback -- in packages of at most 8,192 deposits, up to four of
+ * them outstanding on free pipeline slots (LSG_ERR_BUSY only when other tickets hold
+ * every slot; valid and err are then incomplete and the caller repeats the call, as it would
+ * lsg_submit_jobs).  The packages launch on
+ * their own: they are never held by lsg_set_coalesce and do not flush what it holds, so packages
+ * held for coalescing go out when their own rules say, possibly behind the deposits' slots.
+ * seed as in lsg_submit_jobs.  Calls are serialised among themselves. */
+int lsg_verify_deposits(lsg_ctx* ctx, const uint8_t* data184, size_t n, const uint8_t* domain32, uint64_t seed,
+                        uint8_t* valid, int32_t* err);
 
 /* Test/bench input generation (not on the verify path): sig_i = sk_i * H(m_i) compressed,
  * pk_i = sk_i * G1 uncompressed; sks are 32-byte big-endian secret keys. */

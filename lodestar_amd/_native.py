@@ -26,6 +26,7 @@ LSG_ERROR = 2
 
 LSG_JOB_BATCHABLE = 1
 LSG_JOB_PRIORITY = 2
+LSG_JOB_VALIDATE_KEYS = 4  # KeyValidate on the device for every byte key of the job's sets
 
 BLST_NAMES = {
     0: "BLST_SUCCESS", 1: "BLST_BAD_ENCODING", 2: "BLST_POINT_NOT_ON_CURVE", 3: "BLST_POINT_NOT_IN_GROUP",
@@ -104,6 +105,7 @@ EXPORTS = [
     "lsg_final_submit_groups", "lsg_final_wait_groups", "lsg_aggregate_signatures",
     "lsg_signing_roots", "lsg_attestation_signing_roots", "lsg_jobs_partial_device", "lsg_final_submit_device",
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
+    "lsg_deposit_signing_roots", "lsg_verify_deposits",
 ]
 
 
@@ -157,6 +159,8 @@ def load_library(path=LIB_PATH):
         lib.lsg_pubkey_validate.argtypes = [vp, ctypes.c_char_p, u32, sz, ctypes.c_char_p, pi32]
         lib.lsg_signing_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
         lib.lsg_attestation_signing_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
+        lib.lsg_deposit_signing_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
+        lib.lsg_verify_deposits.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u64, ctypes.c_char_p, pi32]
         lib.lsg_aggregate_signatures.argtypes = [vp, ctypes.c_char_p, u32, ctypes.POINTER(u32), sz,
                                                  ctypes.c_char_p, pi32]
         lib.lsg_final_submit.argtypes = [vp, ctypes.c_char_p, sz, pu64]
@@ -520,6 +524,25 @@ class Context:
     def attestation_signing_roots(self, data128s, domains):
         """getAttestationDataSigningRoot from SSZ-serialized phase0.AttestationData (128 B each)."""
         return self._signing_roots("lsg_attestation_signing_roots", data128s, 128, domains)
+
+    def deposit_signing_roots(self, msgs88, domains):
+        """computeSigningRoot(DepositMessage) from SSZ-serialized DepositMessage (88 B each)."""
+        return self._signing_roots("lsg_deposit_signing_roots", msgs88, 88, domains)
+
+    def verify_deposits(self, data184s, domain, seed=0):
+        """processDeposit.ts:47-66 for SSZ-serialized DepositData (184 B each) under one deposit
+        domain: [(valid, err)] per deposit -- valid 1 when the validator would be added; err 0
+        when key and signature validated, else the BLST code of the first failing step."""
+        n = len(data184s)
+        if n == 0:
+            return []
+        assert all(len(d) == 184 for d in data184s) and len(domain) == 32
+        valid = ctypes.create_string_buffer(n)
+        err = (ctypes.c_int32 * n)()
+        self._check(self.lib.lsg_verify_deposits(self.h, b"".join(data184s), n, bytes(domain), seed, valid, err),
+                    "lsg_verify_deposits")
+        raw = valid.raw
+        return [(raw[i], err[i]) for i in range(n)]
 
     def hash_to_g2(self, msgs, dst=b"BLS_SIG_BLS12381G2_XMD:SHA-256_SSWU_RO_POP_"):
         if not msgs:

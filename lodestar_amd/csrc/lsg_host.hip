@@ -357,6 +357,11 @@ struct Slot {
   SegPlan msum;                  // msg_agg: per message, the masked scaled keys of the package group
   DevBuf d_mmask, d_PmP, d_Pm, d_pinfm, d_errm;
   bool single_keys = false;  // every set has exactly one key (key i is set i's)
+  // KeyValidate of the byte keys of LSG_JOB_VALIDATE_KEYS jobs: n_kv list items (staged key,
+  // its set) in the plan arena at kv_off, kv_off + n_kv; kv_set[i] != 0: set i's keys are on
+  // the list (empty when the package has no such job: nothing staged, nothing launched)
+  size_t n_kv = 0, kv_off = 0;
+  std::vector<uint8_t> kv_set;
   uint32_t pk_stride = 96;   // bytes per key slot in d_pk: 4 when every key is a table index
   // per-set state
   DevBuf d_ub, d_sigaff, d_siginf, d_seterr, d_pkp, d_pkerr, d_agg, d_P, d_pinf, d_H, d_hinf, d_rs, d_rs2, d_fall,
@@ -448,6 +453,8 @@ struct Dev {
   // validator pubkey table (lsg_pubkey_table_set): projective lane-form keys + validity bytes
   DevBuf d_pktab, d_pktab_ok;
   size_t pktab_n = 0, pktab_cap = 0;
+  // lsg_verify_deposits: the call's DepositData and their signing roots (the packages' messages)
+  DevBuf d_dep_in, d_dep_roots;
   // kernel times of the last package / call completed on this device (lsg_last_kernel_times),
   // read from the slot's timing events when it completed, before the slot can be reused
   std::vector<std::pair<const char*, float>> last_times;
@@ -465,6 +472,7 @@ struct lsg_ctx {
   // packages staged at the same time, `staging` counts the submissions in flight.
   std::shared_mutex tab_mu;
   std::mutex xmu;
+  std::mutex dep_mu;  // one lsg_verify_deposits at a time (they share d_dep_*), taken before `mu`
   int staging = 0;
   // coalescing (lsg_set_coalesce): packages of <= co_max_sets sets wait in `pending` while
   // co_inflight launches are on the device, then go out as one launch
@@ -1510,6 +1518,11 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
   } else {
     LSG_RC(run_pk_seg(s, *pkagg, P_<uint32_t>(s->d_agg)));  // (every staged key is in one set)
   }
+  // flagged jobs' byte keys: KeyValidate codes per list item (d_pkp is free in a package: the
+  // keys decode straight into their aggregates); applied to the sets after the signature stages
+  if (s->n_kv)
+    KL(s, "k_pk_keyvalidate", lsgk::pk_keyvalidate(S_(s), (int)s->n_kv, PL(s, s->kv_off), P_<uint8_t>(s->d_pk),
+                                                   P_<uint32_t>(s->d_pklen), P_<int32_t>(s->d_pkp)));
   KL(s, "k_pk_scale", lsgk::pk_scale(S_(s), n, P_<uint32_t>(s->d_agg), P_<uint64_t>(s->d_rnd), P_<uint32_t>(s->d_Pp),
                                      P_<uint32_t>(s->d_zP), P_<uint8_t>(s->d_pinf)));
   LSG_RC(batch_inv(s, 1, "binv_pk", P_<uint32_t>(s->d_zP), (size_t)n, P_<uint32_t>(s->d_zPi)));
@@ -1522,6 +1535,9 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
   else
     KL(s, "k_sig_subgroup", lsgk::sig_subgroup(S_(s), n, P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
                                                P_<int32_t>(s->d_seterr)));
+  if (s->n_kv)  // a key error beats a signature error (the reference validates the key first)
+    KL(s, "k_pk_keyvalidate_apply", lsgk::pk_keyvalidate_apply(S_(s), (int)s->n_kv, PL(s, s->kv_off + s->n_kv),
+                                                               P_<int32_t>(s->d_pkp), P_<int32_t>(s->d_seterr)));
   if (Ph.agg_g >= 0) {  // per message: sum of the package group's usable r_i pk_i, affine
     const Grp& g = Ph.groups[(size_t)Ph.agg_g];
     const size_t nm = Ph.n_magg;
@@ -1787,8 +1803,11 @@ int launch_sig_prep(Slot* s, bool scale, const std::vector<uint8_t>* mode, uint3
 // maybeBatch.ts:34-38).  False when the package group's partial is multiplied with other
 // partials before its verdict (a multi-device ticket, lsg_batch_partial): there every r_i is
 // random and nonzero, or two forged one-set shards (sig_a + D, sig_b - D) would pass together.
+// dev_msgs: the sets' 32-byte messages are already on this device, one per staged set in
+// staging order (lsg_verify_deposits: the signing roots never leave the GPU); the sets' host
+// msg bytes are placeholders then and are overwritten by a device copy.
 int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint64_t seed, int n_node,
-              const std::vector<size_t>* subs = nullptr, bool lone_ok = true) {
+              const std::vector<size_t>* subs = nullptr, bool lone_ok = true, const uint8_t* dev_msgs = nullptr) {
   timer_reset(s);
   s->plan.clear();
   memset(&s->stats, 0, sizeof(s->stats));
@@ -1875,7 +1894,35 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   for (size_t k : nonb)
     if (s->jobs[k].count == 1 && !nb_merge) noscale[s->jobs[k].first] = 1;
   const uint64_t th0 = trace_host() ? now_ns() : 0;
-  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &noscale, true));
+  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &noscale, dev_msgs == nullptr));
+  if (dev_msgs && !flat.empty())  // (placeholders are never merged: message i is set i's)
+    LSG_HIP(s, hipMemcpyAsync(s->d_msg.p, dev_msgs, 32 * flat.size(), hipMemcpyDeviceToDevice, s->st[0]));
+  // the byte keys of LSG_JOB_VALIDATE_KEYS jobs, compacted (table rows were validated when the
+  // node cached them: the flag leaves index keys alone)
+  s->n_kv = 0;
+  s->kv_set.clear();
+  bool any_kv = false;
+  for (size_t k = 0; k < nj && !any_kv; k++) any_kv = (s->jobs[k].flags & LSG_JOB_VALIDATE_KEYS) != 0;
+  if (any_kv) {
+    s->kv_set.assign(flat.size(), 0);
+    for (size_t k = 0; k < nj; k++) {
+      if (!(s->jobs[k].flags & LSG_JOB_VALIDATE_KEYS)) continue;
+      for (size_t i = s->jobs[k].first; i < s->jobs[k].first + s->jobs[k].count; i++)
+        if (flat[i]->pk_len != LSG_PK_INDEX && s->pk_cnt[i]) {
+          s->kv_set[i] = 1;
+          s->n_kv += s->pk_cnt[i];
+        }
+    }
+    s->kv_off = s->plan.size();
+    s->plan.resize(s->kv_off + 2 * s->n_kv);
+    size_t q = 0;
+    for (size_t i = 0; i < flat.size(); i++)  // (staging order: a set's keys are adjacent)
+      for (uint32_t k = 0; s->kv_set[i] && k < s->pk_cnt[i]; k++, q++) {
+        s->plan[s->kv_off + q] = (int32_t)(s->pk_first[i] + k);
+        s->plan[s->kv_off + s->n_kv + q] = (int32_t)i;
+      }
+    if (!s->n_kv) s->kv_set.clear();
+  }
   const uint64_t th1 = trace_host() ? now_ns() : 0;
   // phase-A groups, MSM groups first: the package group, then one per non-batchable job
   PhasePlan& A = s->phA;
@@ -2276,12 +2323,14 @@ int32_t first_pk_error(Slot* s, size_t* job_id) {
   const int32_t* pkerr = H_<int32_t>(s->h_pkerr);
   for (size_t k = 0; k < s->jobs.size(); k++) {  // jobs[k] are in caller order (job_ids ascending)
     const JobRec& J = s->jobs[k];
-    for (size_t i = J.first; i < J.first + J.count; i++)
+    for (size_t i = J.first; i < J.first + J.count; i++) {
+      if (!s->kv_set.empty() && s->kv_set[i]) continue;  // a validated key fails its set only
       for (uint32_t q = 0; q < s->pk_cnt[i]; q++)
         if (const int32_t e = pkerr[s->pk_first[i] + q]) {
           *job_id = s->job_ids[k];
           return e;
         }
+    }
   }
   return 0;
 }
@@ -2326,7 +2375,7 @@ int pkg_resolve(Slot* s, CtxLock* lk, int node_valid, int32_t pkfail) {
     size_t ej = 0;
     for (size_t j = s->sub_first[k]; j < s->sub_first[k + 1] && !e; j++)
       for (size_t i = s->jobs[j].first; i < s->jobs[j].first + s->jobs[j].count && !e; i++)
-        for (uint32_t q = 0; q < s->pk_cnt[i] && !e; q++)
+        for (uint32_t q = 0; q < s->pk_cnt[i] && !e && !(!s->kv_set.empty() && s->kv_set[i]); q++)
           if (pkerr[s->pk_first[i] + q]) {
             e = pkerr[s->pk_first[i] + q];
             ej = j - s->sub_first[k];
@@ -2717,7 +2766,7 @@ int pkg_exchange(lsg_ctx* c, int p) {
 // item 3), and host threads submitting packages to different slots stage them side by side.
 // Errors go to *err (t_err_sink), not to c->err.
 int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t seed, bool lone_ok, bool exch,
-              std::string* err) {
+              std::string* err, const uint8_t* dev_msgs = nullptr) {
   const int n = c->n_dev;
   std::vector<std::vector<size_t>> ids(n);
   {
@@ -2734,7 +2783,8 @@ int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t se
     (void)hipSetDevice(c->dev[d]->device);
     // distinct seeds per device for tests; 0 stays 0 (OS CSPRNG on every device)
     const uint64_t sd = seed ? seed + 0x9e3779b97f4a7c15ull * (uint64_t)d : 0;
-    rcs[d] = pkg_part1(&c->dev[d]->slots[p], jobs, ids[d], sd, (d == 0 && exch) ? n : 0, nullptr, lone_ok && !exch);
+    rcs[d] = pkg_part1(&c->dev[d]->slots[p], jobs, ids[d], sd, (d == 0 && exch) ? n : 0, nullptr, lone_ok && !exch,
+                       n == 1 ? dev_msgs : nullptr);
     t_err_sink = nullptr;
   };
   auto part2 = [&](int d) {
@@ -2823,7 +2873,7 @@ int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t se
 // and on return), staged with the lock released (stage_pkg), and its ticket committed under the
 // lock again.  A reserved slot is SLOT_STAGING: no other call takes, reserves or waits on it.
 int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint64_t seed, lsg_ticket* ticket,
-               bool lone_ok = true) {
+               bool lone_ok = true, const uint8_t* dev_msgs = nullptr) {
   int p = -1;
   for (int i = 0; i < LSG_SLOTS && p < 0; i++)
     if (c->dev[0]->slots[i].kind == SLOT_FREE) p = i;
@@ -2844,7 +2894,7 @@ int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint
   c->staging++;
   lk.unlock();
   std::string err;
-  const int rc = stage_pkg(c, p, jobs, n_jobs, seed, lone_ok, exch, &err);
+  const int rc = stage_pkg(c, p, jobs, n_jobs, seed, lone_ok, exch, &err, dev_msgs);
   lk.lock();
   (void)hipSetDevice(c->dev[0]->device);
   c->staging--;
@@ -3253,6 +3303,8 @@ void dev_destroy(Dev* d) {
   slot_destroy(&d->util);
   free_dev(d->d_pktab);
   free_dev(d->d_pktab_ok);
+  free_dev(d->d_dep_in);
+  free_dev(d->d_dep_roots);
   if (d->s_util) (void)hipStreamDestroy(d->s_util);
   for (hipStream_t st : d->s_fe)
     if (st) (void)hipStreamDestroy(st);
@@ -4036,10 +4088,11 @@ int lsg_aggregate_signatures(lsg_ctx* c, const uint8_t* sigs, uint32_t sig_len, 
   return LSG_OK;
 }
 
-// SSZ signing roots; kind 0: object roots given, 1: AttestationData bytes
+// SSZ signing roots; kind 0: object roots given, 1: AttestationData bytes,
+// 2: DepositMessage bytes
 static int signing_roots(lsg_ctx* c, int kind, const uint8_t* objs, size_t n, const uint8_t* domain, uint32_t dstride,
                          uint8_t* out32) {
-  const size_t ob = kind ? 128 : 32;
+  const size_t ob = kind == 2 ? 88 : (kind ? 128 : 32);
   if (!c || !domain || (dstride != 0 && dstride != 32) || (n && (!objs || !out32)) || n > 0x7fffffffull)
     return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);
@@ -4055,7 +4108,10 @@ static int signing_roots(lsg_ctx* c, int kind, const uint8_t* objs, size_t n, co
   LSG_HIP(s, hipMemcpyAsync(d_obj, objs, ob * n, hipMemcpyHostToDevice, s->st[0]));
   LSG_HIP(s, hipMemcpyAsync(d_dom, domain, 32 * nd, hipMemcpyHostToDevice, s->st[0]));
   const int nn = (int)n;
-  if (kind)
+  if (kind == 2)
+    KL(s, "k_deposit_signing_root",
+       lsgk::deposit_signing_root(S_(s), nn, d_obj, 88, d_dom, dstride, P_<uint8_t>(s->d_Fb)));
+  else if (kind)
     KL(s, "k_attestation_signing_root",
        lsgk::attestation_signing_root(S_(s), nn, d_obj, d_dom, dstride, P_<uint8_t>(s->d_Fb)));
   else
@@ -4074,6 +4130,111 @@ int lsg_signing_roots(lsg_ctx* c, const uint8_t* roots32, size_t n, const uint8_
 int lsg_attestation_signing_roots(lsg_ctx* c, const uint8_t* data128, size_t n, const uint8_t* domain32,
                                   uint32_t domain_stride, uint8_t* out32) {
   return signing_roots(c, 1, data128, n, domain32, domain_stride, out32);
+}
+
+int lsg_deposit_signing_roots(lsg_ctx* c, const uint8_t* msgs88, size_t n, const uint8_t* domain32,
+                              uint32_t domain_stride, uint8_t* out32) {
+  return signing_roots(c, 2, msgs88, n, domain32, domain_stride, out32);
+}
+
+// processDeposit.ts:47-66 for n deposits: signing roots on the device, then one single-set
+// batchable LSG_JOB_VALIDATE_KEYS job per deposit through the package machinery
+int lsg_verify_deposits(lsg_ctx* c, const uint8_t* data184, size_t n, const uint8_t* domain32, uint64_t seed,
+                        uint8_t* valid, int32_t* err) {
+  if (!c || !domain32 || (n && (!data184 || !valid || !err)) || n > 0x7fffffffull) return LSG_ERR_INVALID_ARG;
+  if (n == 0) return LSG_OK;
+  memset(valid, 0, n);
+  memset(err, 0, 4 * n);
+  std::lock_guard<std::mutex> dep(c->dep_mu);
+  Dev* d = c->dev[0];
+  const bool resident = c->n_dev == 1;  // the roots stay on the device as the packages' messages
+  std::vector<uint8_t> host_roots(resident ? 0 : 32 * n);
+  {
+    LSG_ENTER(c);
+    Slot* s = &d->util;
+    timer_reset(s);
+    LSG_RC(ensure(s, d->d_dep_in, 184 * n + 32));
+    LSG_RC(ensure(s, d->d_dep_roots, 32 * n));
+    uint8_t* d_in = P_<uint8_t>(d->d_dep_in);
+    LSG_HIP(s, hipMemcpyAsync(d_in, data184, 184 * n, hipMemcpyHostToDevice, s->st[0]));
+    LSG_HIP(s, hipMemcpyAsync(d_in + 184 * n, domain32, 32, hipMemcpyHostToDevice, s->st[0]));
+    KL(s, "k_deposit_signing_root",
+       lsgk::deposit_signing_root(S_(s), (int)n, d_in, 184, d_in + 184 * n, 0, P_<uint8_t>(d->d_dep_roots)));
+    if (!resident)  // a multi-device context stages each device's share from the host
+      LSG_HIP(s, hipMemcpyAsync(host_roots.data(), d->d_dep_roots.p, 32 * n, hipMemcpyDeviceToHost, s->st[0]));
+    LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+    keep_times(s);
+  }
+  static const uint8_t zero32[32] = {0};
+  std::vector<lsg_set> sets(n);
+  std::vector<lsg_job> jobs(n);
+  for (size_t i = 0; i < n; i++) {
+    const uint8_t* dd = data184 + 184 * i;
+    sets[i].pks = dd;
+    sets[i].pk_len = 48;
+    sets[i].n_pks = 1;
+    sets[i].msg = resident ? zero32 : host_roots.data() + 32 * i;
+    sets[i].msg_len = 32;
+    sets[i].sig = dd + 88;
+    sets[i].sig_len = 96;
+    jobs[i].sets = &sets[i];
+    jobs[i].n_sets = 1;
+    jobs[i].flags = LSG_JOB_BATCHABLE | LSG_JOB_VALIDATE_KEYS;
+  }
+  // packages of at most DEPOSIT_PKG deposits, at most DEPOSIT_INFLIGHT of them outstanding
+  // (enough to keep the device full; the other slots stay free for the host's own packages
+  // and its priority jobs), waited on in order
+  constexpr size_t DEPOSIT_PKG = 8192, DEPOSIT_INFLIGHT = 4;
+  struct Out {
+    lsg_ticket t;
+    size_t first, count;
+  };
+  std::vector<Out> out;  // outstanding, oldest first
+  std::vector<lsg_job_result> res(std::min(n, DEPOSIT_PKG));
+  int rc = LSG_OK;
+  auto wait_oldest = [&]() {
+    const Out o = out.front();
+    out.erase(out.begin());
+    const int w = lsg_wait_jobs(c, o.t, res.data(), nullptr);
+    if (w) return w;
+    for (size_t k = 0; k < o.count; k++) {
+      valid[o.first + k] = res[k].status == LSG_VALID ? 1 : 0;
+      err[o.first + k] = res[k].status == LSG_ERROR ? res[k].err_code : 0;
+    }
+    return (int)LSG_OK;
+  };
+  size_t pkg = 0;
+  for (size_t o = 0; o < n && !rc; pkg++) {
+    const size_t cnt = std::min(DEPOSIT_PKG, n - o);
+    lsg_ticket t = 0;
+    if (out.size() >= DEPOSIT_INFLIGHT) {
+      rc = wait_oldest();
+      pkg--;
+      continue;
+    }
+    {
+      CtxLock lk(c->mu);
+      const hipError_t he = hipSetDevice(d->device);
+      if (he != hipSuccess)  // (no early return: the tickets already out are drained below)
+        rc = fail_c(c, "hipSetDevice", he);
+      else
+        rc = submit_pkg(c, lk, jobs.data() + o, cnt, seed ? seed + 0x9e3779b97f4a7c15ull * pkg : 0, &t, true,
+                        resident ? P_<uint8_t>(d->d_dep_roots) + 32 * o : nullptr);
+    }
+    if (rc == LSG_ERR_BUSY && !out.empty()) {  // every slot is taken: free this call's oldest
+      rc = wait_oldest();
+      pkg--;
+      continue;
+    }
+    if (rc) break;
+    out.push_back({t, o, cnt});
+    o += cnt;
+  }
+  while (!out.empty()) {  // (after an error too: no ticket of this call stays outstanding)
+    const int w = wait_oldest();
+    if (!rc) rc = w;
+  }
+  return rc;
 }
 
 int lsg_sign(lsg_ctx* c, const uint8_t* sks32, const uint8_t* msgs, uint32_t msg_len, size_t n, uint8_t* out96) {

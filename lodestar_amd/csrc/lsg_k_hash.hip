@@ -295,7 +295,40 @@ __global__ void __launch_bounds__(64) k_attestation_signing_root(int n, const ui
   ssz_store(out32 + 32 * i, t);
 }
 
+// computeSigningRoot(ssz.phase0.DepositMessage, msg, domain) (block/processDeposit.ts:49-54)
+// from the SSZ serialization of DepositMessage (88 bytes: pubkey 48, withdrawalCredentials 32,
+// amount u64) at data + stride i (stride 184: the head of a DepositData): the Bytes48 key is
+// two chunks under one node, 3 fields -> 4 leaves, 2 levels, then SigningData -- 5 node
+// hashes per object
+__global__ void __launch_bounds__(64) k_deposit_signing_root(int n, const uint8_t* __restrict__ data, uint32_t stride,
+                                                             const uint8_t* __restrict__ domains, uint32_t dstride,
+                                                             uint8_t* __restrict__ out32) {
+  size_t i = gtid();
+  if (i >= (size_t)n) return;
+  const uint8_t* a = data + (size_t)stride * i;
+  uint32_t l0[8], l1[8], t[8], z[8];
+  for (int k = 0; k < 8; k++) z[k] = 0;
+  ssz_chunk(l0, a, 32);  // pubkey
+  ssz_chunk(t, a + 32, 16);
+  ssz_hash2(l0, t, l0);
+  ssz_chunk(l1, a + 48, 32);  // withdrawalCredentials
+  ssz_hash2(l0, l1, l0);
+  ssz_chunk(t, a + 80, 8);  // amount; leaf 3 is a zero chunk
+  ssz_hash2(t, z, l1);
+  ssz_hash2(l0, l1, t);  // DepositMessage.hashTreeRoot
+  ssz_chunk(z, domains + dstride * i, 32);
+  ssz_hash2(t, z, t);
+  ssz_store(out32 + 32 * i, t);
+}
+
 namespace lsgk {
+hipError_t deposit_signing_root(hipStream_t st, int n, const uint8_t* data, uint32_t stride, const uint8_t* domains,
+                                uint32_t dstride, uint8_t* out32) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_deposit_signing_root, dim3((n + 63) / 64), dim3(64), 0, st, n, data, stride, domains, dstride,
+                     out32);
+  return hipGetLastError();
+}
 hipError_t expand_msg(hipStream_t st, int n, const uint8_t* msg, const uint32_t* off, const uint32_t* len,
                       const uint8_t* dst, uint32_t dst_len, uint8_t* ub) {
   if (n <= 0) return hipSuccess;

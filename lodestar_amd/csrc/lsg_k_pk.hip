@@ -329,21 +329,62 @@ __global__ void LSG_KERNEL_ATTR k_agg_final(lsgk::AggTreeArgs a, int n_sets, con
   lane_store(agg, item, acc);
 }
 
-// KeyValidate: decode, reject infinity and points outside G1; pts receives the key as a
-// projective point (the identity for rejected keys); keys sit in 96-byte slots
-__global__ void LSG_KERNEL_ATTR k_pk_validate(int n, const uint8_t* __restrict__ pk, uint32_t len,
-                                              uint32_t* __restrict__ pts, int32_t* __restrict__ err) {
-  LANE_ITEM(n);
+// KeyValidate of one encoded key (PublicKey.fromBytes(pk, affine, true), processDeposit.ts:57):
+// size, decode, not infinity (BLST_PK_IS_INFINITY), in the r-torsion subgroup
+// (BLST_POINT_NOT_IN_GROUP).  Returns the BLST code; p = the key, the identity when rejected.
+LSG_DEVI int g1_key_validate(const uint8_t* __restrict__ bytes, uint32_t len, g1p_t& p) {
   g1a_t a;
   a.x = fp_zero();
   a.y = fp_zero();
   bool is_inf = false;
-  int e = g1_deserialize(a, is_inf, pk + 96 * item, (int)len);
+  int e = (len == 48 || len == 96) ? g1_deserialize(a, is_inf, bytes, (int)len) : LSG_BLST_INVALID_SIZE;
   if (e == 0 && is_inf) e = LSG_BLST_PK_IS_INFINITY;
-  const g1p_t p = e == 0 ? proj_from_aff(a) : proj_inf<fp_t>();
-  if (e == 0 && !g1_in_group(p)) e = LSG_BLST_POINT_NOT_IN_GROUP;
-  lane_store(pts, item, e == 0 ? p : proj_inf<fp_t>());
+  p = e == 0 ? proj_from_aff(a) : proj_inf<fp_t>();
+  if (e == 0 && !g1_in_group(p)) {
+    e = LSG_BLST_POINT_NOT_IN_GROUP;
+    p = proj_inf<fp_t>();
+  }
+  return e;
+}
+
+// KeyValidate: pts receives the key as a projective point (the identity for rejected keys);
+// keys sit in 96-byte slots
+__global__ void LSG_KERNEL_ATTR k_pk_validate(int n, const uint8_t* __restrict__ pk, uint32_t len,
+                                              uint32_t* __restrict__ pts, int32_t* __restrict__ err) {
+  LANE_ITEM(n);
+  g1p_t p;
+  const int e = g1_key_validate(pk + 96 * item, len, p);
+  lane_store(pts, item, p);
   if (lead) err[item] = e;
+}
+
+// KeyValidate of the keys a package's LSG_JOB_VALIDATE_KEYS jobs carry (processDeposit.ts:57,
+// blsToExecutionChange.ts:32 PublicKey.fromBytes(pk, affine, true)), over the compacted list of
+// those keys only: k_pk_validate's g1_key_validate, nothing stored but the code.
+// The membership test is one long dependent chain per lane pair, so this runs on the side
+// stream while the main stream hashes; it keeps no point and uses no LDS.
+__global__ void LSG_KERNEL_ATTR k_pk_keyvalidate(int n, const int32_t* __restrict__ keys, const uint8_t* __restrict__ pk,
+                                                 const uint32_t* __restrict__ pk_len, int32_t* __restrict__ code) {
+  LANE_ITEM(n);
+  const size_t key = (size_t)keys[item];
+  g1p_t p;
+  const int e = g1_key_validate(pk + 96 * key, pk_len[key], p);
+  if (lead) code[item] = e;
+}
+
+// one thread per list item: a failing key that is the first of its set to fail gives the set
+// its code (a good key returns at once; the scan back is over the set's earlier keys only)
+__global__ void __launch_bounds__(64) k_pk_keyvalidate_apply(int n, const int32_t* __restrict__ sets,
+                                                             const int32_t* __restrict__ code,
+                                                             int32_t* __restrict__ set_err) {
+  const size_t j = gtid();
+  if (j >= (size_t)n) return;
+  const int32_t e = code[j];
+  if (e == 0) return;
+  const int32_t set = sets[j];
+  for (size_t k = j; k > 0 && sets[k - 1] == set; k--)
+    if (code[k - 1] != 0) return;
+  set_err[set] = e;
 }
 
 // P_i = [r_i] agg_i, projective (r_i == 0: no scaling); zP_i = its Z (0 at infinity) for the
@@ -474,6 +515,15 @@ hipError_t agg_final(hipStream_t st, const AggTreeArgs& a, int n_sets, const int
 }
 hipError_t pk_validate(hipStream_t st, int n, const uint8_t* pk, uint32_t len, uint32_t* pts, int32_t* err) {
   LSG_LAUNCH_ITEMS(k_pk_validate, n, st, n, pk, len, pts, err);
+}
+hipError_t pk_keyvalidate(hipStream_t st, int n, const int32_t* keys, const uint8_t* pk, const uint32_t* pk_len,
+                          int32_t* code) {
+  LSG_LAUNCH_ITEMS(k_pk_keyvalidate, n, st, n, keys, pk, pk_len, code);
+}
+hipError_t pk_keyvalidate_apply(hipStream_t st, int n, const int32_t* sets, const int32_t* code, int32_t* set_err) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_pk_keyvalidate_apply, dim3((n + 63) / 64), dim3(64), 0, st, n, sets, code, set_err);
+  return hipGetLastError();
 }
 hipError_t pk_scale(hipStream_t st, int n, const uint32_t* agg, const uint64_t* rnd, uint32_t* Pp, uint32_t* zP,
                     uint8_t* pinf) {

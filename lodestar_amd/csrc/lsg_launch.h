@@ -24,6 +24,9 @@ hipError_t signing_root(hipStream_t st, int n, const uint8_t* roots, const uint8
                         uint8_t* out32);
 hipError_t attestation_signing_root(hipStream_t st, int n, const uint8_t* data, const uint8_t* domains,
                                     uint32_t dstride, uint8_t* out32);
+// DepositMessage signing roots: object i is the 88 bytes at data + stride * i
+hipError_t deposit_signing_root(hipStream_t st, int n, const uint8_t* data, uint32_t stride, const uint8_t* domains,
+                                uint32_t dstride, uint8_t* out32);
 
 // ---- signatures (lsg_k_sig.hip)                                       SURVEY 8a M2, M4
 hipError_t sig_decode(hipStream_t st, int n, const uint8_t* sig, const uint32_t* sig_len, uint32_t* sig_aff,
@@ -49,6 +52,14 @@ hipError_t sign(hipStream_t st, int n, const uint8_t* sks, const uint32_t* H, ui
 hipError_t pk_decode(hipStream_t st, int n, const uint8_t* pk, uint32_t stride, const uint32_t* pk_len, uint32_t* pts,
                      int32_t* err, const uint32_t* tab, const uint8_t* tab_ok, uint32_t tab_n);
 hipError_t pk_validate(hipStream_t st, int n, const uint8_t* pk, uint32_t len, uint32_t* pts, int32_t* err);
+// KeyValidate inside a package (LSG_JOB_VALIDATE_KEYS): item j of the compacted list is staged
+// key keys[j] (96-byte slots, byte keys only); code[j] = its BLST_* (0 = valid).  Then
+// keyvalidate_apply gives every set its first failing key's code: set_err[sets[j]] = code[j]
+// when no earlier item of the same set (items of a set are adjacent, in key order) failed --
+// over whatever the signature stages wrote there (the key is validated first).
+hipError_t pk_keyvalidate(hipStream_t st, int n, const int32_t* keys, const uint8_t* pk, const uint32_t* pk_len,
+                          int32_t* code);
+hipError_t pk_keyvalidate_apply(hipStream_t st, int n, const int32_t* sets, const int32_t* code, int32_t* set_err);
 // keys -> pubkey-table rows (lsgl::W_TAB words: affine point) + infinity flags + per-key errors
 hipError_t pk_gather_aff(hipStream_t st, int n, const uint8_t* pk, uint32_t stride, const uint32_t* pk_len, uint32_t* pts,
                          uint8_t* inf, int32_t* err, const uint32_t* tab, const uint8_t* tab_ok, uint32_t tab_n);

@@ -47,6 +47,10 @@
  * Extensions required by the north star (SURVEY.md 8b, not in the reference snapshot):
  *   opts.priority                  queue at the head instead of the tail
  *   verifySignatureSetsSameMessage per-set verdicts for sets sharing one message
+ * Objects that carry their own, untrusted keys (INTEGRATION.md):
+ *   opts.validatePubkeys           PublicKey.fromBytes(pk, affine, true) for the call's keys, on
+ *                                  the GPU inside the package (signatureSets/blsToExecutionChange.ts:32)
+ *   verifyDeposits                 block/processDeposit.ts:47-66 for a list of DepositData
  */
 
 const MAX_SIGNATURE_SETS_PER_JOB = 128;
@@ -56,6 +60,7 @@ const MAX_JOBS_CAN_ACCEPT_WORK = 512;
 
 const JOB_BATCHABLE = 1;
 const JOB_PRIORITY = 2;
+const JOB_VALIDATE_KEYS = 4; // LSG_JOB_VALIDATE_KEYS: KeyValidate of the job's byte keys on the GPU
 
 const LSG_INVALID = 0;
 const LSG_VALID = 1;
@@ -173,8 +178,8 @@ function EXEC(resolve) {
  * with the verdict and the JS thread keeps running meanwhile.  No retry: one job is one
  * maybeBatch call; an error rejects with its BLST code (e.g. BLST_INVALID_SIZE).
  */
-function verifyDirect(addon, ctx, sets, seed) {
-  const page = new JobPage(false, true, null);
+function verifyDirect(addon, ctx, sets, seed, validate = false) {
+  const page = new JobPage(false, true, null, validate);
   const p = page.push(sets);
   const pkg = packJobs([page, 0, 1], sets.length, undefined, 0);
   if (pkg.nJobs === 1) {
@@ -194,6 +199,35 @@ function getAggregatedPubkeysCount(sets) {
     else if (set.type === SignatureSetType.aggregate) n += set.pubkeys.length;
   }
   return n;
+}
+
+/**
+ * block/processDeposit.ts:47-66 for a list of deposits in one device pass (lsg_verify_deposits):
+ * KeyValidate of the deposit's own key, Signature.fromBytes(sig, affine, true) and the verify
+ * over computeSigningRoot(DepositMessage, domain).  depositDatas: SSZ-serialized DepositData,
+ * 184 bytes each (pubkey 48, withdrawalCredentials 32, amount u64 LE, signature 96), as a list
+ * of Uint8Arrays or one concatenated Uint8Array.  Returns one boolean per deposit: true exactly
+ * when processDeposit would go on to add the validator (a bad key or signature is false, never
+ * an error: the reference skips such a deposit).  The addon call is synchronous: the JS thread
+ * is blocked until the verdicts are back (~20 ms for 16,384 deposits, ~9 ms for a handful),
+ * as processDeposit's own blst calls block it in the reference; while the verifier's packages
+ * hold every pipeline slot the addon waits for one instead of failing.
+ */
+function verifyDepositsSync(addon, ctx, depositDatas, domain) {
+  let data = depositDatas;
+  if (!(data instanceof Uint8Array)) {
+    data = new Uint8Array(184 * depositDatas.length);
+    for (let i = 0; i < depositDatas.length; i++) {
+      if (!(depositDatas[i] instanceof Uint8Array) || depositDatas[i].length !== 184) throw Error("DepositData must be 184 serialized bytes");
+      data.set(depositDatas[i], 184 * i);
+    }
+  }
+  if (data.length % 184 !== 0) throw Error("DepositData must be 184 serialized bytes");
+  if (typeof addon.verifyDeposits !== "function") throw Error("the addon does not support verifyDeposits");
+  const r = addon.verifyDeposits(ctx, data, domain);
+  const out = new Array(r.valid.length);
+  for (let i = 0; i < out.length; i++) out[i] = r.valid[i] === 1;
+  return out;
 }
 
 function loadAddon() {
@@ -250,14 +284,22 @@ class Fifo {
  * later, than in the reference; verdicts do not depend on it).  A package takes jobs from the
  * head page onwards one job at a time, as prepareWork does (index.ts:400-418), so a page can
  * be spread over several packages; a page a package has taken from accepts no more jobs.
+ * The job flags are the page's: a page holds jobs of one kind only (batchable, priority,
+ * validate), so calls with and without opts.validatePubkeys never share a page -- they may
+ * share a package, where each job carries its own page's flag word.  One effect on timing: a
+ * batchable call of the other kind sends the open buffer to the queue before its 100 ms or
+ * 32-sig limit, so under alternating flagged and unflagged traffic unflagged jobs reach the
+ * queue earlier and in smaller pages than they would alone (later calls of that kind rejoin
+ * the queued tail page while it is open).  Verdicts do not depend on it.
  */
 const PAGE_JOBS = 8192;
 
 class JobPage {
   /** @param {number[]|null} added  per-job Date.now() at queueing (jobWaitTime metric) */
-  constructor(batchable, priority, added) {
+  constructor(batchable, priority, added, validate = false) {
     this.batchable = batchable;
     this.priority = priority;
+    this.validate = validate; // opts.validatePubkeys: its jobs carry JOB_VALIDATE_KEYS
     this.sets = []; // per job: its sets (dropped once packed)
     this.res = []; // per job: its promise's resolve function (undefined once settled)
     this.added = added;
@@ -363,7 +405,7 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
   let j = 0;
   for (let r = 0; r < ranges.length; r += 3) {
     const page = ranges[r];
-    const flags = (page.batchable ? JOB_BATCHABLE : 0) | (page.priority ? JOB_PRIORITY : 0);
+    const flags = (page.batchable ? JOB_BATCHABLE : 0) | (page.priority ? JOB_PRIORITY : 0) | (page.validate ? JOB_VALIDATE_KEYS : 0);
     const pageSets = page.sets;
     for (let q = ranges[r + 1], qEnd = ranges[r + 2]; q < qEnd; q++) {
       const sets = pageSets[q];
@@ -542,6 +584,13 @@ class BlsGpuVerifier {
     return this.addon.aggregateSignatures(this.ctx, groups);
   }
 
+  /** processDeposit.ts:47-66 for a list of deposits (verifyDepositsSync above): domain is
+   * computeDomain(DOMAIN_DEPOSIT, GENESIS_FORK_VERSION, ZERO_HASH); resolves to boolean[]. */
+  async verifyDeposits(depositDatas, domain) {
+    if (this.closed) throw new QueueError({code: QueueErrorCode.QUEUE_ABORTED});
+    return verifyDepositsSync(this.addon, this.ctx, depositDatas, domain);
+  }
+
   /** Sets not yet answered: queued, buffered and on the GPU. */
   pendingSigs() {
     return this.queuedSigs + (this.buffer ? this.buffer.nSigs : 0) + this.sigsInFlight;
@@ -559,7 +608,7 @@ class BlsGpuVerifier {
         // verifySignatureSetsMaybeBatch without the queue: no retry, errors reject
         const m = this.metrics && this.metrics.blsThreadPool;
         const timer = m ? m.mainThreadDurationInThreadPool.startTimer() : null;
-        const p = verifyDirect(this.addon, this.ctx, sets, this.seed);
+        const p = verifyDirect(this.addon, this.ctx, sets, this.seed, opts.validatePubkeys === true);
         if (timer) p.then(timer, timer);
         return p;
       }
@@ -629,9 +678,10 @@ class BlsGpuVerifier {
       return Promise.reject(new QueueError({code: QueueErrorCode.QUEUE_ABORTED}));
     }
     const added = this.metrics !== null;
+    const validate = opts.validatePubkeys === true;
     if (opts.priority === true) {
       // north-star extension: the job goes to the head of the queue, not through the buffer
-      const page = new JobPage(opts.batchable === true, true, added ? [] : null);
+      const page = new JobPage(opts.batchable === true, true, added ? [] : null, validate);
       const p = page.push(sets);
       page.open = false;
       this.priorityPages.push(page);
@@ -642,7 +692,7 @@ class BlsGpuVerifier {
     }
     if (opts.batchable === true) {
       const tail = this.tail;
-      if (tail !== null && tail.batchable && tail.open) {
+      if (tail !== null && tail.batchable && tail.open && tail.validate === validate) {
         // the buffer was flushed and is still waiting in the queue: join it there
         const p = tail.push(sets);
         this.queuedJobs++;
@@ -651,8 +701,13 @@ class BlsGpuVerifier {
         return p;
       }
       let buf = this.buffer;
+      if (buf !== null && buf.validate !== validate) {
+        // the buffer holds the other kind: it goes to the queue as it is, a new one opens
+        this._runBufferedJobs();
+        buf = null;
+      }
       if (buf === null) {
-        buf = this.buffer = new JobPage(true, false, added ? [] : null);
+        buf = this.buffer = new JobPage(true, false, added ? [] : null, validate);
         buf.firstPush = Date.now();
         this._armBufferTimer();
       }
@@ -661,8 +716,8 @@ class BlsGpuVerifier {
       return p;
     }
     let page = this.tail;
-    if (page === null || page.batchable || !page.open) {
-      page = new JobPage(false, false, added ? [] : null);
+    if (page === null || page.batchable || !page.open || page.validate !== validate) {
+      page = new JobPage(false, false, added ? [] : null, validate);
       this.jobs.push(page);
       this.tail = page;
     }
@@ -825,7 +880,8 @@ class BlsGpuVerifier {
 /**
  * BlsSingleThreadVerifier (chain/bls/singleThread.ts:14-35) on the GPU: each call is one
  * verifySignatureSetsMaybeBatch (verifyDirect: one priority job, no queue) with no retry; opts
- * are ignored, errors reject.  The reference blocks the event loop for the call; here the
+ * are ignored but for opts.validatePubkeys (the job carries JOB_VALIDATE_KEYS: an object's own
+ * key is validated whichever verifier createBlsVerifier chose), errors reject.  The reference blocks the event loop for the call; here the
  * promise settles when the GPU answers.  The duration is observed after the call as the
  * reference does (it observes the total and the per-set time; its startNs - endNs has the
  * sign inverted, here the duration is positive).
@@ -842,11 +898,11 @@ class BlsGpuSingleThreadVerifier {
     this.ctx = this.addon.open(Array.isArray(options.devices) ? options.devices : options.device || 0);
   }
 
-  async verifySignatureSets(sets) {
+  async verifySignatureSets(sets, opts = {}) {
     if (this.metrics && this.metrics.bls) this.metrics.bls.aggregatedPubkeys.inc(getAggregatedPubkeysCount(sets));
     // Count time after aggregating (serialisation happens inside verifyDirect)
     const startNs = process.hrtime.bigint();
-    const valid = await verifyDirect(this.addon, this.ctx, sets, this.seed);
+    const valid = await verifyDirect(this.addon, this.ctx, sets, this.seed, opts.validatePubkeys === true);
     // Don't use a try/catch, only count run without exceptions
     const endNs = process.hrtime.bigint();
     const totalSec = Number(endNs - startNs) / 1e9;
@@ -856,6 +912,12 @@ class BlsGpuSingleThreadVerifier {
       m.mainThreadDurationInThreadPool.observe(totalSec / sets.length);
     }
     return valid;
+  }
+
+  /** processDeposit.ts:47-66 for a list of deposits, as BlsGpuVerifier.verifyDeposits */
+  async verifyDeposits(depositDatas, domain) {
+    if (!this.ctx) throw new QueueError({code: QueueErrorCode.QUEUE_ABORTED});
+    return verifyDepositsSync(this.addon, this.ctx, depositDatas, domain);
   }
 
   async close() {

@@ -33,6 +33,10 @@
  *   pubkeyTableSet(ctx, firstIndex, pubkeys[]) -> errCodes[]          lsg_pubkey_table_set
  *       (a set may then carry pubkeyIndices: Uint32Array instead of pubkeys)
  *   hashToG2(ctx, message, dst) -> Uint8Array(192)                     lsg_hash_to_g2
+ *   verifyDeposits(ctx, data: n x 184 B, domain: 32 B) -> {valid: Uint8Array, err: Int32Array}
+ *                                                                      lsg_verify_deposits
+ *   pubkeyValidate(ctx, pks: n x pkLen B, pkLen) -> Int32Array         lsg_pubkey_validate
+ *       (these two throw "not supported" when the loaded library lacks the entry point)
  * Failures of the library itself (not verdicts) throw an Error carrying lsg_last_error().
  */
 #include <node_api.h>
@@ -42,6 +46,13 @@
 #include <string.h>
 
 #include "lodestar_bls.h"
+
+/* Entry points a library older than this addon may lack: weak, so that the addon still loads
+ * against it, and checked for NULL where they are called. */
+extern int lsg_verify_deposits(lsg_ctx* ctx, const uint8_t* data184, size_t n, const uint8_t* domain32, uint64_t seed,
+                               uint8_t* valid, int32_t* err) __attribute__((weak));
+extern int lsg_pubkey_validate(lsg_ctx* ctx, const uint8_t* pks, uint32_t pk_len, size_t n, uint8_t* out96,
+                               int32_t* err) __attribute__((weak));
 
 #define LSG_NAPI_THREADS 16 /* package threads per context: one outstanding package each */
 
@@ -888,6 +899,79 @@ static napi_value js_attestation_signing_roots(napi_env env, napi_callback_info 
   return out;
 }
 
+/* verifyDeposits(ctx, data: Uint8Array (n x 184 B SSZ DepositData), domain: Uint8Array(32)) ->
+ * {valid: Uint8Array(n), err: Int32Array(n)}: processDeposit.ts:47-66 for n deposits
+ * (lsg_verify_deposits; randomizers from the OS).  Synchronous: the calling thread is blocked for
+ * the whole call, including the wait for a pipeline slot while the package threads hold them all */
+static napi_value js_verify_deposits(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  lsg_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  const uint8_t *d, *dom;
+  size_t dl, doml;
+  if (argc < 3 || get_bytes(env, argv[1], &d, &dl) || get_bytes(env, argv[2], &dom, &doml) || dl % 184 || doml != 32) {
+    napi_throw_type_error(env, NULL, "lsg_napi: verifyDeposits(ctx, data: n x 184 B, domain: 32 B)");
+    return NULL;
+  }
+  if (!lsg_verify_deposits) {
+    napi_throw_error(env, NULL, "lsg_napi: the loaded library does not support verifyDeposits (no lsg_verify_deposits)");
+    return NULL;
+  }
+  const size_t n = dl / 184;
+  void *vp, *ep;
+  napi_value vab, eab, v, e, out;
+  NAPI_CALL(env, napi_create_arraybuffer(env, n ? n : 1, &vp, &vab));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, n, vab, 0, &v));
+  NAPI_CALL(env, napi_create_arraybuffer(env, 4 * (n ? n : 1), &ep, &eab));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, eab, 0, &e));
+  /* BUSY (nothing verified yet): the verifier's package threads hold every pipeline slot; back
+   * off until one of them is waited on, as the package threads themselves do (engine_main) */
+  int rc = LSG_OK;
+  for (int tries = 0; n; tries++) {
+    rc = lsg_verify_deposits(ctx, d, n, dom, 0, (uint8_t*)vp, (int32_t*)ep);
+    if (rc != LSG_ERR_BUSY || tries > 100000) break;
+    struct timespec ts = {0, 200000};
+    nanosleep(&ts, NULL);
+  }
+  if (rc) return throw_lsg(env, ctx, "lsg_verify_deposits", rc);
+  NAPI_CALL(env, napi_create_object(env, &out));
+  NAPI_CALL(env, napi_set_named_property(env, out, "valid", v));
+  NAPI_CALL(env, napi_set_named_property(env, out, "err", e));
+  return out;
+}
+
+/* pubkeyValidate(ctx, pks: Uint8Array (n x pkLen B), pkLen: 48 | 96) -> Int32Array(n): batched
+ * KeyValidate, BLST_* per key, 0 = valid (8f(2), lsg_pubkey_validate) */
+static napi_value js_pubkey_validate(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  lsg_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  const uint8_t* k;
+  size_t kl;
+  uint32_t pk_len = 0;
+  if (argc < 3 || get_bytes(env, argv[1], &k, &kl) || napi_get_value_uint32(env, argv[2], &pk_len) != napi_ok ||
+      (pk_len != 48 && pk_len != 96) || kl % pk_len) {
+    napi_throw_type_error(env, NULL, "lsg_napi: pubkeyValidate(ctx, pks: n x pkLen B, pkLen: 48 | 96)");
+    return NULL;
+  }
+  if (!lsg_pubkey_validate) {
+    napi_throw_error(env, NULL, "lsg_napi: the loaded library does not support pubkeyValidate (no lsg_pubkey_validate)");
+    return NULL;
+  }
+  const size_t n = kl / pk_len;
+  void* ep;
+  napi_value eab, e;
+  NAPI_CALL(env, napi_create_arraybuffer(env, 4 * (n ? n : 1), &ep, &eab));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, eab, 0, &e));
+  int rc = n ? lsg_pubkey_validate(ctx, k, pk_len, n, NULL, (int32_t*)ep) : LSG_OK;
+  if (rc) return throw_lsg(env, ctx, "lsg_pubkey_validate", rc);
+  return e;
+}
+
 /* sign(ctx, sks: Uint8Array(32n, big-endian), msgs: Uint8Array(32n)) -> Uint8Array(96n) and
  * skToPk(ctx, sks) -> Uint8Array(96n): test/bench input generation on the GPU (lsg_sign,
  * lsg_sk_to_pk), not on the verify path */
@@ -953,6 +1037,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"pubkeyTableSet", NULL, js_pubkey_table_set, NULL, NULL, NULL, napi_enumerable, NULL},
       {"aggregateSignatures", NULL, js_aggregate_signatures, NULL, NULL, NULL, napi_enumerable, NULL},
       {"attestationSigningRoots", NULL, js_attestation_signing_roots, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"verifyDeposits", NULL, js_verify_deposits, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"pubkeyValidate", NULL, js_pubkey_validate, NULL, NULL, NULL, napi_enumerable, NULL},
   };
   NAPI_CALL(env, napi_define_properties(env, exports, sizeof props / sizeof props[0], props));
   return exports;
