@@ -18,6 +18,13 @@
 //     worker.ts (phase B) and then the jobs of failing chunks (phase C) checked, on the
 //     per-set values still resident, so per-job verdicts and the batch_retries /
 //     batch_sigs_success counters are the reference's.
+// Which file holds what: this one has the device side -- streams, events, buffers, staging,
+// kernel launches, tickets, locks.  The policy over small integers is host-only code in
+// lsg_plan.hpp (namespace lsgp), tested on the CPU by tests/native/plancheck.cpp: the staging
+// order and 16-job chunks of a package (PkgShape), its phase-A groups (plan_groups), the
+// Miller items and segmented reductions of a phase (plan_phase, plan_seg), the deserializeSet
+// rule (first_key_error) and the verdict rules (resolve_package, which calls back into
+// run_fallback_phase here for every phase B0 / B / C1 / C2 it needs).
 // Per device a context owns LSG_SLOTS pipeline slots (two streams each, all buffers
 // preallocated by lsg_reserve); several devices share one ticket (whole jobs per device, one
 // all-gather of the 576-byte partials, one node final exponentiation: SURVEY.md 8e).
@@ -46,8 +53,10 @@
 #include "lsg_layout.h"
 #include "lsg_serial.h"
 #include "lsg_ab.h"
+#include "lsg_plan.hpp"
 
 using namespace lsgl;
+using namespace lsgp;
 
 namespace {
 
@@ -124,126 +133,6 @@ struct Timer {
   hipEvent_t a, b;
 };
 
-// chunkifyMaximizeChunkSize (multithread/utils.ts:4-19)
-std::vector<std::pair<size_t, size_t>> chunkify(size_t len, size_t min_per_chunk) {
-  std::vector<std::pair<size_t, size_t>> out;
-  size_t chunk_count = len / min_per_chunk;
-  if (chunk_count <= 1) {
-    out.push_back({0, len});
-    return out;
-  }
-  size_t per = (len + chunk_count - 1) / chunk_count;
-  for (size_t i = 0; i < len; i += per) out.push_back({i, std::min(len, i + per)});
-  return out;
-}
-
-
-// ---- segmented-reduction plans (lsgk::seg_reduce): int32 words appended to a slot's plan
-// arena, uploaded once per phase
-struct SegPass {
-  int ips_log2 = 0, n_chunks = 0;
-  size_t chunk_off = 0;  // words into the arena
-  int src = 0;           // 0: the reduction's input, 1/2: tmp buffer A/B
-  int tmp_out = 1;       // tmp buffer (1/2) that negative outputs go to
-};
-struct SegPlan {
-  int op = 0;
-  bool has_idx = false;
-  size_t idx_off = 0;
-  std::vector<SegPass> passes;
-  size_t tmp_items = 0;  // per tmp buffer
-};
-constexpr int SEG_FOLD = 16;  // at most this many serial folds per lane pair within one pass
-// Fp12 products (op 2) cost ~50 us each on one lane pair: their passes fold at most 4 terms
-// per pair before the butterfly (an 8193-term package product: 17 serial products in two
-// passes instead of 28)
-constexpr int SEG_FOLD_FP12 = 4;
-// work-bound passes (>= SEG_WIDE_PAIRS lane pairs at a wave's 32 pairs per segment): up to 64
-// folds per pair
-constexpr int SEG_FOLD_WIDE = 64;
-constexpr size_t SEG_WIDE_PAIRS = 131072;
-
-// lane pairs per chunk (log2): enough that the longest segment fits one chunk of SEG_FOLD
-// folds per pair (one pass), and at least a quarter of the mean length (latency: folds are
-// serial, the butterfly is log2(ips) steps); at most a wave's 32 pairs
-int ips_for(double avg, int32_t max_len, int fold) {
-  int l = 0;
-  while (l < 5 && ((int32_t)(fold << l) < max_len || (double)(2 << l) * 4.0 <= avg)) l++;
-  return l;
-}
-
-// Segments s = 0..ns-1: elements [seg_off[s], seg_off[s] + seg_len[s]) of the idx list (at
-// idx_off in the arena; has_idx) or of the input itself; result s goes to dst[dst_base + s].
-SegPlan plan_seg(std::vector<int32_t>& A, int op, const std::vector<int32_t>& seg_off,
-                 const std::vector<int32_t>& seg_len, bool has_idx, size_t idx_off, int32_t dst_base) {
-  SegPlan P;
-  P.op = op;
-  P.has_idx = has_idx;
-  P.idx_off = idx_off;
-  const size_t ns = seg_len.size();
-  if (ns == 0) return P;
-  size_t total = 0;
-  for (int32_t l : seg_len) total += (size_t)l;
-  // pending: (segment, element offset, length, source) still to reduce
-  struct Pend {
-    int32_t seg, off, len;
-  };
-  std::vector<Pend> cur(ns);
-  for (size_t s = 0; s < ns; s++) cur[s] = {(int32_t)s, seg_off[s], seg_len[s]};
-  double avg = (double)total / (double)ns;
-  int src = 0, tmp_out = 1;
-  while (!cur.empty()) {
-    SegPass pass;
-    int32_t max_len = 0;
-    for (const Pend& p : cur) max_len = std::max(max_len, p.len);
-    int fold = op == 2 ? SEG_FOLD_FP12 : SEG_FOLD;
-    pass.ips_log2 = ips_for(avg, max_len, fold);
-    // many segments (a block body's ~8k aggregations of ~450 keys): the launch is work-bound,
-    // and every butterfly level costs each lane pair one operation, so use as few pairs per
-    // chunk as keep the chip full, folding up to SEG_FOLD_WIDE terms each
-    if (op != 2 && (cur.size() << 5) >= SEG_WIDE_PAIRS) {
-      const int wide = (int)lsg_ab_long("LSG_SEG_FOLD_WIDE", SEG_FOLD_WIDE);  // (A/B build)
-      int l = 0;
-      while (l < pass.ips_log2 && (int32_t)(wide << l) < max_len) l++;
-      pass.ips_log2 = l;
-      fold = wide;
-    }
-    pass.src = src;
-    pass.tmp_out = tmp_out;
-    const int32_t cap = (int32_t)((1 << pass.ips_log2) * fold);
-    pass.chunk_off = A.size();
-    std::vector<Pend> nxt;
-    int32_t t = 0;
-    size_t nxt_total = 0;
-    for (const Pend& p : cur) {
-      if (p.len <= cap) {
-        A.push_back(p.off);
-        A.push_back(p.len);
-        A.push_back(dst_base + p.seg);
-        pass.n_chunks++;
-      } else {
-        const int32_t first = t;
-        for (int32_t o = 0; o < p.len; o += cap) {
-          A.push_back(p.off + o);
-          A.push_back(std::min(cap, p.len - o));
-          A.push_back(-(t + 1));
-          t++;
-          pass.n_chunks++;
-        }
-        nxt.push_back({p.seg, first, t - first});
-        nxt_total += (size_t)(t - first);
-      }
-    }
-    P.tmp_items = std::max(P.tmp_items, (size_t)t);
-    P.passes.push_back(pass);
-    avg = nxt.empty() ? 1.0 : (double)nxt_total / (double)nxt.size();
-    cur.swap(nxt);
-    src = tmp_out;  // the next pass reads this pass's partial results, contiguously
-    tmp_out = tmp_out == 1 ? 2 : 1;
-  }
-  return P;
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------------- state
@@ -275,41 +164,6 @@ struct MergeTicket {
 
 struct Dev;
 
-// One RLC group: sets [first, first + len) (a contiguous range: the package group, one
-// non-batchable job, one 16-job chunk or one job).
-struct Grp {
-  size_t first = 0, len = 0;
-  bool msm = false;
-};
-
-// ---- group stages of one phase (no host synchronisation).  Groups with msm sum their
-// signatures by the bucket MSM over the unscaled points in d_rs (MSM groups must come first);
-// the rest sum the scaled points in rs.  Then per group ML(-G1, S_g) on a row, the product
-// with the group's Miller items (fall: items [0, n_items) followed by one slot per group),
-// the canonical product F_g (d_Fb, D2H into h_blob when export), and FE(F_g) into d_verdict.
-struct PhasePlan {
-  std::vector<Grp> groups;
-  size_t n_msm = 0;
-  SegPlan buckets, bits, sums, prod;
-  size_t n_items = 0;   // Miller items of the phase's groups (fall slots 0 .. n_items-1)
-  size_t item_off = 0;  // item_first / item_cnt in the plan arena
-  size_t term_base = 0;  // fall slot of group g's ML(-G1, S_g) term: term_base + g
-  // per group, optional set sub-ranges items must not cross (the package group's 16-job
-  // chunks); sub_items = the item range of every sub-range, in order
-  std::vector<std::vector<std::pair<size_t, size_t>>> sub;
-  std::vector<std::pair<int32_t, int32_t>> sub_items;
-  // reuse: the groups' products take their items from an earlier phase (given item ranges)
-  bool reuse_items = false;
-  std::vector<std::pair<int32_t, int32_t>> given;
-  // host copy of the items (first set, set count): phase C's item-aligned job groups
-  std::vector<int32_t> it_first, it_cnt;
-  bool single_items = false;  // every item is one set: the list form of the Miller loop runs
-  // one Miller pair per distinct message for group agg_g (>= 0): its items are the n_magg
-  // message items (plan arena at magg_off) after the n_set_items per-set items
-  int agg_g = -1;
-  size_t n_magg = 0, magg_off = 0, n_set_items = 0;
-};
-
 // PublicKey.aggregate as the batch-affine pairwise tree (lsg_k_pk.hip k_agg_*, lsg_launch.h
 // AggTreeArgs): L levels, T items per lane pair, n_c0 level-0 lane pairs, N0 level-0 points;
 // plan arena offsets of the per-block set map, the per-set (o0, len, pk0) and k_agg_final's
@@ -322,11 +176,6 @@ struct AggPlan {
   size_t blk_off = 0, o0_off = 0, len_off = 0, pk0_off = 0, src_off = 0;
 };
 constexpr size_t AGG_TREE_MIN_KEYS = 32768;  // smaller packages: the serial fold + butterfly
-
-struct JobRec {
-  size_t first = 0, count = 0;  // staged set range
-  uint32_t flags = 0;
-};
 
 struct Slot {
   Dev* d = nullptr;
@@ -345,7 +194,6 @@ struct Slot {
   DevBuf d_sig, d_siglen, d_msg, d_msgoff, d_msglen, d_pk, d_pklen, d_rnd, d_mode, d_dst;
   HostBuf h_arena;
   size_t n_sets = 0, n_pks = 0;
-  std::vector<uint32_t> pk_cnt, pk_first;
   std::vector<uint64_t> rnd;
   // distinct messages of the staged package: set i hashes message msg_id[i] (n_msgs of them);
   // msg_dedup when some sets share one (a committee's attestations sign one AttestationData)
@@ -358,10 +206,9 @@ struct Slot {
   DevBuf d_mmask, d_PmP, d_Pm, d_pinfm, d_errm;
   bool single_keys = false;  // every set has exactly one key (key i is set i's)
   // KeyValidate of the byte keys of LSG_JOB_VALIDATE_KEYS jobs: n_kv list items (staged key,
-  // its set) in the plan arena at kv_off, kv_off + n_kv; kv_set[i] != 0: set i's keys are on
-  // the list (empty when the package has no such job: nothing staged, nothing launched)
+  // its set) in the plan arena at kv_off, kv_off + n_kv; shape.kv_set[i] != 0: set i's keys are
+  // on the list (empty when the package has no such job: nothing staged, nothing launched)
   size_t n_kv = 0, kv_off = 0;
-  std::vector<uint8_t> kv_set;
   uint32_t pk_stride = 96;   // bytes per key slot in d_pk: 4 when every key is a table index
   // per-set state
   DevBuf d_ub, d_sigaff, d_siginf, d_seterr, d_pkp, d_pkerr, d_agg, d_P, d_pinf, d_H, d_hinf, d_rs, d_rs2, d_fall,
@@ -392,42 +239,26 @@ struct Slot {
   // ticket state
   int kind = SLOT_FREE;
   uint64_t serial = 0;
-  std::vector<JobRec> jobs;         // this device's share of the package, caller order
-  std::vector<size_t> job_ids;      // caller job index of jobs[k]
-  std::vector<size_t> batch_order;  // indices into jobs: batchable jobs in staging order
-  size_t nb_sets = 0;               // sets of the batchable jobs (staged first)
-  std::vector<Grp> groups;          // phase-A groups (MSM groups first)
-  int big_g = -1;                   // the package group's index in groups
-  int K = 4;                        // Miller pairs per item for this package
-  std::vector<std::pair<int32_t, int32_t>> chunk_items;  // package mode: per chunk, its phase-A items
-  bool chunk_mode = false;          // phase A ran one group per 16-job chunk (LSG_PACKAGE_GROUP=0)
-  std::vector<int> chunk_group;     // chunk mode: per chunk of batch_order, its phase-A group
-  std::vector<int> sub_big;         // a coalesced launch: per sub-package, its package group (-1: none)
-  std::vector<int> job_group;       // per job: its phase-A group (non-batchable), else -1
-  // the non-batchable jobs' merged group (-1: one group per job) and, per job, its phase-A
-  // items (the merged group's items never cross a job: a failing merged group is localised
-  // per job over them)
-  int nb_g = -1;
-  std::vector<std::pair<int32_t, int32_t>> nb_items;
+  // this device's share of the package (jobs in staging order, sub-package bounds of a
+  // coalesced launch, per-set key counts), its phase-A groups and the switches read for it
+  PkgShape shape;
+  GroupPlan gp;
+  Switches sw;
+  int K = 4;  // Miller pairs per item for this package
   std::vector<lsg_job_result> results;
   lsg_stats stats;
   bool has_node = false;  // this slot computed the node check (device 0 of a multi-device ticket)
   size_t n_jobs = 0;      // device 0: the ticket's job count
-  // the package group is one set verified unscaled (r_i = 0, a plain verify): its partial is
-  // raised to a fresh 64-bit randomizer before it leaves the slot (lsg_jobs_partial*)
-  bool lone_unscaled = false;
+  // (gp.lone_unscaled: the package group is one set verified unscaled, r_i = 0, a plain verify:
+  // its partial is raised to a fresh 64-bit randomizer before it leaves the slot, lsg_jobs_partial*)
   uint64_t seed = 0;  // the package's randomizer seed (0: OS CSPRNG)
   DevBuf d_xport;
   HostBuf h_xport;
   // multi-device ticket: the package group's final exponentiation was not launched -- the
   // node check over every device's partial decides, and this one runs only if that fails
   bool big_fe_pending = false;
-  // coalesced launch (lsg_set_coalesce): n_sub caller packages in one slot.  sub_first: their
-  // job-index bounds in the merged job list; bpos_first: their bounds in batch_order.  Each
-  // one keeps its own 16-job chunks, deserialisation rule and counters; the slot is freed
-  // when every sub-package's ticket has been waited on.
-  int n_sub = 0;
-  std::vector<size_t> sub_first, bpos_first;
+  // coalesced launch (lsg_set_coalesce): shape.n_sub caller packages in one slot, each with
+  // its own counters; the slot is freed when every sub-package's ticket has been waited on.
   std::vector<uint64_t> sub_serial;
   std::vector<lsg_stats> sub_stats;
   std::vector<int32_t> sub_pkfail;
@@ -742,28 +573,6 @@ int slot_ready(Dev* d, Slot* s, int index) {
   return rc;
 }
 
-// the 16-job chunks (worker.ts:51) of the slot's batchable jobs as batch_order positions:
-// over the whole package, or per sub-package of a coalesced launch (never across two)
-std::vector<std::pair<size_t, size_t>> slot_chunks(const Slot* s) {
-  if (s->n_sub == 0) return chunkify(s->batch_order.size(), 16);
-  std::vector<std::pair<size_t, size_t>> out;
-  for (int k = 0; k < s->n_sub; k++) {
-    const size_t a = s->bpos_first[k], b = s->bpos_first[k + 1];
-    if (b == a) continue;
-    for (auto& c : chunkify(b - a, 16)) out.push_back({a + c.first, a + c.second});
-  }
-  return out;
-}
-// sub-package of a batch_order position / of a job (coalesced launches; 0 otherwise)
-int sub_of_pos(const Slot* s, size_t q) {
-  if (s->n_sub == 0) return 0;
-  return (int)(std::upper_bound(s->bpos_first.begin(), s->bpos_first.end(), q) - s->bpos_first.begin()) - 1;
-}
-int sub_of_job(const Slot* s, size_t j) {
-  if (s->n_sub == 0) return 0;
-  return (int)(std::upper_bound(s->sub_first.begin(), s->sub_first.end(), j) - s->sub_first.begin()) - 1;
-}
-
 // ---- sizes
 // Miller pairs per item (one shared f and its squarings): K = 4 does the least work per set,
 // but one item is one lane pair, so a small package has few items and its accumulation wave
@@ -787,38 +596,47 @@ int miller_k_for(size_t n_sets) {
 // point round trips cost more than the four products per key the affine additions save.
 bool agg_tree_on() { return lsg_ab_long("LSG_AGG_TREE", 0) != 0; }
 
-// Minimum RLC group size for the bucket MSM (A/B build: env LSG_MSM_MIN_GROUP).  By operation
-// count the MSM wins from ~4 sets (2-bit windows: ~24 bucket additions plus 4 of the group's 64
-// bit sums, ~1k Fp products, against ~2.25k for a 64-bit scalar multiplication; the group's
-// Horner program ~4k more), but the per-set [r_i] sig_i kernel runs near 0.3 of the mad peak
-// and the bucket and bit-sum reductions far below it, plus a Horner program per group: on
-// config C (64 groups of 128 sets) 1.05-1.08M sets/s without the MSM against 1.01M with it
+// The switches of lsg_plan.hpp's plans and verdict rules (the A/B build reads the environment
+// here, once per package: pkg_part1; the shipped library's values are constants).
+// LSG_MSM_MIN_GROUP, the minimum RLC group size for the bucket MSM: by operation count the MSM
+// wins from ~4 sets (2-bit windows: ~24 bucket additions plus 4 of the group's 64 bit sums, ~1k
+// Fp products, against ~2.25k for a 64-bit scalar multiplication; the group's Horner program
+// ~4k more), but the per-set [r_i] sig_i kernel runs near 0.3 of the mad peak and the bucket
+// and bit-sum reductions far below it, plus a Horner program per group: on config C (64 groups
+// of 128 sets) 1.05-1.08M sets/s without the MSM against 1.01M with it
 // (profiles/r04_msm_ab.txt).  The MSM stays for groups of 256 and more (8-bit windows: the
 // firehose's package group, the fallback phases' halves).
-size_t msm_min_group() {
-  const long x = lsg_ab_long("LSG_MSM_MIN_GROUP", 256);
-  return x < 1 ? (size_t)1 : (size_t)x;
+// LSG_PACKAGE_GROUP=0: phase A as the reference batches it, one RLC group per 16-job chunk
+// instead of one package group (A/B and the equivalence test of the two modes).
+// LSG_SUB_GROUPS=0: a coalesced launch as round 3's one group per 16-job chunk instead of one
+// package group per sub-package.
+// LSG_NB_MERGE=0: one group per non-batchable job instead of ONE RLC group for all of them
+// (>= 2 with sets), localised per job only when it fails.  Each job's verdict is its own
+// validity either way (worker.ts:88-96: such a job is verified alone), and non-batchable jobs
+// never enter the batch counters.
+// LSG_B0_MIN / LSG_B0_RUN (phase B0): with at least B0_MIN chunks to check, runs of up to B0_RUN
+// consecutive chunks are checked as one group first (0: off).
+// LSG_MSG_AGG=0: one Miller pair per set instead of one per distinct message in the package
+// group (read per package, so that a test can compare both forms in one process).
+Switches read_switches() {
+  Switches w;
+  w.package_group = lsg_ab_long("LSG_PACKAGE_GROUP", 1) != 0;
+  w.sub_groups = lsg_ab_long("LSG_SUB_GROUPS", 1) != 0;
+  w.nb_merge = lsg_ab_long("LSG_NB_MERGE", 1) != 0;
+  w.msg_agg = lsg_ab_long("LSG_MSG_AGG", 1) != 0;
+  w.msm_min_group = (size_t)std::max(1L, lsg_ab_long("LSG_MSM_MIN_GROUP", 256));
+  w.b0_min = (size_t)std::max(0L, lsg_ab_long("LSG_B0_MIN", 64));
+  w.b0_run = (size_t)std::max(2L, lsg_ab_long("LSG_B0_RUN", 4));
+  w.seg_fold_wide = (int)lsg_ab_long("LSG_SEG_FOLD_WIDE", SEG_FOLD_WIDE);
+  w.slp_items = slp_items_max();
+  return w;
 }
-// Window width c of a group's bucket MSM (plan_phase): per set 64/c digits (bucket
-// additions), per group the 64 bit sums over 2^(c-1) buckets each.  n sets cost about
-// n (64/c) + 2^(c-1) 64 G2 additions: c = 2 below 48 sets, 4 below 256, 8 from there.
-int msm_window_bits(size_t n) { return n >= 256 ? 8 : (n >= 48 ? 4 : 2); }
-
-// Phase A as the reference batches it: one RLC group per 16-job chunk instead of one package
-// group (env LSG_PACKAGE_GROUP=0; A/B and the equivalence test of the two modes)
-bool package_group_mode() { return lsg_ab_long("LSG_PACKAGE_GROUP", 1) != 0; }
-// A coalesced launch with one package group per sub-package (A/B build: LSG_SUB_GROUPS=0 gives
-// round 3's one group per 16-job chunk)
-bool sub_groups_on() { return lsg_ab_long("LSG_SUB_GROUPS", 1) != 0; }
-// A package's non-batchable jobs (>= 2 of them with sets) verified as ONE RLC group, localised
-// per job only when it fails (A/B build: LSG_NB_MERGE=0 gives one group per job).  Each job's
-// verdict is its own validity either way (worker.ts:88-96: such a job is verified alone), and
-// non-batchable jobs never enter the batch counters.
-bool nb_merge_on() { return lsg_ab_long("LSG_NB_MERGE", 1) != 0; }
-// Phase B0 (pkg_resolve): with at least this many chunks to check, runs of up to
-// LSG_B0_RUN consecutive chunks are checked as one group first (0: off)
-size_t b0_min_chunks() { return (size_t)std::max(0L, lsg_ab_long("LSG_B0_MIN", 64)); }
-size_t b0_run() { return (size_t)std::max(2L, lsg_ab_long("LSG_B0_RUN", 4)); }
+// plan_seg for a slot's plan arena
+SegPlan slot_seg(Slot* s, int op, const std::vector<int32_t>& seg_off, const std::vector<int32_t>& seg_len, bool has_idx,
+                 size_t idx_off, int32_t dst_base) {
+  return plan_seg(s->plan, op, seg_off, seg_len, has_idx, idx_off, dst_base,
+                  (int)lsg_ab_long("LSG_SEG_FOLD_WIDE", SEG_FOLD_WIDE));
+}
 
 void binv_sizes(size_t n, size_t* lv, size_t* iv);
 size_t binv_lv_words(size_t n) {
@@ -1038,9 +856,6 @@ int batch_inv(Slot* s, int ws, const char* name, const uint32_t* v, size_t n, ui
 // Packages of up to LSG_SLP_ITEMS sets (default 2048; 0: never) run one-set Miller items as
 // straight-line programs (lsg_slp.hip, one workgroup per set, ~0.8 ms) instead of the fused
 // kernel, whose latency is one full loop per lane whatever the package size (~5.4 ms).
-// one Miller pair per distinct message in the package group (LSG_MSG_AGG=0: one per set);
-// read per package, so that a test can compare both forms in one process
-static bool msg_agg_on() { return lsg_ab_long("LSG_MSG_AGG", 1) != 0; }
 
 size_t slp_items_max() {
   const long v = lsg_ab_long("LSG_SLP_ITEMS", 2048);
@@ -1107,8 +922,8 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   uint64_t* rnd = (uint64_t*)(A + o_rnd);
   siglen[0] = msgoff[0] = msglen[0] = pklen[0] = 0;
   rnd[0] = 0;
-  s->pk_cnt.resize(n);
-  s->pk_first.resize(n);
+  s->shape.pk_cnt.resize(n);
+  s->shape.pk_first.resize(n);
   s->rnd.resize(n);
   size_t mo = 0, po = 0, nm = 0;
   bool single = npk == n;
@@ -1179,8 +994,8 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
       mo += q->msg_len;
       nm++;
     }
-    s->pk_cnt[i] = q->n_pks;
-    s->pk_first[i] = (uint32_t)po;
+    s->shape.pk_cnt[i] = q->n_pks;
+    s->shape.pk_first[i] = (uint32_t)po;
     if (q->n_pks != 1) single = false;
     if (all_index) {  // the set's indices are contiguous in the caller's buffer
       std::fill(pklen + po, pklen + po + q->n_pks, (uint32_t)LSG_PK_INDEX);
@@ -1247,162 +1062,6 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   return LSG_OK;
 }
 
-// ---- Miller items: <= K consecutive sets of one range (group); item_first / item_cnt go to
-// the arena.  Returns the number of items; set_item (optional) maps set -> item.
-size_t plan_items(Slot* s, const std::vector<std::pair<size_t, size_t>>& ranges, size_t* off,
-                  std::vector<int32_t>* set_item, std::vector<std::pair<int32_t, int32_t>>* range_items,
-                  std::vector<int32_t>* host_first = nullptr, std::vector<int32_t>* host_cnt = nullptr) {
-  const size_t K = (size_t)s->K;
-  std::vector<int32_t> first, cnt;
-  for (auto& r : ranges) {
-    const int32_t i0 = (int32_t)first.size();
-    for (size_t i = r.first; i < r.second; i += K) {
-      size_t c = std::min(K, r.second - i);
-      if (set_item)
-        for (size_t k = 0; k < c; k++) (*set_item)[i + k] = (int32_t)first.size();
-      first.push_back((int32_t)i);
-      cnt.push_back((int32_t)c);
-    }
-    if (range_items) range_items->push_back({i0, (int32_t)first.size()});
-  }
-  *off = s->plan.size();
-  s->plan.insert(s->plan.end(), first.begin(), first.end());
-  s->plan.insert(s->plan.end(), cnt.begin(), cnt.end());
-  if (host_first) *host_first = first;
-  if (host_cnt) *host_cnt = cnt;
-  return first.size();
-}
-
-int plan_phase(Slot* s, PhasePlan& Ph) {
-  std::vector<int32_t>& A = s->plan;
-  const size_t ng = Ph.groups.size();
-  Ph.n_msm = 0;
-  while (Ph.n_msm < ng && Ph.groups[Ph.n_msm].msm) Ph.n_msm++;
-  // bucket MSM: per MSM group, bucket (w, d) = the sets whose w-th c-bit digit of r_i is d.
-  // c = 8 (8 windows x 255 buckets) for large groups; c = 4 (16 x 15) below MSM_C8_MIN sets,
-  // where 2040 buckets' bit sums would cost more than the sets' bucket additions (a block's
-  // 128-set groups: 16 additions per set + 512 per group instead of a 64-bit scalar
-  // multiplication per set).  Buckets are numbered compactly (group bases); bit k = c w + j
-  // sums the buckets (w, d) whose digit d has bit j set, so every group has 64 bit sums and
-  // one Horner program whatever its c.
-  if (Ph.n_msm) {
-    std::vector<int> cw(Ph.n_msm);
-    std::vector<size_t> gbase(Ph.n_msm + 1, 0);
-    for (size_t g = 0; g < Ph.n_msm; g++) {
-      cw[g] = msm_window_bits(Ph.groups[g].len);
-      gbase[g + 1] = gbase[g] + (size_t)(64 / cw[g]) * (size_t)((1u << cw[g]) - 1);
-    }
-    auto bucket = [&](size_t g, int w, uint32_t d) { return gbase[g] + (size_t)w * ((1u << cw[g]) - 1) + d - 1; };
-    std::vector<int32_t> cnt(gbase[Ph.n_msm], 0);
-    for (size_t g = 0; g < Ph.n_msm; g++) {
-      const int c = cw[g], nw = 64 / c;
-      const uint64_t dm = (1ull << c) - 1;
-      for (size_t i = Ph.groups[g].first; i < Ph.groups[g].first + Ph.groups[g].len; i++) {
-        const uint64_t r = s->rnd[i];
-        for (int w = 0; w < nw; w++) {
-          const uint32_t d = (uint32_t)((r >> (c * w)) & dm);
-          if (d) cnt[bucket(g, w, d)]++;
-        }
-      }
-    }
-    std::vector<int32_t> seg_off(cnt.size()), seg_len(cnt);
-    int32_t tot = 0;
-    for (size_t b = 0; b < cnt.size(); b++) {
-      seg_off[b] = tot;
-      tot += cnt[b];
-    }
-    const size_t idx_off = A.size();
-    A.resize(idx_off + (size_t)tot);
-    int32_t* idx = A.data() + idx_off;
-    std::vector<int32_t> fill(seg_off);
-    for (size_t g = 0; g < Ph.n_msm; g++) {
-      const int c = cw[g], nw = 64 / c;
-      const uint64_t dm = (1ull << c) - 1;
-      for (size_t i = Ph.groups[g].first; i < Ph.groups[g].first + Ph.groups[g].len; i++) {
-        const uint64_t r = s->rnd[i];
-        for (int w = 0; w < nw; w++) {
-          const uint32_t d = (uint32_t)((r >> (c * w)) & dm);
-          if (d) idx[fill[bucket(g, w, d)]++] = (int32_t)i;
-        }
-      }
-    }
-    Ph.buckets = plan_seg(A, 1, seg_off, seg_len, true, idx_off, 0);
-    // bit (g, k = c w + j): the buckets (g, w, d) whose digit d has bit j set
-    const size_t bidx = A.size();
-    std::vector<int32_t> boff, blen;
-    for (size_t g = 0; g < Ph.n_msm; g++) {
-      const int c = cw[g], nw = 64 / c;
-      for (int w = 0; w < nw; w++)
-        for (int j = 0; j < c; j++) {
-          boff.push_back((int32_t)(A.size() - bidx));
-          for (uint32_t d = 1; d < (1u << c); d++)
-            if ((d >> j) & 1u) A.push_back((int32_t)bucket(g, w, d));
-          blen.push_back((int32_t)(A.size() - bidx) - boff.back());
-        }
-    }
-    Ph.bits = plan_seg(A, 1, boff, blen, true, bidx, 0);
-  }
-  // scaled groups: S_g = sum of the contiguous scaled points
-  if (Ph.n_msm < ng) {
-    std::vector<int32_t> off, len;
-    for (size_t g = Ph.n_msm; g < ng; g++) {
-      off.push_back((int32_t)Ph.groups[g].first);
-      len.push_back((int32_t)Ph.groups[g].len);
-    }
-    Ph.sums = plan_seg(A, 1, off, len, false, 0, (int32_t)Ph.n_msm);
-  }
-  // Miller items of this phase: <= K consecutive sets, never crossing a group (nor one of its
-  // sub-ranges), unless the groups reuse an earlier phase's items
-  std::vector<std::pair<int32_t, int32_t>> gi;
-  if (Ph.reuse_items) {
-    gi = Ph.given;
-  } else {
-    std::vector<std::pair<size_t, size_t>> ranges;
-    std::vector<size_t> nsub(ng, 1);
-    for (size_t g = 0; g < ng; g++) {
-      if ((int)g == Ph.agg_g) {  // message items instead (below)
-        nsub[g] = 0;
-      } else if (g < Ph.sub.size() && !Ph.sub[g].empty()) {
-        ranges.insert(ranges.end(), Ph.sub[g].begin(), Ph.sub[g].end());
-        nsub[g] = Ph.sub[g].size();
-      } else {
-        ranges.push_back({Ph.groups[g].first, Ph.groups[g].first + Ph.groups[g].len});
-      }
-    }
-    Ph.sub_items.clear();
-    Ph.n_items = plan_items(s, ranges, &Ph.item_off, nullptr, &Ph.sub_items, &Ph.it_first, &Ph.it_cnt);
-    Ph.single_items = true;
-    for (int32_t c : Ph.it_cnt) Ph.single_items = Ph.single_items && c == 1;
-    Ph.n_set_items = Ph.n_items;
-    if (Ph.agg_g >= 0) {  // item n_set_items + j = message j (one pair)
-      Ph.magg_off = A.size();
-      for (size_t j = 0; j < Ph.n_magg; j++) A.push_back((int32_t)j);
-      for (size_t j = 0; j < Ph.n_magg; j++) A.push_back(1);
-      Ph.n_items += Ph.n_magg;
-    }
-    Ph.term_base = Ph.n_items;
-    size_t r = 0;
-    for (size_t g = 0; g < ng; g++) {
-      if ((int)g == Ph.agg_g) {
-        gi.push_back({(int32_t)Ph.n_set_items, (int32_t)Ph.n_items});
-        continue;
-      }
-      gi.push_back({Ph.sub_items[r].first, Ph.sub_items[r + nsub[g] - 1].second});
-      r += nsub[g];
-    }
-  }
-  // F_g = f_g * prod of the group's items; element ids index fall
-  const size_t pidx = A.size();
-  std::vector<int32_t> poff, plen;
-  for (size_t g = 0; g < ng; g++) {
-    poff.push_back((int32_t)(A.size() - pidx));
-    for (int32_t it = gi[g].first; it < gi[g].second; it++) A.push_back(it);
-    A.push_back((int32_t)(Ph.term_base + g));
-    plen.push_back((int32_t)(A.size() - pidx) - poff.back());
-  }
-  Ph.prod = plan_seg(A, 2, poff, plen, true, pidx, 0);
-  return LSG_OK;
-}
 
 // Miller accumulation of planned items (after ev_sig on the main stream)
 int launch_accum(Slot* s, size_t n_items, size_t item_off, uint32_t* fall, bool single = false) {
@@ -1585,10 +1244,10 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
 SegPlan plan_pk_agg(Slot* s) {
   std::vector<int32_t> off(s->n_sets), len(s->n_sets);
   for (size_t i = 0; i < s->n_sets; i++) {
-    off[i] = (int32_t)s->pk_first[i];
-    len[i] = (int32_t)s->pk_cnt[i];
+    off[i] = (int32_t)s->shape.pk_first[i];
+    len[i] = (int32_t)s->shape.pk_cnt[i];
   }
-  return plan_seg(s->plan, 0, off, len, false, 0, 0);
+  return slot_seg(s, 0, off, len, false, 0, 0);
 }
 
 // The batch-affine tree's plan for the slot's sets (keys of set i: pk_first[i] .. + pk_cnt[i]).
@@ -1608,7 +1267,7 @@ AggPlan plan_agg_tree(Slot* s) {
   for (int L = 0; L <= 9; L++) {
     int64_t cost = 0;
     for (size_t i = 0; i < n; i++) {
-      const int64_t len = (int64_t)s->pk_cnt[i];
+      const int64_t len = (int64_t)s->shape.pk_cnt[i];
       cost += L > 0 ? std::min(tree_cost(len, L), len * 11) : len * 11;
     }
     if (best < 0 || cost < best) {
@@ -1621,7 +1280,7 @@ AggPlan plan_agg_tree(Slot* s) {
   std::vector<int32_t> o0(n, 0), src(3 * n);
   int64_t N0 = 0;
   for (size_t i = 0; i < n; i++) {
-    const int64_t len = (int64_t)s->pk_cnt[i];
+    const int64_t len = (int64_t)s->shape.pk_cnt[i];
     if (P.L > 0 && tree_cost(len, P.L) < len * 11) {
       o0[i] = (int32_t)N0;
       src[3 * i] = 0;
@@ -1630,7 +1289,7 @@ AggPlan plan_agg_tree(Slot* s) {
       N0 += (len + A - 1) / A * A;
     } else {
       src[3 * i] = 1;
-      src[3 * i + 1] = (int32_t)s->pk_first[i];
+      src[3 * i + 1] = (int32_t)s->shape.pk_first[i];
       src[3 * i + 2] = (int32_t)len;
     }
   }
@@ -1651,9 +1310,9 @@ AggPlan plan_agg_tree(Slot* s) {
   P.o0_off = s->plan.size();
   s->plan.insert(s->plan.end(), o0.begin(), o0.end());
   P.len_off = s->plan.size();
-  for (size_t i = 0; i < n; i++) s->plan.push_back((int32_t)s->pk_cnt[i]);
+  for (size_t i = 0; i < n; i++) s->plan.push_back((int32_t)s->shape.pk_cnt[i]);
   P.pk0_off = s->plan.size();
-  for (size_t i = 0; i < n; i++) s->plan.push_back((int32_t)s->pk_first[i]);
+  for (size_t i = 0; i < n; i++) s->plan.push_back((int32_t)s->shape.pk_first[i]);
   P.src_off = s->plan.size();
   s->plan.insert(s->plan.end(), src.begin(), src.end());
   return P;
@@ -1719,12 +1378,6 @@ int launch_readback(Slot* s, bool status) {
   return LSG_OK;
 }
 
-struct SetStatus {
-  const int32_t* err;         // per set: BLST code (0 ok)
-  std::vector<uint8_t> pinf;  // per set: aggregated pk is infinity (2: no keys at all)
-  const int32_t* pkerr;       // per pubkey
-};
-
 SetStatus read_status(Slot* s) {
   SetStatus ss;
   const size_t n = s->n_sets;
@@ -1732,26 +1385,8 @@ SetStatus read_status(Slot* s) {
   ss.pkerr = H_<int32_t>(s->h_pkerr);
   ss.pinf.assign(H_<uint8_t>(s->h_pinf), H_<uint8_t>(s->h_pinf) + n);
   for (size_t i = 0; i < n; i++)
-    if (s->pk_cnt[i] == 0) ss.pinf[i] = 2;  // PublicKey.aggregate([]) throws
+    if (s->shape.pk_cnt[i] == 0) ss.pinf[i] = 2;  // PublicKey.aggregate([]) throws
   return ss;
-}
-
-int32_t set_error(const SetStatus& ss, size_t i) {
-  if (ss.err[i]) return ss.err[i];
-  if (ss.pinf[i] == 2) return LSG_ERR_EMPTY_AGGREGATE;
-  return ss.pinf[i] ? LSG_BLST_PK_IS_INFINITY : 0;
-}
-
-// Error a job's maybeBatch call would throw, in the reference's order:
-// Signature.fromBytes over all sets first (maybeBatch.ts:17-26 map), then
-// mul_n_aggregate rejecting an infinite public key (BLST_PK_IS_INFINITY).
-int32_t job_error(const SetStatus& ss, size_t first, size_t count) {
-  if (count == 0) return LSG_ERR_EMPTY_SET;
-  for (size_t k = 0; k < count; k++)
-    if (ss.err[first + k]) return ss.err[first + k];
-  for (size_t k = 0; k < count; k++)
-    if (ss.pinf[first + k]) return set_error(ss, first + k);
-  return 0;
 }
 
 }  // namespace
@@ -1813,211 +1448,67 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   memset(&s->stats, 0, sizeof(s->stats));
   s->stats.start_ns = now_ns();
   const size_t nj = ids.size();
-  s->jobs.assign(nj, JobRec());
-  s->job_ids = ids;
   s->results.assign(nj, lsg_job_result{LSG_INVALID, 0});
-  s->job_group.assign(nj, -1);
-  s->batch_order.clear();
-  s->big_g = -1;
   s->rs2_ready = false;
   s->rs2_scaled.clear();
   s->has_node = n_node > 0;
-  s->lone_unscaled = false;
   s->big_fe_pending = false;
   s->seed = seed;
-  s->nb_g = -1;
-  s->nb_items.clear();
-  std::vector<const lsg_set*> flat;
-  std::vector<size_t> nonb;
-  for (int pass = 0; pass < 2; pass++)
-    for (size_t k = 0; k < nj; k++) {
-      const lsg_job& J = jobs[ids[k]];
-      const bool b = (J.flags & LSG_JOB_BATCHABLE) != 0;
-      if (b != (pass == 0)) continue;
-      s->jobs[k].first = flat.size();
-      s->jobs[k].count = J.n_sets;
-      s->jobs[k].flags = J.flags;
-      for (uint32_t q = 0; q < J.n_sets; q++) flat.push_back(&J.sets[q]);
-      (b ? s->batch_order : nonb).push_back(k);
-    }
-  s->nb_sets = 0;
-  for (size_t k : s->batch_order) s->nb_sets += s->jobs[k].count;
-  // a coalesced launch: sub-package bounds (jobs and batch_order positions), per-sub state
-  s->n_sub = subs ? (int)subs->size() - 1 : 0;
   s->resolved = s->resolving = false;
   s->resolve_rc = LSG_OK;
-  if (subs) {
-    s->sub_first = *subs;
-    s->bpos_first.assign(1, 0);
-    size_t q = 0;
-    for (int k = 0; k < s->n_sub; k++) {
-      while (q < s->batch_order.size() && s->batch_order[q] < (*subs)[k + 1]) q++;
-      s->bpos_first.push_back(q);
-    }
+  std::vector<const lsg_set*> flat(shape_jobs(s->shape, jobs, ids, subs));
+  for (size_t k = 0; k < nj; k++)
+    for (uint32_t q = 0; q < jobs[ids[k]].n_sets; q++) flat[s->shape.jobs[k].first + q] = &jobs[ids[k]].sets[q];
+  if (subs) {  // a coalesced launch: per-sub state
     lsg_stats z;
     memset(&z, 0, sizeof(z));
-    s->sub_stats.assign(s->n_sub, z);
-    s->sub_pkfail.assign(s->n_sub, 0);
-    s->sub_done.assign(s->n_sub, 0);
+    s->sub_stats.assign(s->shape.n_sub, z);
+    s->sub_pkfail.assign(s->shape.n_sub, 0);
+    s->sub_done.assign(s->shape.n_sub, 0);
   }
   s->K = miller_k_for(flat.size());
-  // sets alone in their phase-A group (and so in every later group): no RLC scaling
-  std::vector<uint8_t> noscale(flat.size(), 0);
-  if (!lone_ok) {
-    // (non-batchable jobs below: their groups never enter the package partial)
-  } else if (package_group_mode() && !subs) {
-    if (s->nb_sets == 1) noscale[0] = s->lone_unscaled = true;
-  } else if (package_group_mode() && sub_groups_on()) {  // a coalesced launch: one package group per sub-package
-    for (int k = 0; k < s->n_sub; k++) {
-      size_t len = 0, first = 0;
-      for (size_t q = s->bpos_first[(size_t)k]; q < s->bpos_first[(size_t)k + 1]; q++) {
-        if (!len) first = s->jobs[s->batch_order[q]].first;
-        len += s->jobs[s->batch_order[q]].count;
-      }
-      if (len == 1) noscale[first] = 1;
-    }
-  } else {
-    const auto ch = slot_chunks(s);
-    for (auto& c : ch) {
-      size_t len = 0;
-      for (size_t q = c.first; q < c.second; q++) len += s->jobs[s->batch_order[q]].count;
-      if (len == 1)
-        for (size_t q = c.first; q < c.second; q++)
-          if (s->jobs[s->batch_order[q]].count == 1) noscale[s->jobs[s->batch_order[q]].first] = 1;
-    }
-  }
-  // the merged non-batchable group (nb_merge_on): every one of its sets is randomised, so a
-  // one-set job in it is scaled too (its own check, if the group fails, stays exact: r_i != 0)
-  size_t nb_live = 0;
-  for (size_t k : nonb) nb_live += s->jobs[k].count ? 1 : 0;
-  const bool nb_merge = nb_merge_on() && nb_live >= 2 && !subs && package_group_mode();
-  for (size_t k : nonb)
-    if (s->jobs[k].count == 1 && !nb_merge) noscale[s->jobs[k].first] = 1;
+  // phase-A groups, MSM groups first: the package group (a coalesced launch: one per
+  // sub-package, each with its own verdicts, chunks and fallback), then the non-batchable jobs
+  s->sw = read_switches();
+  s->gp = plan_groups(s->shape, s->sw, lone_ok);
   const uint64_t th0 = trace_host() ? now_ns() : 0;
-  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &noscale, dev_msgs == nullptr));
+  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &s->gp.noscale, dev_msgs == nullptr));
   if (dev_msgs && !flat.empty())  // (placeholders are never merged: message i is set i's)
     LSG_HIP(s, hipMemcpyAsync(s->d_msg.p, dev_msgs, 32 * flat.size(), hipMemcpyDeviceToDevice, s->st[0]));
   // the byte keys of LSG_JOB_VALIDATE_KEYS jobs, compacted (table rows were validated when the
   // node cached them: the flag leaves index keys alone)
   s->n_kv = 0;
-  s->kv_set.clear();
+  s->shape.kv_set.clear();
   bool any_kv = false;
-  for (size_t k = 0; k < nj && !any_kv; k++) any_kv = (s->jobs[k].flags & LSG_JOB_VALIDATE_KEYS) != 0;
+  for (size_t k = 0; k < nj && !any_kv; k++) any_kv = (s->shape.jobs[k].flags & LSG_JOB_VALIDATE_KEYS) != 0;
   if (any_kv) {
-    s->kv_set.assign(flat.size(), 0);
+    s->shape.kv_set.assign(flat.size(), 0);
     for (size_t k = 0; k < nj; k++) {
-      if (!(s->jobs[k].flags & LSG_JOB_VALIDATE_KEYS)) continue;
-      for (size_t i = s->jobs[k].first; i < s->jobs[k].first + s->jobs[k].count; i++)
-        if (flat[i]->pk_len != LSG_PK_INDEX && s->pk_cnt[i]) {
-          s->kv_set[i] = 1;
-          s->n_kv += s->pk_cnt[i];
+      if (!(s->shape.jobs[k].flags & LSG_JOB_VALIDATE_KEYS)) continue;
+      for (size_t i = s->shape.jobs[k].first; i < s->shape.jobs[k].first + s->shape.jobs[k].count; i++)
+        if (flat[i]->pk_len != LSG_PK_INDEX && s->shape.pk_cnt[i]) {
+          s->shape.kv_set[i] = 1;
+          s->n_kv += s->shape.pk_cnt[i];
         }
     }
     s->kv_off = s->plan.size();
     s->plan.resize(s->kv_off + 2 * s->n_kv);
     size_t q = 0;
     for (size_t i = 0; i < flat.size(); i++)  // (staging order: a set's keys are adjacent)
-      for (uint32_t k = 0; s->kv_set[i] && k < s->pk_cnt[i]; k++, q++) {
-        s->plan[s->kv_off + q] = (int32_t)(s->pk_first[i] + k);
+      for (uint32_t k = 0; s->shape.kv_set[i] && k < s->shape.pk_cnt[i]; k++, q++) {
+        s->plan[s->kv_off + q] = (int32_t)(s->shape.pk_first[i] + k);
         s->plan[s->kv_off + s->n_kv + q] = (int32_t)i;
       }
-    if (!s->n_kv) s->kv_set.clear();
+    if (!s->n_kv) s->shape.kv_set.clear();
   }
   const uint64_t th1 = trace_host() ? now_ns() : 0;
-  // phase-A groups, MSM groups first: the package group, then one per non-batchable job
   PhasePlan& A = s->phA;
   A = PhasePlan();
-  std::vector<Grp> gm, gs;
-  std::vector<int> om, os;  // owner: -2 the package group, else the job
-  auto add = [&](size_t first, size_t len, int owner) {
-    Grp g;
-    g.first = first;
-    g.len = len;
-    g.msm = len >= std::max(msm_min_group(), (size_t)2);  // an r_i = 0 set never enters a bucket MSM
-    (g.msm ? gm : gs).push_back(g);
-    (g.msm ? om : os).push_back(owner);
-  };
-  // one RLC group per package; a coalesced launch: one per sub-package (each keeps its own
-  // verdicts, chunks and fallback: pkg_resolve)
-  s->chunk_mode = !package_group_mode() || (subs && !sub_groups_on());
-  s->chunk_group.clear();
-  s->sub_big.assign((size_t)s->n_sub, -1);
-  std::vector<std::pair<size_t, size_t>> chunks;
-  if (s->chunk_mode) {
-    chunks = slot_chunks(s);
-    for (size_t c = 0; c < chunks.size(); c++) {
-      size_t len = 0;
-      for (size_t q = chunks[c].first; q < chunks[c].second; q++) len += s->jobs[s->batch_order[q]].count;
-      if (len) add(s->jobs[s->batch_order[chunks[c].first]].first, len, -3 - (int)c);
-    }
-    s->chunk_group.assign(chunks.size(), -1);
-  } else if (s->n_sub) {
-    for (int k = 0; k < s->n_sub; k++) {
-      size_t len = 0, first = 0;
-      for (size_t q = s->bpos_first[(size_t)k]; q < s->bpos_first[(size_t)k + 1]; q++) {
-        if (!len) first = s->jobs[s->batch_order[q]].first;
-        len += s->jobs[s->batch_order[q]].count;
-      }
-      if (len) add(first, len, -1000 - k);
-    }
-  } else if (s->nb_sets) {
-    add(0, s->nb_sets, -2);
-  }
-  size_t nb_first = 0, nb_len = 0;
-  for (size_t k : nonb) {
-    if (s->jobs[k].count == 0) {
-      s->results[k] = {LSG_ERROR, LSG_ERR_EMPTY_SET};  // maybeBatch.ts:29-31
-    } else if (nb_merge) {  // staged contiguously after the batchable sets, in job order
-      if (!nb_len) nb_first = s->jobs[k].first;
-      nb_len += s->jobs[k].count;
-    } else {
-      add(s->jobs[k].first, s->jobs[k].count, (int)k);
-    }
-  }
-  constexpr int NB_OWNER = INT32_MIN;  // (chunk owners are -3 - c, sub-package owners -1000 - k)
-  if (nb_merge) add(nb_first, nb_len, NB_OWNER);
-  A.groups = gm;
-  A.groups.insert(A.groups.end(), gs.begin(), gs.end());
-  om.insert(om.end(), os.begin(), os.end());
-  // the package group's items never cross a 16-job chunk: if the group fails, each chunk's
-  // check (phase B) reuses them instead of re-running the Miller accumulation
-  std::vector<size_t> chunk_sub;  // chunks with sets, in order
-  if (nb_merge || (!s->chunk_mode && s->nb_sets)) A.sub.assign(om.size(), {});
-  if (nb_merge)  // the merged group's items never cross a job
-    for (size_t g = 0; g < om.size(); g++)
-      if (om[g] == NB_OWNER)
-        for (size_t k : nonb)
-          if (s->jobs[k].count) A.sub[g].push_back({s->jobs[k].first, s->jobs[k].first + s->jobs[k].count});
-  if (!s->chunk_mode && s->nb_sets) {
-    chunks = slot_chunks(s);
-    for (size_t g = 0; g < om.size(); g++) {
-      if ((om[g] != -2 && om[g] > -1000) || om[g] == NB_OWNER) continue;
-      const int sub = om[g] <= -1000 ? -1000 - om[g] : -1;
-      for (size_t c = 0; c < chunks.size(); c++) {
-        if (sub >= 0 && sub_of_pos(s, chunks[c].first) != sub) continue;
-        const size_t first = s->jobs[s->batch_order[chunks[c].first]].first;
-        size_t len = 0;
-        for (size_t q = chunks[c].first; q < chunks[c].second; q++) len += s->jobs[s->batch_order[q]].count;
-        if (len) {
-          A.sub[g].push_back({first, first + len});
-          chunk_sub.push_back(c);
-        }
-      }
-    }
-  }
-  for (size_t g = 0; g < om.size(); g++) {
-    if (om[g] == -2)
-      s->big_g = (int)g;
-    else if (om[g] == NB_OWNER)
-      s->nb_g = (int)g;
-    else if (om[g] <= -3 && s->chunk_mode)  // (chunk mode has no sub-package owners)
-      s->chunk_group[(size_t)(-3 - om[g])] = (int)g;
-    else if (om[g] <= -1000)
-      s->sub_big[(size_t)(-1000 - om[g])] = (int)g;
-    else
-      s->job_group[(size_t)om[g]] = (int)g;
-  }
-  LSG_RC(size_state(s, s->n_sets, s->n_pks, A.groups.size(), gm.size(), 1));
+  A.groups = s->gp.groups;
+  A.sub = s->gp.sub;
+  size_t n_msm = 0;
+  while (n_msm < A.groups.size() && A.groups[n_msm].msm) n_msm++;
+  LSG_RC(size_state(s, s->n_sets, s->n_pks, A.groups.size(), n_msm, 1));
   s->agg = AggPlan();
   if (!s->single_keys) {
     if (s->n_pks >= AGG_TREE_MIN_KEYS && agg_tree_on())
@@ -2029,9 +1520,9 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   // = e(Σ r_i pk_i, H(m)) exactly.  Its per-set items are then never computed, so a failing
   // package group's chunks (phase B) run their own items and phase C goes per job.
   A.agg_g = -1;
-  if (s->msg_dedup && !s->chunk_mode && s->big_g >= 0 && msg_agg_on() && s->n_msgs <= (size_t)8192 &&
-      slp_items_max() > 0) {
-    const Grp& g = A.groups[(size_t)s->big_g];
+  if (s->msg_dedup && !s->gp.chunk_mode && s->gp.big_g >= 0 && s->sw.msg_agg && s->n_msgs <= (size_t)8192 &&
+      s->sw.slp_items > 0) {
+    const Grp& g = A.groups[(size_t)s->gp.big_g];
     std::vector<int32_t> cnt(s->n_msgs, 0), off(s->n_msgs), fill;
     for (size_t i = g.first; i < g.first + g.len; i++) cnt[s->msg_id[i]]++;
     int32_t tot = 0;
@@ -2043,43 +1534,16 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
     const size_t idx_off = s->plan.size();
     s->plan.resize(idx_off + (size_t)tot);
     for (size_t i = g.first; i < g.first + g.len; i++) s->plan[idx_off + (size_t)fill[s->msg_id[i]]++] = (int32_t)i;
-    s->msum = plan_seg(s->plan, 0, off, cnt, true, idx_off, 0);
-    A.agg_g = s->big_g;
+    s->msum = slot_seg(s, 0, off, cnt, true, idx_off, 0);
+    A.agg_g = s->gp.big_g;
     A.n_magg = s->n_msgs;
   }
-  LSG_RC(plan_phase(s, A));
-  if (s->nb_g >= 0) {  // per non-batchable job, its items among the merged group's
-    s->nb_items.assign(nj, {-1, -1});
-    size_t r = 0;
-    for (size_t g = 0; g < om.size(); g++) {
-      if ((int)g == A.agg_g) continue;  // (message items: no sub_items entries)
-      const size_t ns = g < A.sub.size() && !A.sub[g].empty() ? A.sub[g].size() : 1;
-      if ((int)g == s->nb_g) {
-        size_t q = r;
-        for (size_t k : nonb)
-          if (s->jobs[k].count) s->nb_items[k] = A.sub_items[q++];
-      }
-      r += ns;
-    }
-    for (size_t k : nonb)
-      if (s->jobs[k].count) s->job_group[k] = s->nb_g;
-  }
-  s->chunk_items.assign(chunks.size(), {-1, -1});
-  if (!chunk_sub.empty() && A.agg_g < 0) {  // sub_items of the package group, in chunk order
-    size_t r = 0;
-    for (size_t g = 0; g < om.size(); g++) {
-      const size_t ns = g < A.sub.size() && !A.sub[g].empty() ? A.sub[g].size() : 1;
-      const bool pkg = om[g] == -2 || (om[g] <= -1000 && om[g] != NB_OWNER);
-      if (pkg)
-        for (size_t k = 0; k < ns; k++) s->chunk_items[chunk_sub[k]] = A.sub_items[r + k];
-      if (pkg) chunk_sub.erase(chunk_sub.begin(), chunk_sub.begin() + (long)ns);
-      r += ns;
-    }
-  }
+  plan_phase(s->plan, s->rnd, s->K, s->sw, A);
+  group_items(s->gp, s->shape, A);
   SegPlan node;
   if (n_node > 0) {
     std::vector<int32_t> off{0}, len{(int32_t)n_node};
-    node = plan_seg(s->plan, 2, off, len, false, 0, 0);
+    node = slot_seg(s, 2, off, len, false, 0, 0);
   }
   LSG_RC(upload_plan(s));
   const uint64_t th2 = trace_host() ? now_ns() : 0;
@@ -2099,7 +1563,7 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
     LSG_RC(launch_sig_prep(s, any_small, mode.empty() ? nullptr : &mode, P_<uint32_t>(s->d_rs)));
   }
   LSG_RC(launch_phase(s, A, P_<uint32_t>(s->d_rs), P_<uint32_t>(s->d_fall), true));
-  if (A.groups.empty() || s->big_g < 0) {  // no package group: the partial is the identity
+  if (A.groups.empty() || s->gp.big_g < 0) {  // no package group: the partial is the identity
     s->cur = 0;
     LSG_HIP(s, hipMemcpyAsync(P_<uint8_t>(s->d_gath) + 576 * LSG_MAX_DEVICES, fp12_one_blob(), 576,
                               hipMemcpyHostToDevice, s->st[0]));
@@ -2109,7 +1573,7 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   if (trace_host()) {
     const uint64_t th4 = now_ns();
     fprintf(stderr, "lsg host: sets %zu jobs %zu subs %d groups %zu | stage %.3f plan %.3f set-launch %.3f group-launch %.3f ms\n",
-            (size_t)s->n_sets, nj, s->n_sub, A.groups.size(), (th1 - th0) * 1e-6, (th2 - th1) * 1e-6, (th3 - th2) * 1e-6,
+            (size_t)s->n_sets, nj, s->shape.n_sub, A.groups.size(), (th1 - th0) * 1e-6, (th2 - th1) * 1e-6, (th3 - th2) * 1e-6,
             (th4 - th3) * 1e-6);
   }
   return LSG_OK;
@@ -2117,8 +1581,8 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
 
 // device pointer of the package group's canonical partial (576 bytes)
 const uint8_t* pkg_partial_dev(Slot* s) {
-  if (s->phA.groups.empty() || s->big_g < 0) return P_<uint8_t>(s->d_gath) + 576 * LSG_MAX_DEVICES;
-  return P_<uint8_t>(s->d_Fb) + 576 * (size_t)s->big_g;
+  if (s->phA.groups.empty() || s->gp.big_g < 0) return P_<uint8_t>(s->d_gath) + 576 * LSG_MAX_DEVICES;
+  return P_<uint8_t>(s->d_Fb) + 576 * (size_t)s->gp.big_g;
 }
 
 // The package group's partial as it may leave the slot (lsg_jobs_partial*), on the main stream:
@@ -2127,7 +1591,7 @@ const uint8_t* pkg_partial_dev(Slot* s) {
 // xs: launch the power there instead of on the slot's stream (the partial is complete)
 int export_partial_dev(Slot* s, const uint8_t** src, hipStream_t xs = nullptr) {
   *src = pkg_partial_dev(s);
-  if (!s->lone_unscaled) return LSG_OK;
+  if (!s->gp.lone_unscaled) return LSG_OK;
   uint64_t r = 0;
   if (s->seed) {  // tests: reproducible
     uint64_t sd = s->seed ^ 0x5851f42d4c957f2dull;
@@ -2174,10 +1638,10 @@ int pkg_node_check(Slot* s, int n) {
 // exponentiation per node), and it runs only when that check fails (pkg_resolve).
 int pkg_part2(Slot* s, bool skip_big = false) {
   const size_t ng = s->phA.groups.size();
-  s->big_fe_pending = skip_big && !s->chunk_mode && s->big_g >= 0;
+  s->big_fe_pending = skip_big && !s->gp.chunk_mode && s->gp.big_g >= 0;
   if (s->big_fe_pending) {
-    LSG_RC(launch_fe_range(s, 0, (size_t)s->big_g));
-    LSG_RC(launch_fe_range(s, (size_t)s->big_g + 1, ng));
+    LSG_RC(launch_fe_range(s, 0, (size_t)s->gp.big_g));
+    LSG_RC(launch_fe_range(s, (size_t)s->gp.big_g + 1, ng));
   } else {
     LSG_RC(launch_fe(s, ng));
   }
@@ -2206,7 +1670,7 @@ int run_fallback_phase(Slot* s, CtxLock* lk, const std::vector<Grp>& groups,
   std::vector<size_t> order;
   std::vector<uint8_t> gm(groups.size(), 0);
   for (size_t g = 0; g < groups.size(); g++) {
-    bool ok = groups[g].len >= std::max(msm_min_group(), (size_t)2) && s->rs_raw.size() == s->n_sets;
+    bool ok = groups[g].len >= std::max(s->sw.msm_min_group, (size_t)2) && s->rs_raw.size() == s->n_sets;
     for (size_t i = groups[g].first; ok && i < groups[g].first + groups[g].len; i++) ok = s->rs_raw[i] != 0;
     gm[g] = ok;
     if (ok) order.push_back(g);
@@ -2229,17 +1693,14 @@ int run_fallback_phase(Slot* s, CtxLock* lk, const std::vector<Grp>& groups,
   // the list form instead of four-wave fused items holding one pair
   size_t singles = 0;
   for (auto& g : groups) singles += g.len == 1 ? 1 : 0;
-  const int K0 = s->K;
-  if (!given && 2 * singles >= groups.size()) s->K = 1;
+  const int K = !given && 2 * singles >= groups.size() ? 1 : s->K;
   if (given) {
     Ph.reuse_items = true;
     for (size_t k = 0; k < order.size(); k++) Ph.given.push_back((*given)[order[k]]);
     Ph.n_items = s->phA.n_items;
     Ph.term_base = s->phA.n_items + s->phA.groups.size();  // after phase A's own terms
   }
-  const int prc = plan_phase(s, Ph);
-  s->K = K0;
-  LSG_RC(prc);
+  plan_phase(s->plan, s->rnd, K, s->sw, Ph);
   LSG_RC(upload_plan(s));
   // [r_i] sig_i into d_rs2 for the sets no earlier fallback phase of this package scaled
   if (s->rs2_scaled.size() != s->n_sets) s->rs2_scaled.assign(s->n_sets, 0);
@@ -2299,7 +1760,7 @@ int run_fallback_phase(Slot* s, CtxLock* lk, const std::vector<Grp>& groups,
 // the deferred final exponentiation of the package group (pkg_part2 skip_big), synchronous
 int run_big_fe(Slot* s, CtxLock* lk) {
   s->cur = 0;
-  LSG_RC(launch_fe_range(s, (size_t)s->big_g, (size_t)s->big_g + 1));
+  LSG_RC(launch_fe_range(s, (size_t)s->gp.big_g, (size_t)s->gp.big_g + 1));
   LSG_HIP(s, hipEventRecord(s->ev_done, s->st[0]));
   const int dev = s->d->device;
   if (lk) lk->unlock();
@@ -2313,389 +1774,49 @@ int run_big_fe(Slot* s, CtxLock* lk) {
   return LSG_OK;
 }
 
-// The reference's verdict rules for this device's share of the package (worker.ts:30-106),
-// after ev_done.  node_valid: 1 = the node-wide check of all devices' partials passed, 0 = it
-// failed (this device's own package check localises), -1 = no node check (single device).
-// worker.ts:41-43: deserializeSet runs over the package's jobs in caller order before any
-// verification; the first bad pubkey throws out of verifyManySignatureSets.  Returns that
-// key's code for this device's share (0: none) and the caller index of its job.
+// The first bad key of this device's share in caller order (lsgp::first_key_error; 0: none)
+// and the caller index of its job.
 int32_t first_pk_error(Slot* s, size_t* job_id) {
-  const int32_t* pkerr = H_<int32_t>(s->h_pkerr);
-  for (size_t k = 0; k < s->jobs.size(); k++) {  // jobs[k] are in caller order (job_ids ascending)
-    const JobRec& J = s->jobs[k];
-    for (size_t i = J.first; i < J.first + J.count; i++) {
-      if (!s->kv_set.empty() && s->kv_set[i]) continue;  // a validated key fails its set only
-      for (uint32_t q = 0; q < s->pk_cnt[i]; q++)
-        if (const int32_t e = pkerr[s->pk_first[i] + q]) {
-          *job_id = s->job_ids[k];
-          return e;
-        }
-    }
-  }
-  return 0;
+  size_t k = 0;
+  const int32_t e = first_key_error(s->shape, H_<int32_t>(s->h_pkerr), 0, s->shape.jobs.size(), &k);
+  if (e) *job_id = s->shape.job_ids[k];
+  return e;
 }
 
+// The reference's verdict rules for this device's share of the package (worker.ts:30-106),
+// after ev_done: lsgp::resolve_package over the phase-A verdicts, its group checks run here
+// as fallback phases.  node_valid: 1 = the node-wide check of all devices' partials passed,
+// 0 = it failed (this device's own package check localises), -1 = no node check (single
+// device), 2 = this ticket's own node check (lsg_init_devices: the library gathered every
+// device's partial itself) passed, and it decides a package group whose final exponentiation
+// was deferred.  Otherwise the node-wide verdict is advisory (resolve_package).
 // pkfail: the package-wide deserializeSet failure (first_pk_error over every device of the
 // ticket, in caller order) -- a bad key on any device rejects every job of the package
-// node_valid 2: this ticket's own node check (lsg_init_devices: the library gathered every
-// device's partial itself) passed, and it decides the package group.
 int pkg_resolve(Slot* s, CtxLock* lk, int node_valid, int32_t pkfail) {
   const SetStatus ss = read_status(s);
   const PhasePlan& A = s->phA;
   std::vector<int32_t> vA(H_<int32_t>(s->h_verdict), H_<int32_t>(s->h_verdict) + A.groups.size());
   s->stats.n_final_exps += (uint32_t)(A.groups.size() - (s->big_fe_pending ? 1 : 0));
-  const size_t nj = s->jobs.size();
-  if (pkfail) {
-    for (size_t j = 0; j < nj; j++) s->results[j] = {LSG_ERROR, pkfail};
-    return LSG_OK;
-  }
-  if (s->big_fe_pending) {
+  if (s->big_fe_pending && !pkfail) {
     if (node_valid == 2) {
-      vA[(size_t)s->big_g] = 1;
+      vA[(size_t)s->gp.big_g] = 1;
     } else {  // the node check failed: this device's own check localises
       LSG_RC(run_big_fe(s, lk));
-      vA[(size_t)s->big_g] = H_<int32_t>(s->h_verdict)[s->big_g];
+      vA[(size_t)s->gp.big_g] = H_<int32_t>(s->h_verdict)[s->gp.big_g];
       s->stats.n_final_exps++;
     }
   }
-  // counters of the chunk at batch_order position q: the slot's, and its sub-package's
-  auto retry_inc = [&](size_t q) {
-    s->stats.batch_retries++;
-    if (s->n_sub) s->sub_stats[(size_t)sub_of_pos(s, q)].batch_retries++;
+  const CheckFn check = [&](const std::vector<Grp>& groups, const std::vector<ItemRange>* given, std::vector<int32_t>& v) {
+    return run_fallback_phase(s, lk, groups, given, v);
   };
-  auto succ_add = [&](size_t q, size_t len) {
-    s->stats.batch_sigs_success += (uint32_t)len;
-    if (s->n_sub) s->sub_stats[(size_t)sub_of_pos(s, q)].batch_sigs_success += (uint32_t)len;
-  };
-  // a coalesced launch: the deserializeSet rule per sub-package (worker.ts:41-43)
-  std::vector<uint8_t> job_dead(nj, 0);
-  for (int k = 0; k < s->n_sub; k++) {
-    const int32_t* pkerr = H_<int32_t>(s->h_pkerr);
-    int32_t e = 0;
-    size_t ej = 0;
-    for (size_t j = s->sub_first[k]; j < s->sub_first[k + 1] && !e; j++)
-      for (size_t i = s->jobs[j].first; i < s->jobs[j].first + s->jobs[j].count && !e; i++)
-        for (uint32_t q = 0; q < s->pk_cnt[i] && !e && !(!s->kv_set.empty() && s->kv_set[i]); q++)
-          if (pkerr[s->pk_first[i] + q]) {
-            e = pkerr[s->pk_first[i] + q];
-            ej = j - s->sub_first[k];
-          }
-    s->sub_pkfail[k] = e;
-    s->sub_stats[k].key_error = e;
-    s->sub_stats[k].key_error_job = e ? (uint32_t)ej : 0;
-    if (e)
-      for (size_t j = s->sub_first[k]; j < s->sub_first[k + 1]; j++) {
-        s->results[j] = {LSG_ERROR, e};
-        job_dead[j] = 1;
-      }
-  }
-  // non-batchable jobs: their own group (worker.ts:88-96), or the merged group (nb_g): a
-  // passing one answers every such job; a failing one is localised job by job over the jobs'
-  // resident phase-A items (a fallback phase), so each verdict is still the job's own
-  std::vector<Grp> nbg;
-  std::vector<size_t> nbj;
-  std::vector<std::pair<int32_t, int32_t>> nbi;
-  for (size_t j = 0; j < nj; j++) {
-    const int g = s->job_group[j];
-    if (g < 0 || job_dead[j]) continue;
-    const int32_t e = job_error(ss, s->jobs[j].first, s->jobs[j].count);
-    if (!e && g == s->nb_g && !vA[(size_t)g]) {
-      Grp q;
-      q.first = s->jobs[j].first;
-      q.len = s->jobs[j].count;
-      nbg.push_back(q);
-      nbj.push_back(j);
-      nbi.push_back(s->nb_items[j]);
-      continue;
-    }
-    s->results[j] = e ? lsg_job_result{LSG_ERROR, e} : lsg_job_result{vA[(size_t)g] ? LSG_VALID : LSG_INVALID, 0};
-  }
-  if (!nbg.empty()) {
-    std::vector<int32_t> vn;
-    LSG_RC(run_fallback_phase(s, lk, nbg, &nbi, vn));
-    for (size_t k = 0; k < nbj.size(); k++) s->results[nbj[k]] = {vn[k] ? LSG_VALID : LSG_INVALID, 0};
-  }
-  if (s->batch_order.empty()) return LSG_OK;
-  // batchable jobs: chunks of >= 16 jobs (worker.ts:51-86)
-  // The device's own check of its share (computed in phase A in any case) decides.  The
-  // node-wide verdict is advisory: a passing node check with a failing own check (a caller
-  // whose all-gather missed a rank) localises like a failing one instead of
-  // accepting the package.
-  (void)node_valid;
-  auto chunks = slot_chunks(s);
-  // the package group covering chunk c passed (a coalesced launch: its sub-package's group)
-  auto pkg_ok = [&](size_t c) {
-    const int g = s->n_sub ? s->sub_big[(size_t)sub_of_pos(s, chunks[c].first)] : s->big_g;
-    return g < 0 || vA[(size_t)g] != 0;
-  };
-  std::vector<size_t> retry;  // jobs verified individually (phase C)
-  std::vector<Grp> chk;       // chunks checked on their own (phase B)
-  std::vector<std::pair<size_t, size_t>> chk_jobs;
-  std::vector<std::pair<int32_t, int32_t>> chk_items;  // their resident phase-A items
-  std::vector<uint8_t> chk_threw;                      // the chunk threw (its retry is counted)
-  std::vector<uint8_t> job_err(nj, 0);                 // the job's result is its decode error
-  bool any_err_chunk = false;
-  std::vector<uint8_t> chunk_err(chunks.size(), 0);
-  for (size_t c = 0; c < chunks.size(); c++) {
-    for (size_t q = chunks[c].first; q < chunks[c].second && !chunk_err[c]; q++) {
-      const JobRec& J = s->jobs[s->batch_order[q]];
-      for (size_t i = J.first; i < J.first + J.count; i++)
-        if (set_error(ss, i)) {
-          chunk_err[c] = 1;
-          break;
-        }
-    }
-    any_err_chunk = any_err_chunk || chunk_err[c];
-  }
-  // a coalesced sub-package of exactly one chunk: its group has the chunk's sets and r_i
-  std::vector<int> sub_nchunks((size_t)s->n_sub, 0);
-  for (size_t c = 0; c < chunks.size() && s->n_sub; c++) sub_nchunks[(size_t)sub_of_pos(s, chunks[c].first)]++;
-  auto group_is_chunk = [&](size_t c) {
-    if (!s->n_sub) return chunks.size() == 1 && !any_err_chunk;
-    return sub_nchunks[(size_t)sub_of_pos(s, chunks[c].first)] == 1;  // (chunk c has no decode error)
-  };
-  for (size_t c = 0; c < chunks.size(); c++) {
-    if (job_dead[s->batch_order[chunks[c].first]]) continue;  // its sub-package has a bad key
-    const size_t first = s->jobs[s->batch_order[chunks[c].first]].first;
-    size_t len = 0;
-    for (size_t q = chunks[c].first; q < chunks[c].second; q++) len += s->jobs[s->batch_order[q]].count;
-    if (len == 0) {  // maybeBatch([]) throws: retried, and every job throws again
-      retry_inc(chunks[c].first);
-      for (size_t q = chunks[c].first; q < chunks[c].second; q++)
-        s->results[s->batch_order[q]] = {LSG_ERROR, LSG_ERR_EMPTY_SET};
-      continue;
-    }
-    if (!chunk_err[c] && s->chunk_mode) {  // the chunk's own phase-A group decides
-      if (vA[(size_t)s->chunk_group[c]]) {
-        for (size_t q = chunks[c].first; q < chunks[c].second; q++) s->results[s->batch_order[q]] = {LSG_VALID, 0};
-        succ_add(chunks[c].first, len);
-      } else {
-        retry_inc(chunks[c].first);
-        for (size_t q = chunks[c].first; q < chunks[c].second; q++) retry.push_back(s->batch_order[q]);
-      }
-    } else if (!chunk_err[c]) {
-      if (pkg_ok(c)) {
-        for (size_t q = chunks[c].first; q < chunks[c].second; q++) s->results[s->batch_order[q]] = {LSG_VALID, 0};
-        succ_add(chunks[c].first, len);
-      } else if (group_is_chunk(c)) {
-        // the package (or sub-package) group is exactly this chunk: its verdict is the chunk's
-        retry_inc(chunks[c].first);
-        for (size_t q = chunks[c].first; q < chunks[c].second; q++) retry.push_back(s->batch_order[q]);
-      } else {
-        Grp g;
-        g.first = first;
-        g.len = len;
-        chk.push_back(g);
-        chk_jobs.push_back(chunks[c]);
-        chk_items.push_back(c < s->chunk_items.size() ? s->chunk_items[c] : std::make_pair(-1, -1));
-        chk_threw.push_back(0);
-      }
-    } else {  // the chunk throws (worker.ts:79-85): every job is verified on its own
-      retry_inc(chunks[c].first);
-      // A job's own verdict is its validity alone, so the chunk's jobs that do not throw are
-      // checked as ONE group first -- the throwing sets are the identity in the chunk's items
-      // and signature sums (the kernels' err rule) -- and localised only if it fails: a chunk
-      // with one undecodable signature costs one group check instead of 16 per-job checks.
-      // Verdicts and the batch counters are the reference's (the retry counted above, no
-      // batch success for a chunk that threw).
-      bool live = false;
-      for (size_t q = chunks[c].first; q < chunks[c].second; q++) {
-        const size_t j = s->batch_order[q];
-        const int32_t e = job_error(ss, s->jobs[j].first, s->jobs[j].count);
-        if (e) {
-          s->results[j] = {LSG_ERROR, e};
-          job_err[j] = 1;
-        } else {
-          live = true;
-        }
-      }
-      if (!live) continue;
-      if (!s->chunk_mode && pkg_ok(c)) {  // its sets are in the passing package group
-        for (size_t q = chunks[c].first; q < chunks[c].second; q++)
-          if (!job_err[s->batch_order[q]]) s->results[s->batch_order[q]] = {LSG_VALID, 0};
-      } else if (s->chunk_mode) {  // the chunk's own phase-A group (throwing sets as identity)
-        const bool ok = vA[(size_t)s->chunk_group[c]] != 0;
-        for (size_t q = chunks[c].first; q < chunks[c].second; q++) {
-          const size_t j = s->batch_order[q];
-          if (job_err[j]) continue;
-          if (ok)
-            s->results[j] = {LSG_VALID, 0};
-          else
-            retry.push_back(j);
-        }
-      } else {
-        Grp g;
-        g.first = first;
-        g.len = len;
-        chk.push_back(g);
-        chk_jobs.push_back(chunks[c]);
-        chk_items.push_back(c < s->chunk_items.size() ? s->chunk_items[c] : std::make_pair(-1, -1));
-        chk_threw.push_back(1);
-      }
-    }
-  }
-  std::vector<int32_t> v;
-  std::vector<size_t> fail_chunks;  // phase-B chunks that failed, whose phase-A items phase C1 reuses
-  bool reuse = true;
-  if (!chk.empty()) {  // phase B
-    for (auto& r : chk_items) reuse = reuse && r.first >= 0;
-    // Phase B0: runs of consecutive chunks (adjacent sets and resident items) as one group
-    // each, so that only the chunks of a failing run are checked on their own.  A run passes
-    // only if every chunk in it would (the RLC check of its sets, the throwing sets the
-    // identity as in the chunks' own groups), so each chunk's verdict -- and with it the batch
-    // counters below -- is what its own check gives.  At 1 % corrupted sets about a fifth of
-    // the runs of four fail: 2048 chunk checks of a 32k package become ~512 + ~460.
-    std::vector<uint8_t> passed(chk.size(), 0);
-    if (reuse && b0_min_chunks() > 0 && chk.size() >= b0_min_chunks()) {
-      std::vector<Grp> rg;
-      std::vector<std::pair<int32_t, int32_t>> ri;
-      std::vector<std::pair<size_t, size_t>> rc;  // chk index range [a, b) of each run
-      for (size_t c = 0; c < chk.size();) {
-        size_t e = c + 1;
-        while (e < chk.size() && e - c < b0_run() && chk[e].first == chk[e - 1].first + chk[e - 1].len &&
-               chk_items[e].first == chk_items[e - 1].second)
-          e++;
-        if (e - c >= 2) {
-          Grp g;
-          g.first = chk[c].first;
-          g.len = chk[e - 1].first + chk[e - 1].len - chk[c].first;
-          rg.push_back(g);
-          ri.push_back({chk_items[c].first, chk_items[e - 1].second});
-          rc.push_back({c, e});
-        }
-        c = e;
-      }
-      if (!rg.empty()) {
-        std::vector<int32_t> vr;
-        LSG_RC(run_fallback_phase(s, lk, rg, &ri, vr));
-        for (size_t k = 0; k < rg.size(); k++)
-          if (vr[k])
-            for (size_t c = rc[k].first; c < rc[k].second; c++) passed[c] = 1;
-      }
-    }
-    std::vector<Grp> rest;
-    std::vector<std::pair<int32_t, int32_t>> rest_items;
-    std::vector<size_t> rest_of;
-    for (size_t c = 0; c < chk.size(); c++)
-      if (!passed[c]) {
-        rest.push_back(chk[c]);
-        rest_items.push_back(chk_items[c]);
-        rest_of.push_back(c);
-      }
-    std::vector<int32_t> vb;
-    LSG_RC(run_fallback_phase(s, lk, rest, reuse ? &rest_items : nullptr, vb));
-    v.assign(chk.size(), 1);
-    for (size_t k = 0; k < rest.size(); k++) v[rest_of[k]] = vb[k];
-    for (size_t c = 0; c < chk.size(); c++) {
-      if (v[c]) {
-        for (size_t q = chk_jobs[c].first; q < chk_jobs[c].second; q++)
-          if (!job_err[s->batch_order[q]]) s->results[s->batch_order[q]] = {LSG_VALID, 0};
-        if (!chk_threw[c]) succ_add(chk_jobs[c].first, chk[c].len);
-      } else {
-        if (!chk_threw[c]) retry_inc(chk_jobs[c].first);
-        if (reuse) {
-          fail_chunks.push_back(c);
-        } else {
-          for (size_t q = chk_jobs[c].first; q < chk_jobs[c].second; q++)
-            if (!job_err[s->batch_order[q]]) retry.push_back(s->batch_order[q]);
-        }
-      }
-    }
-  }
-  // Phase C1: the jobs of a failing chunk, localised over its phase-A items.  A group is a
-  // run of whole items ending on a job boundary (for single-set jobs: one item = four jobs),
-  // checked with its resident items -- no new Miller work.  A passing group answers its jobs
-  // (valid); a one-job group's verdict is that job's maybeBatch verdict (the same RLC check,
-  // worker.ts:88-96); the jobs of a failing multi-job group are checked one by one (C2).
-  // Per-job verdicts and the batch counters are unchanged: only the work is (a chunk with one
-  // bad set costs 4 group checks + 4 one-set checks instead of 16 one-set checks).
-  if (!fail_chunks.empty()) {
-    const PhasePlan& A0 = s->phA;
-    std::vector<Grp> g1;
-    std::vector<std::pair<int32_t, int32_t>> g1_items;
-    std::vector<std::pair<size_t, size_t>> g1_jobs;  // batch_order positions [a, b)
-    for (size_t c : fail_chunks) {
-      size_t q = chk_jobs[c].first;
-      const size_t qe = chk_jobs[c].second;
-      int32_t ia = chk_items[c].first;
-      for (int32_t it = chk_items[c].first; it < chk_items[c].second; it++) {
-        const size_t end = (size_t)A0.it_first[(size_t)it] + (size_t)A0.it_cnt[(size_t)it];
-        // jobs of this group: those ending at or before `end`; close the group on a boundary
-        size_t qb = q;
-        while (qb < qe && s->jobs[s->batch_order[qb]].first + s->jobs[s->batch_order[qb]].count <= end) qb++;
-        const bool boundary = qb > q && s->jobs[s->batch_order[qb - 1]].first + s->jobs[s->batch_order[qb - 1]].count == end;
-        if (!boundary && it + 1 < chk_items[c].second) continue;
-        Grp g;
-        g.first = (size_t)A0.it_first[(size_t)ia];
-        g.len = end - g.first;
-        g1.push_back(g);
-        g1_items.push_back({ia, it + 1});
-        g1_jobs.push_back({q, qb});
-        q = qb;
-        ia = it + 1;
-      }
-      for (; q < qe; q++) retry.push_back(s->batch_order[q]);  // (not reached: items cover the chunk)
-    }
-    LSG_RC(run_fallback_phase(s, lk, g1, &g1_items, v));
-    for (size_t g = 0; g < g1.size(); g++) {
-      // A thrown job keeps its error.  Only its throwing sets are the identity in the group:
-      // its other sets take part, so a failing group with one live job localises that job on
-      // its own (C2) unless every other job of the group is live too.
-      size_t nlive = 0;
-      bool thrown = false;
-      for (size_t q = g1_jobs[g].first; q < g1_jobs[g].second; q++) {
-        nlive += job_err[s->batch_order[q]] ? 0 : 1;
-        thrown = thrown || job_err[s->batch_order[q]];
-      }
-      for (size_t q = g1_jobs[g].first; q < g1_jobs[g].second; q++) {
-        const size_t j = s->batch_order[q];
-        if (job_err[j]) continue;
-        if (v[g])
-          s->results[j] = {LSG_VALID, 0};
-        else if (nlive == 1 && !thrown)
-          s->results[j] = {LSG_INVALID, 0};
-        else
-          retry.push_back(j);
-      }
-    }
-  }
-  if (!retry.empty()) {  // phase C2: one group per job
-    std::vector<Grp> g3;
-    std::vector<size_t> g3job;
-    for (size_t j : retry) {
-      const int32_t e = job_error(ss, s->jobs[j].first, s->jobs[j].count);
-      if (e) {
-        s->results[j] = {LSG_ERROR, e};
-        continue;
-      }
-      Grp g;
-      g.first = s->jobs[j].first;
-      g.len = s->jobs[j].count;
-      g3.push_back(g);
-      g3job.push_back(j);
-    }
-    LSG_RC(run_fallback_phase(s, lk, g3, nullptr, v));
-    for (size_t g = 0; g < g3.size(); g++) s->results[g3job[g]] = {v[g] ? LSG_VALID : LSG_INVALID, 0};
-  }
-  return LSG_OK;
+  return resolve_package(s->shape, s->gp, ss, vA, pkfail, A, s->sw, check,
+                         PkgVerdicts{s->results, s->stats, s->sub_stats, s->sub_pkfail});
 }
 
 }  // namespace
 
 // ---------------------------------------------------------------------------- tickets
 namespace {
-
-// Whole jobs per device by cumulative set count (never splits a job): job j goes
-// to floor(sets_before_j * n_dev / total).
-void assign_jobs(const uint32_t* sizes, size_t n_jobs, int n_dev, int32_t* owner) {
-  uint64_t total = 0;
-  for (size_t j = 0; j < n_jobs; j++) total += sizes[j];
-  uint64_t before = 0;
-  for (size_t j = 0; j < n_jobs; j++) {
-    owner[j] = (total == 0 || n_dev <= 1) ? 0 : (int32_t)std::min<uint64_t>((uint64_t)n_dev - 1, before * (uint64_t)n_dev / total);
-    before += sizes[j];
-  }
-}
 
 uint64_t make_ticket(lsg_ctx* c, int kind, int index, uint64_t* serial) {
   *serial = c->next_serial++;
@@ -2950,7 +2071,7 @@ int wait_pkg(lsg_ctx* c, CtxLock* lk, int p, int node_valid, lsg_job_result* res
     (void)hipSetDevice(c->dev[d]->device);
     rc = pkg_resolve(s, lk, node_valid, pkfail);
     if (rc) break;
-    for (size_t k = 0; k < s->jobs.size(); k++) results[s->job_ids[k]] = s->results[k];
+    for (size_t k = 0; k < s->shape.jobs.size(); k++) results[s->shape.job_ids[k]] = s->results[k];
     total.batch_retries += s->stats.batch_retries;
     total.batch_sigs_success += s->stats.batch_sigs_success;
     total.n_final_exps += s->stats.n_final_exps;
@@ -3154,7 +2275,7 @@ int wait_merged(lsg_ctx* c, lsg_ticket t, lsg_job_result* results, lsg_stats* st
     c->cv.notify_all();
   }
   const int rc = s->resolve_rc;
-  for (size_t j = s->sub_first[k]; j < s->sub_first[k + 1]; j++) results[j - s->sub_first[k]] = s->results[j];
+  for (size_t j = s->shape.sub_first[k]; j < s->shape.sub_first[k + 1]; j++) results[j - s->shape.sub_first[k]] = s->results[j];
   if (stats) {
     *stats = s->sub_stats[k];
     stats->start_ns = s->stats.start_ns;
@@ -3169,7 +2290,7 @@ int wait_merged(lsg_ctx* c, lsg_ticket t, lsg_job_result* results, lsg_stats* st
   if (all) {
     if (rc) sync_slot(s);
     s->kind = SLOT_FREE;
-    s->n_sub = 0;
+    s->shape.n_sub = 0;
     keep_times(s);
     maybe_flush(c);
   }
@@ -3223,7 +2344,7 @@ int submit_final(Slot* s, const uint8_t* partials576, size_t ng, size_t pg, bool
       off.push_back((int32_t)(g * pg));
       len.push_back((int32_t)pg);
     }
-    SegPlan P = plan_seg(s->plan, 2, off, len, false, 0, 0);
+    SegPlan P = slot_seg(s, 2, off, len, false, 0, 0);
     LSG_RC(upload_plan(s));
     hipStream_t S = s->st[0];
     if (on_device) {  // the caller's device buffer (e.g. a collective's output): no host copy
@@ -3590,8 +2711,8 @@ int lsg_jobs_partial(lsg_ctx* c, lsg_ticket ticket, uint8_t* out576, int32_t* ha
   const int p = ticket_pkg(c, ticket);
   if (p < 0) return LSG_ERR_INVALID_ARG;
   Slot* s = &c->dev[0]->slots[p];
-  const bool has = !s->phA.groups.empty() && s->big_g >= 0;
-  if (has && s->lone_unscaled) {
+  const bool has = !s->phA.groups.empty() && s->gp.big_g >= 0;
+  if (has && s->gp.lone_unscaled) {
     const uint8_t* src;
     LSG_RC(export_partial_dev(s, &src));
     LSG_RC(ensure_host(s, s->h_xport, 576));
@@ -3599,7 +2720,7 @@ int lsg_jobs_partial(lsg_ctx* c, lsg_ticket ticket, uint8_t* out576, int32_t* ha
     LSG_HIP(s, hipStreamSynchronize(s->st[0]));
     memcpy(out576, s->h_xport.p, 576);
   } else if (has) {
-    memcpy(out576, H_<uint8_t>(s->h_blob) + 576 * (size_t)s->big_g, 576);
+    memcpy(out576, H_<uint8_t>(s->h_blob) + 576 * (size_t)s->gp.big_g, 576);
   } else {
     memcpy(out576, fp12_one_blob(), 576);
   }
@@ -3621,7 +2742,7 @@ int lsg_jobs_partial_device(lsg_ctx* c, lsg_ticket ticket, void* dev_out576, int
     const int p = ticket_pkg(c, ticket);
     if (p < 0) return LSG_ERR_INVALID_ARG;
     Slot* s = &c->dev[0]->slots[p];
-    has = !s->phA.groups.empty() && s->big_g >= 0;
+    has = !s->phA.groups.empty() && s->gp.big_g >= 0;
     // the copy goes out on a high-priority stream (the node final exponentiations'): on the
     // package's own stream it would queue behind other packages' kernels sharing its hardware
     // queue, and the node's next verdicts wait on it (ev_part is complete: presync_pkg)
@@ -3750,8 +2871,8 @@ int lsg_batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_t s
   }
   for (size_t k = 0; k < s->n_pks; k++)
     if (ss.pkerr[k]) *any_error = 1;
-  if (s->big_g >= 0)
-    memcpy(out576, H_<uint8_t>(s->h_blob) + 576 * (size_t)s->big_g, 576);
+  if (s->gp.big_g >= 0)
+    memcpy(out576, H_<uint8_t>(s->h_blob) + 576 * (size_t)s->gp.big_g, 576);
   else
     memcpy(out576, fp12_one_blob(), 576);
   s->kind = SLOT_FREE;
@@ -3866,7 +2987,7 @@ int lsg_aggregate_pubkeys(lsg_ctx* c, const uint8_t* pks, uint32_t pk_len, size_
   s->plan.clear();
   LSG_RC(util_stage_keys(s, pks, pk_len, n));
   std::vector<int32_t> off{0}, len{(int32_t)n};
-  SegPlan P = plan_seg(s->plan, 0, off, len, false, 0, 0);
+  SegPlan P = slot_seg(s, 0, off, len, false, 0, 0);
   LSG_RC(upload_plan(s));
   const int np = (int)n;
   KL(s, "k_pk_decode", lsgk::pk_decode(S_(s), np, P_<uint8_t>(s->d_pk), s->pk_stride, P_<uint32_t>(s->d_pklen),
@@ -3930,8 +3051,8 @@ int lsg_aggregate_pubkeys_multi(lsg_ctx* c, const lsg_set* sets, size_t n_sets, 
   LSG_HIP(s, hipStreamSynchronize(s->st[0]));
   keep_times(s);
   for (size_t i = 0; i < n_sets; i++) {
-    err[i] = s->pk_cnt[i] == 0 ? LSG_ERR_EMPTY_AGGREGATE : 0;
-    for (uint32_t q = 0; q < s->pk_cnt[i] && !err[i]; q++) err[i] = pkerr[s->pk_first[i] + q];
+    err[i] = s->shape.pk_cnt[i] == 0 ? LSG_ERR_EMPTY_AGGREGATE : 0;
+    for (uint32_t q = 0; q < s->shape.pk_cnt[i] && !err[i]; q++) err[i] = pkerr[s->shape.pk_first[i] + q];
   }
   return LSG_OK;
 }
@@ -4064,7 +3185,7 @@ int lsg_aggregate_signatures(lsg_ctx* c, const uint8_t* sigs, uint32_t sig_len, 
     off[g] = (int32_t)offsets[g];
     len[g] = (int32_t)(offsets[g + 1] - offsets[g]);
   }
-  SegPlan P = plan_seg(s->plan, 1, off, len, false, 0, 0);
+  SegPlan P = slot_seg(s, 1, off, len, false, 0, 0);
   LSG_RC(upload_plan(s));
   LSG_RC(ensure(s, s->d_aux, 96 * n_groups));
   const int nn = (int)n;

@@ -10,7 +10,7 @@
 // pair j folds elements j, j + ips, j + 2 ips, ... serially (every fold is a full-width
 // SIMD operation), then the ips partial values are combined by a butterfly over lanes
 // (shuffles, no LDS round trip).  Segments longer than one chunk get a second pass over the
-// chunk results (lsg_host.hip plan_seg), so a reduction is one or two launches instead of
+// chunk results (lsg_plan.hpp plan_seg), so a reduction is one or two launches instead of
 // one launch per tree level.
 #include "lsg_kcommon.hpp"
 namespace {

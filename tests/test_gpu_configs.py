@@ -207,7 +207,7 @@ def test_thrown_chunk_localises_its_live_jobs(ctx, keys):
     """A chunk whose batch throws (an undecodable signature) is checked as one group of its
     other jobs; a thrown job's remaining sets still take part, so a failing Miller-item group
     whose only live job shares it with a thrown job must not convict that job (found by the
-    10^7 soak, pkg_resolve phase C1).  The package has more than 8192 distinct messages (so its
+    10^7 soak, phase C1: lsg_plan.hpp localise_items).  The package has more than 8192 distinct messages (so its
     group keeps per-set Miller items) and more than 2048 sets (four-set items, k_miller_fused):
     sets 0-3 = job [truncated, wrong message, valid] + job [valid] form one item.  Verdicts and
     batch counters against the oracle's worker.ts rules (multithread/worker.ts:51-96); the
@@ -235,7 +235,7 @@ def test_thrown_chunk_localises_its_live_jobs(ctx, keys):
 
 
 def test_phase_b0_runs_localise_like_chunks(ctx, keys):
-    """Phase B0 (lsg_host.hip pkg_resolve): a failing package of 2048 single-set jobs (128
+    """Phase B0 (lsg_plan.hpp Resolver::check_chunks): a failing package of 2048 single-set jobs (128
     chunks of 16) is first checked as 32 runs of four chunks; only the chunks of a failing run
     are checked on their own.  An invalid set in chunk 5, an undecodable one in chunk 9 (its run
     passes: the thrown set is the identity, as in the chunk's own group) and an invalid set at

@@ -19,7 +19,7 @@ from tests import blsdata as bd
 class OracleBackend:
     """ShardedVerifier backend computed by the oracle (test infrastructure only): the same
     submit / partial / final_verify / resolve protocol as GpuBackend, and ``resolve`` follows
-    the device's package rules (lsg_host.hip pkg_resolve): the rank's own package-group check
+    the device's package rules (lsg_plan.hpp resolve_package): the rank's own package-group check
     (every batchable set that decodes, one RLC batch) decides -- the node verdict is advisory;
     a passing group answers every batchable job, a failing one is localised by the 16-job
     chunks (phase B) and then per job (phase C); a bad key rejects every job."""

@@ -47,7 +47,7 @@ def main():
     msm_per_set = 8 * c["g2_add"]
     msm_per_group = (64 * 127 + 126) * c["g2_add"]
     per_set_msm = per_set - c["sig_scale"] - c["g2_add"] + msm_per_set
-    # groups of 32..255 sets: 4-bit windows (lsg_host.hip plan_phase): 16 digits per set, the
+    # groups of 32..255 sets: 4-bit windows (lsg_plan.hpp plan_phase): 16 digits per set, the
     # 64 bit sums over 8 buckets each (64 * 7 additions), the same Horner pass
     msm4_per_set = 16 * c["g2_add"]
     msm4_per_group = (64 * 7 + 126) * c["g2_add"]
