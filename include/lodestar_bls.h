@@ -65,10 +65,26 @@ extern "C" {
 #define LSG_ERR_EMPTY_SET 100        /* maybeBatch.ts:29-31 "Empty signature set" */
 #define LSG_ERR_EMPTY_AGGREGATE 101  /* PublicKey.aggregate([]) "EMPTY_AGGREGATE_ARRAY" */
 #define LSG_ERR_BAD_INDEX 102        /* a pubkey index outside the loaded table (index2pubkey[i] undefined) */
+#define LSG_ERR_BAD_COMMITTEE 103    /* unknown / unset committee id, or n_pks != its length */
 
 /* lsg_set.pk_len value for keys given by validator index into the context's pubkey table
  * (lsg_pubkey_table_set): pks then points at n_pks uint32 indices (host byte order). */
 #define LSG_PK_INDEX 4u
+/* lsg_set.pk_len value for keys named by committee id + participation bits (lsg_committees_set):
+ * n_pks is the bit count and must equal the committee's length; pks points at
+ * 4 + ceil(n_pks / 8) bytes: the uint32 committee id (host byte order), then the bitfield in SSZ
+ * order without a delimiter bit -- member k is bit k & 7 of byte k >> 3; bits at positions
+ * >= n_pks are ignored.  The set behaves exactly as the same set with LSG_PK_INDEX and the
+ * participating members' table indices in committee order: no bit set is
+ * LSG_ERR_EMPTY_AGGREGATE as n_pks == 0 is; an unknown id, an unset committee or a length
+ * mismatch is LSG_ERR_BAD_COMMITTEE, routed exactly like LSG_ERR_BAD_INDEX (a deserializeSet
+ * failure: the package is rejected, lsg_stats.key_error / key_error_job say where).  Honoured
+ * wherever sets are staged -- lsg_submit_jobs / lsg_wait_jobs / lsg_verify_jobs,
+ * lsg_verify_sets, lsg_aggregate_pubkeys_multi, lsg_batch_partial, coalesced packages, every
+ * device of a multi-device context, the node protocol -- and a package may mix byte, index and
+ * bits sets.  lsg_aggregate_pubkeys (one key list) does not take it: 8 stays an unknown key
+ * length there.  LSG_JOB_VALIDATE_KEYS leaves such sets alone, as it leaves index sets alone. */
+#define LSG_PK_BITS 8u
 
 /* ---- job verdicts (WorkResult<boolean>, multithread/types.ts:21-24) */
 #define LSG_INVALID 0 /* {code: success, result: false} */
@@ -164,7 +180,10 @@ int lsg_device_name(lsg_ctx* ctx, char* buf, size_t len);
  * bytes, so that submissions within those bounds allocate nothing.  A context over n devices
  * reserves each device for its share: 1/n of each bound plus one 4,096-set job's worth.
  * lsg_submit_jobs stages a package with the context lock released (several host threads may
- * stage packages at once; the devices of a multi-device context are staged in parallel). */
+ * stage packages at once; the devices of a multi-device context are staged in parallel).
+ * A committee + bits set (LSG_PK_BITS) of n bits counts 16 + ceil(n / 32) toward max_pks; its
+ * bit arena is reserved once the context has a committee registered (call lsg_reserve after
+ * lsg_committees_set, or again). */
 int lsg_reserve(lsg_ctx* ctx, size_t max_sets, size_t max_pks, size_t max_msg_bytes, int32_t n_slots);
 /* Device + pinned allocations made by this process so far (steady-state checks). */
 int lsg_allocation_count(lsg_ctx* ctx, uint64_t* n);
@@ -237,10 +256,11 @@ int lsg_aggregate_pubkeys(lsg_ctx* ctx, const uint8_t* pks, uint32_t pk_len, siz
                           int32_t* err_code);
 /* PublicKey.aggregate for n_sets sets in one device pass (utils.ts:11 getAggregatedPubkey over
  * a block's aggregate sets, indexedAttestation.ts:21-47): set i's keys are sets[i].pks /
- * pk_len / n_pks (bytes or table indices; msg and sig are ignored).  out96[96 i..] = set i's
+ * pk_len / n_pks (bytes, table indices, or a committee id + bits; msg and sig are ignored).  out96[96 i..] = set i's
  * uncompressed sum; err[i] = its first bad key's BLST_* / LSG_ERR_BAD_INDEX, or
- * LSG_ERR_EMPTY_AGGREGATE for no keys.  Every input size runs the jobs path's fused gather +
- * mixed-addition fold (k_pk_agg_seg); the batch-affine aggregation tree exists only in the
+ * LSG_ERR_EMPTY_AGGREGATE for no keys, LSG_ERR_BAD_COMMITTEE for a LSG_PK_BITS set naming no
+ * registered committee of its length.  Every input size runs the jobs path's fused gather +
+ * mixed-addition fold (k_pk_agg_seg; LSG_PK_BITS sets: k_pk_agg_bits); the batch-affine aggregation tree exists only in the
  * A/B build (liblodestar_bls_ab.so, LSG_AGG_TREE=1), where it was measured slower. */
 int lsg_aggregate_pubkeys_multi(lsg_ctx* ctx, const lsg_set* sets, size_t n_sets, uint8_t* out96, int32_t* err);
 
@@ -289,6 +309,36 @@ int lsg_final_wait_groups(lsg_ctx* ctx, lsg_ticket ticket, int32_t* valid /* [n_
 int lsg_pubkey_table_set(lsg_ctx* ctx, size_t first_index, const uint8_t* pks, uint32_t pk_len, size_t n,
                          int32_t* err);
 int lsg_pubkey_table_size(lsg_ctx* ctx, size_t* n);
+
+/* ---- Committees resident on the GPU.  An attestation or a sync aggregate
+ * reaches the node as a committee plus a bitfield (aggregationBits.intersectValues(committee),
+ * state-transition/src/cache/epochContext.ts:620-623; syncCommitteeBits.intersectValues,
+ * block/processSyncCommittee.ts:87-90), and committees are fixed for an epoch.  With the
+ * committees held beside the pubkey table a set names its keys as committee id + bits
+ * (lsg_set.pk_len = LSG_PK_BITS, ~60 bytes instead of ~1.8 KB of indices), and its aggregate
+ * is the cheaper of  sum of the participants  and  committee sum - sum of the absentees  --
+ * the same point, so verdicts and serialised aggregates are those of the index form.
+ *   lsg_committees_set    committee first_id + c <- members indices[offsets[c] .. offsets[c+1])
+ *                         (rows of the pubkey table; duplicates allowed, as a sync committee has
+ *                         them; offsets has n_committees + 1 entries, offsets[0] = 0).  One
+ *                         device pass over all of them stores the index rows and each full sum
+ *                         (projective; a row holding the infinity key adds nothing) on every
+ *                         device.  err[c] (may be NULL) = LSG_ERR_BAD_INDEX when a member names
+ *                         an unset row, LSG_ERR_EMPTY_AGGREGATE for an empty committee; such a
+ *                         committee stays unset.  ids are below 2^20 and a committee has at most
+ *                         131,072 members (else LSG_ERR_INVALID_ARG).  Registering an id again
+ *                         replaces it.  Waits for in-flight work, as a table rewrite does.
+ *                         A lsg_pubkey_table_set call that writes a row below the current table
+ *                         size (a rewrite, not an append) unsets EVERY committee -- a stored
+ *                         sum may be stale -- and they are registered again.
+ *   lsg_committees_clear  unsets ids first_id .. first_id + n - 1.
+ *   lsg_committee_count   highest set id + 1.
+ * A context that never registers a committee behaves, allocates and launches as before. */
+int lsg_committees_set(lsg_ctx* ctx, uint32_t first_id, const uint32_t* indices,
+                       const uint32_t* offsets /* n_committees + 1, offsets[0] = 0 */, size_t n_committees,
+                       int32_t* err /* may be NULL */);
+int lsg_committees_clear(lsg_ctx* ctx, uint32_t first_id, size_t n);
+int lsg_committee_count(lsg_ctx* ctx, size_t* n);
 
 /* Batched KeyValidate: PublicKey.fromBytes(pk, affine, validate=true) of
  * processDeposit.ts:57-65 for n keys of pk_len (48/96) bytes -- decode, not the point at

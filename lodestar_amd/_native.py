@@ -36,7 +36,9 @@ BLST_NAMES = {
 LSG_ERR_EMPTY_SET = 100
 LSG_ERR_EMPTY_AGGREGATE = 101
 LSG_ERR_BAD_INDEX = 102
+LSG_ERR_BAD_COMMITTEE = 103
 LSG_PK_INDEX = 4  # lsg_set.pk_len for keys named by pubkey-table index
+LSG_PK_BITS = 8  # lsg_set.pk_len for keys named by committee id + participation bits
 
 
 def error_message(code):
@@ -48,6 +50,8 @@ def error_message(code):
         return "EMPTY_AGGREGATE_ARRAY"
     if code == LSG_ERR_BAD_INDEX:
         return "Unknown pubkey index"
+    if code == LSG_ERR_BAD_COMMITTEE:
+        return "Unknown committee or bit length mismatch"
     return "BLST_ERROR: " + BLST_NAMES.get(code, f"BLST_UNKNOWN_{code}")
 
 
@@ -64,6 +68,39 @@ class PkIndices(list):
         a = array.array("I", self)
         assert a.itemsize == 4
         return a.tobytes()
+
+
+class PkBits:
+    """A set's pubkeys given as a committee registered with Context.committees_set plus the
+    participation bits (lsg_set.pk_len = LSG_PK_BITS): `bits` is the SSZ bitvector's bytes
+    (member k = bit k & 7 of byte k >> 3, no delimiter bit), `n_bits` the bit count, which must
+    equal the committee's length.  Accepted wherever a key list is."""
+
+    def __init__(self, committee, bits, n_bits):
+        self.committee = int(committee)
+        self.n_bits = int(n_bits)
+        nb = (self.n_bits + 7) // 8
+        self.bits = bytes(bits)[:nb].ljust(nb, b"\0")
+
+    def __len__(self):
+        return self.n_bits
+
+    def tobytes(self):
+        return struct.pack("=I", self.committee) + self.bits
+
+
+def _key_form(pks):
+    """(pk_len, n_pks, bytes) of a set's keys: encoded keys, PkIndices or PkBits"""
+    if isinstance(pks, PkBits):
+        return LSG_PK_BITS, pks.n_bits, pks.tobytes()
+    if isinstance(pks, PkIndices):
+        return LSG_PK_INDEX, len(pks), pks.tobytes()
+    pk_len = len(pks[0]) if pks else 96
+    if any(len(p) != pk_len for p in pks):
+        raise ValueError("all pubkeys of one set must share one encoding length")
+    if pk_len == LSG_PK_BITS:  # 8-byte "keys" are an unknown key length, never committee + bits
+        pk_len = 0
+    return pk_len, len(pks), b"".join(pks)
 
 
 class LsgSet(ctypes.Structure):
@@ -106,6 +143,7 @@ EXPORTS = [
     "lsg_signing_roots", "lsg_attestation_signing_roots", "lsg_jobs_partial_device", "lsg_final_submit_device",
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
+    "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
 ]
 
 
@@ -154,6 +192,9 @@ def load_library(path=LIB_PATH):
         lib.lsg_poll.argtypes = [vp, u64, pi32]
         lib.lsg_pubkey_table_set.argtypes = [vp, sz, ctypes.c_char_p, u32, sz, pi32]
         lib.lsg_pubkey_table_size.argtypes = [vp, ctypes.POINTER(sz)]
+        lib.lsg_committees_set.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), sz, pi32]
+        lib.lsg_committees_clear.argtypes = [vp, u32, sz]
+        lib.lsg_committee_count.argtypes = [vp, ctypes.POINTER(sz)]
         lib.lsg_final_submit_groups.argtypes = [vp, ctypes.c_char_p, sz, sz, pu64]
         lib.lsg_final_wait_groups.argtypes = [vp, u64, pi32]
         lib.lsg_pubkey_validate.argtypes = [vp, ctypes.c_char_p, u32, sz, ctypes.c_char_p, pi32]
@@ -186,19 +227,13 @@ class SetBuffer:
         sets = list(sets)
         self.arr = (LsgSet * max(len(sets), 1))()
         for i, (pks, msg, sig) in enumerate(sets):
-            if isinstance(pks, PkIndices):
-                pk_len, pkb = LSG_PK_INDEX, pks.tobytes()
-            else:
-                pk_len = len(pks[0]) if pks else 96
-                if any(len(p) != pk_len for p in pks):
-                    raise ValueError("all pubkeys of one set must share one encoding length")
-                pkb = b"".join(pks)
+            pk_len, n_pks, pkb = _key_form(pks)
             for b in (pkb, msg, sig):
                 self._keep.append(b)
             s = self.arr[i]
             s.pks = ctypes.cast(ctypes.c_char_p(pkb), ctypes.c_void_p) if pkb else None
             s.pk_len = pk_len
-            s.n_pks = len(pks)
+            s.n_pks = n_pks
             s.msg = ctypes.cast(ctypes.c_char_p(msg), ctypes.c_void_p) if msg else None
             s.msg_len = len(msg)
             s.sig = ctypes.cast(ctypes.c_char_p(sig), ctypes.c_void_p) if sig else None
@@ -230,14 +265,7 @@ class PreparedJobs:
         n = len(flat)
         pk_parts, pk_len, n_pks = [], np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
         for i, (pks, _m, _s) in enumerate(flat):
-            if isinstance(pks, PkIndices):
-                pk_len[i], b = LSG_PK_INDEX, pks.tobytes()
-            else:
-                pk_len[i] = len(pks[0]) if pks else 96
-                if any(len(p) != pk_len[i] for p in pks):
-                    raise ValueError("all pubkeys of one set must share one encoding length")
-                b = b"".join(pks)
-            n_pks[i] = len(pks)
+            pk_len[i], n_pks[i], b = _key_form(pks)
             pk_parts.append(b)
 
         def pack(parts):
@@ -468,6 +496,27 @@ class Context:
     def pubkey_table_size(self):
         n = ctypes.c_size_t()
         self._check(self.lib.lsg_pubkey_table_size(self.h, ctypes.byref(n)), "lsg_pubkey_table_size")
+        return n.value
+
+    def committees_set(self, first_id, lists):
+        """lsg_committees_set: committee first_id + c <- lists[c] (pubkey-table indices, in
+        committee order); returns the per-committee codes (0: registered)."""
+        n = len(lists)
+        flat = [int(i) for lst in lists for i in lst]
+        idx = (ctypes.c_uint32 * max(len(flat), 1))(*flat)
+        offs = (ctypes.c_uint32 * (n + 1))()
+        for k in range(n):
+            offs[k + 1] = offs[k] + len(lists[k])
+        err = (ctypes.c_int32 * max(n, 1))()
+        self._check(self.lib.lsg_committees_set(self.h, int(first_id), idx, offs, n, err), "lsg_committees_set")
+        return list(err[:n])
+
+    def committees_clear(self, first_id, n):
+        self._check(self.lib.lsg_committees_clear(self.h, int(first_id), int(n)), "lsg_committees_clear")
+
+    def committee_count(self):
+        n = ctypes.c_size_t()
+        self._check(self.lib.lsg_committee_count(self.h, ctypes.byref(n)), "lsg_committee_count")
         return n.value
 
     def pubkey_validate(self, pks):

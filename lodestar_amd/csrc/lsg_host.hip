@@ -205,6 +205,14 @@ struct Slot {
   SegPlan msum;                  // msg_agg: per message, the masked scaled keys of the package group
   DevBuf d_mmask, d_PmP, d_Pm, d_pinfm, d_errm;
   bool single_keys = false;  // every set has exactly one key (key i is set i's)
+  // sets given as committee id + participation bits (LSG_PK_BITS): their
+  // fields staged into the bit arena (h_cbits -> d_cbits, allocated by the first such package),
+  // aggregated by k_pk_agg_bits (bplan) instead of run_pk_seg; pk_all_bits: no other kind of set
+  std::vector<BitsSet> bits_sets;
+  BitsPlan bplan;
+  HostBuf h_cbits;
+  DevBuf d_cbits;
+  bool pk_all_bits = false;
   // KeyValidate of the byte keys of LSG_JOB_VALIDATE_KEYS jobs: n_kv list items (staged key,
   // its set) in the plan arena at kv_off, kv_off + n_kv; shape.kv_set[i] != 0: set i's keys are
   // on the list (empty when the package has no such job: nothing staged, nothing launched)
@@ -284,6 +292,10 @@ struct Dev {
   // validator pubkey table (lsg_pubkey_table_set): projective lane-form keys + validity bytes
   DevBuf d_pktab, d_pktab_ok;
   size_t pktab_n = 0, pktab_cap = 0;
+  // committees (lsg_committees_set): the index rows of every registered committee back to back
+  // (cm_idx), per id its first row word (cm_off) and its projective sum (cm_sum, lane form);
+  // lengths and the set flags are the context's (cm_len, cm_ok: the same on every device)
+  DevBuf d_cm_idx, d_cm_off, d_cm_sum;
   // lsg_verify_deposits: the call's DepositData and their signing roots (the packages' messages)
   DevBuf d_dep_in, d_dep_roots;
   // kernel times of the last package / call completed on this device (lsg_last_kernel_times),
@@ -302,6 +314,13 @@ struct lsg_ctx {
   // lsg_pubkey_table_set, always taken before `mu`), `xmu` orders the RCCL exchanges of
   // packages staged at the same time, `staging` counts the submissions in flight.
   std::shared_mutex tab_mu;
+  // committees (lsg_committees_set; read while staging under tab_mu shared, written under it
+  // exclusively): per id its length, set flag and first word in cm_rows, the host copy of the
+  // devices' index rows (replaced and cleared committees leave dead words behind: cm_dead;
+  // compacted when they outweigh the live ones)
+  std::vector<uint32_t> cm_len, cm_off, cm_rows;
+  std::vector<uint8_t> cm_ok;
+  size_t cm_dead = 0;
   std::mutex xmu;
   std::mutex dep_mu;  // one lsg_verify_deposits at a time (they share d_dep_*), taken before `mu`
   int staging = 0;
@@ -517,12 +536,12 @@ void slot_destroy(Slot* s) {
                     &s->d_Sb,   &s->d_fgb,    &s->d_Fb,   &s->d_bkt,    &s->d_bits,   &s->d_aux,   &s->d_gath,
                     &s->d_nodeF, &s->d_nodeV, &s->d_plan, &s->d_mid, &s->d_Hm, &s->d_hinfm,
                     &s->d_mmask, &s->d_PmP, &s->d_Pm, &s->d_pinfm, &s->d_errm, &s->d_xport,
-                    &s->d_agga, &s->d_aggi, &s->d_aggpre, &s->d_aggtot, &s->d_aggflag};
+                    &s->d_agga, &s->d_aggi, &s->d_aggpre, &s->d_aggtot, &s->d_aggflag, &s->d_cbits};
   for (DevBuf* b : bufs) free_dev(*b);
   for (auto& u : s->seg_tmp)
     for (DevBuf& b : u) free_dev(b);
   HostBuf* hb[] = {&s->h_arena, &s->h_err, &s->h_pinf, &s->h_pkerr, &s->h_verdict, &s->h_blob, &s->h_plan, &s->h_nodeV,
-                   &s->h_xport};
+                   &s->h_xport, &s->h_cbits};
   for (HostBuf* b : hb) free_host(*b);
   for (Timer& t : s->timers) {
     (void)hipEventDestroy(t.a);
@@ -893,16 +912,42 @@ static uint64_t msg_key(const uint8_t* m, uint32_t len) {
   return h ^ (h >> 29);
 }
 
+// bits_ok: a set with pk_len == LSG_PK_BITS names its keys by committee id + participation bits
+// (the entry points that take sets); false where the caller passes one key list of one length
+// (lsg_aggregate_pubkeys, the table and KeyValidate calls), which keeps treating 8 as an
+// unknown key length.  Such a set stages its id and bits only -- no key slots, no per-key
+// error entries -- and its set-level errors are resolved here: an unknown or unset committee
+// or a length mismatch (LSG_ERR_BAD_COMMITTEE, shape.bits_kerr), no participant (shape.bits_p 0).
 int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, bool scale,
-               const std::vector<uint8_t>* noscale = nullptr, bool dedup = false) {
-  size_t npk = 0, msg_total = 0;
+               const std::vector<uint8_t>* noscale = nullptr, bool dedup = false, bool bits_ok = false) {
+  size_t npk = 0, msg_total = 0, n_bits_sets = 0, bit_words = 0;
   bool all_index = true;  // every key names a table row: 4-byte key slots (a block body's
                           // ~3.7M signers cross PCIe as 15 MB instead of 355 MB)
+  auto is_bits = [&](const lsg_set* q) { return bits_ok && q->pk_len == LSG_PK_BITS; };
   for (size_t i = 0; i < n; i++) {
-    npk += sets[i]->n_pks;
     msg_total += sets[i]->msg_len;
+    if (is_bits(sets[i])) {
+      n_bits_sets++;
+      bit_words += bits_words(sets[i]->n_pks);
+      continue;
+    }
+    npk += sets[i]->n_pks;
     if (sets[i]->n_pks && sets[i]->pk_len != LSG_PK_INDEX) all_index = false;
   }
+  s->bits_sets.clear();
+  s->shape.bits_p.clear();
+  s->shape.bits_kerr.clear();
+  s->pk_all_bits = n > 0 && n_bits_sets == n;
+  uint32_t* cbits = nullptr;
+  if (n_bits_sets) {
+    s->shape.bits_p.assign(n, -1);
+    s->shape.bits_kerr.assign(n, 0);
+    s->bits_sets.reserve(n_bits_sets);
+    LSG_RC(ensure_host(s, s->h_cbits, 4 * bit_words));
+    LSG_RC(ensure(s, s->d_cbits, 4 * bit_words));
+    cbits = H_<uint32_t>(s->h_cbits);
+  }
+  size_t bw = 0;  // words of the bit arena in use
   const size_t ks = all_index ? 4 : 96;
   s->pk_stride = (uint32_t)ks;
   s->n_sets = n;
@@ -926,7 +971,7 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   s->shape.pk_first.resize(n);
   s->rnd.resize(n);
   size_t mo = 0, po = 0, nm = 0;
-  bool single = npk == n;
+  bool single = npk == n && n_bits_sets == 0;
   // open-addressing table over the messages: slot -> distinct message id (mfirst: its set),
   // with the message's 64-bit key beside it so that a probe compares bytes only on a key match
   size_t cap = 0;
@@ -994,6 +1039,22 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
       mo += q->msg_len;
       nm++;
     }
+    if (is_bits(q)) {
+      const lsg_ctx* c = s->d->c;
+      s->shape.pk_cnt[i] = 0;
+      s->shape.pk_first[i] = (uint32_t)po;
+      BitsSet b;
+      b.out = (int32_t)i;
+      uint32_t id = 0;
+      if (q->pks) memcpy(&id, q->pks, 4);
+      if (!q->pks || id >= c->cm_ok.size() || !c->cm_ok[id] || c->cm_len[id] != q->n_pks)
+        s->shape.bits_kerr[i] = LSG_ERR_BAD_COMMITTEE;
+      else
+        b = bits_stage_set(id, q->pks + 4, q->n_pks, (int32_t)i, cbits, &bw);
+      s->shape.bits_p[i] = (int32_t)b.p;
+      s->bits_sets.push_back(b);
+      continue;
+    }
     s->shape.pk_cnt[i] = q->n_pks;
     s->shape.pk_first[i] = (uint32_t)po;
     if (q->n_pks != 1) single = false;
@@ -1059,6 +1120,19 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
             {&s->d_pklen, o_pklen, 4 * np},   {&s->d_rnd, o_rnd, 8 * nn}};
   for (auto& x : cp) LSG_HIP(s, hipMemcpyAsync(x.d->p, A + x.off, x.len, hipMemcpyHostToDevice, S));
   if (s->msg_dedup) LSG_HIP(s, hipMemcpyAsync(s->d_mid.p, A + o_mid, 4 * n, hipMemcpyHostToDevice, S));
+  if (bw) LSG_HIP(s, hipMemcpyAsync(s->d_cbits.p, cbits, 4 * bw, hipMemcpyHostToDevice, S));
+  return LSG_OK;
+}
+
+// PublicKey.aggregate of the slot's LSG_PK_BITS sets on the current stream (k_pk_agg_bits; the
+// plan s->bplan is in the uploaded arena)
+int run_pk_bits(Slot* s, uint32_t* dst) {
+  if (s->bits_sets.empty()) return LSG_OK;
+  Dev* d = s->d;
+  KL(s, "k_pk_agg_bits", lsgk::pk_agg_bits(S_(s), (int)s->bplan.n_pairs, PL(s, s->bplan.pair_off), PL(s, s->bplan.plan_off),
+                                           P_<uint32_t>(s->d_cbits), P_<uint32_t>(d->d_cm_idx), P_<uint32_t>(d->d_cm_off),
+                                           P_<uint32_t>(d->d_cm_sum), P_<uint32_t>(d->d_pktab), P_<uint8_t>(d->d_pktab_ok),
+                                           (uint32_t)d->pktab_n, dst));
   return LSG_OK;
 }
 
@@ -1174,9 +1248,12 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
       KL(s, "k_pk_decode", lsgk::pk_decode(S_(s), np, P_<uint8_t>(s->d_pk), s->pk_stride, P_<uint32_t>(s->d_pklen),
                                            P_<uint32_t>(s->d_agg), P_<int32_t>(s->d_pkerr), P_<uint32_t>(d->d_pktab),
                                            P_<uint8_t>(d->d_pktab_ok), (uint32_t)d->pktab_n));
-  } else {
+  } else if (!s->pk_all_bits) {
     LSG_RC(run_pk_seg(s, *pkagg, P_<uint32_t>(s->d_agg)));  // (every staged key is in one set)
   }
+  // committee + bits sets: their aggregates over whatever run_pk_seg left in their slots (the
+  // identity of a set without staged keys)
+  LSG_RC(run_pk_bits(s, P_<uint32_t>(s->d_agg)));
   // flagged jobs' byte keys: KeyValidate codes per list item (d_pkp is free in a package: the
   // keys decode straight into their aggregates); applied to the sets after the signature stages
   if (s->n_kv)
@@ -1385,7 +1462,8 @@ SetStatus read_status(Slot* s) {
   ss.pkerr = H_<int32_t>(s->h_pkerr);
   ss.pinf.assign(H_<uint8_t>(s->h_pinf), H_<uint8_t>(s->h_pinf) + n);
   for (size_t i = 0; i < n; i++)
-    if (s->shape.pk_cnt[i] == 0) ss.pinf[i] = 2;  // PublicKey.aggregate([]) throws
+    if (s->shape.pk_cnt[i] == 0 && !(i < s->shape.bits_p.size() && s->shape.bits_p[i] > 0))
+      ss.pinf[i] = 2;  // PublicKey.aggregate([]) throws (a bits set: no participant)
   return ss;
 }
 
@@ -1472,7 +1550,7 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   s->sw = read_switches();
   s->gp = plan_groups(s->shape, s->sw, lone_ok);
   const uint64_t th0 = trace_host() ? now_ns() : 0;
-  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &s->gp.noscale, dev_msgs == nullptr));
+  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &s->gp.noscale, dev_msgs == nullptr, true));
   if (dev_msgs && !flat.empty())  // (placeholders are never merged: message i is set i's)
     LSG_HIP(s, hipMemcpyAsync(s->d_msg.p, dev_msgs, 32 * flat.size(), hipMemcpyDeviceToDevice, s->st[0]));
   // the byte keys of LSG_JOB_VALIDATE_KEYS jobs, compacted (table rows were validated when the
@@ -1486,7 +1564,7 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
     for (size_t k = 0; k < nj; k++) {
       if (!(s->shape.jobs[k].flags & LSG_JOB_VALIDATE_KEYS)) continue;
       for (size_t i = s->shape.jobs[k].first; i < s->shape.jobs[k].first + s->shape.jobs[k].count; i++)
-        if (flat[i]->pk_len != LSG_PK_INDEX && s->shape.pk_cnt[i]) {
+        if (flat[i]->pk_len != LSG_PK_INDEX && flat[i]->pk_len != LSG_PK_BITS && s->shape.pk_cnt[i]) {
           s->shape.kv_set[i] = 1;
           s->n_kv += s->shape.pk_cnt[i];
         }
@@ -1510,12 +1588,13 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   while (n_msm < A.groups.size() && A.groups[n_msm].msm) n_msm++;
   LSG_RC(size_state(s, s->n_sets, s->n_pks, A.groups.size(), n_msm, 1));
   s->agg = AggPlan();
-  if (!s->single_keys) {
-    if (s->n_pks >= AGG_TREE_MIN_KEYS && agg_tree_on())
+  if (!s->single_keys && !s->pk_all_bits) {
+    if (s->n_pks >= AGG_TREE_MIN_KEYS && agg_tree_on() && s->bits_sets.empty())
       s->agg = plan_agg_tree(s);
     else
       s->pkagg = plan_pk_agg(s);
   }
+  s->bplan = plan_bits(s->plan, s->bits_sets);
   // sets of the package group that share a message share one Miller pair: Π e(r_i pk_i, H(m))
   // = e(Σ r_i pk_i, H(m)) exactly.  Its per-set items are then never computed, so a failing
   // package group's chunks (phase B) run their own items and phase C goes per job.
@@ -2092,6 +2171,12 @@ int wait_pkg(lsg_ctx* c, CtxLock* lk, int p, int node_valid, lsg_job_result* res
 }
 
 // ---- coalesced launches (lsg_set_coalesce)
+// bytes behind a set's pks: key slots, table indices, or a committee id + its bitfield
+size_t set_key_bytes(const lsg_set& t) {
+  if (!t.pks) return 0;
+  if (t.pk_len == LSG_PK_BITS) return 4 + (((size_t)t.n_pks + 7) >> 3);
+  return (size_t)t.n_pks * (t.pk_len == LSG_PK_INDEX ? 4 : t.pk_len);
+}
 PendingPkg copy_pkg(const lsg_job* jobs, size_t n_jobs, uint64_t seed) {
   PendingPkg pk;
   pk.seed = seed;
@@ -2100,7 +2185,7 @@ PendingPkg copy_pkg(const lsg_job* jobs, size_t n_jobs, uint64_t seed) {
     for (uint32_t q = 0; q < jobs[j].n_sets; q++) {
       const lsg_set& t = jobs[j].sets[q];
       ns++;
-      nb += (t.pks ? (size_t)t.n_pks * (t.pk_len == LSG_PK_INDEX ? 4 : t.pk_len) : 0) + (t.msg ? t.msg_len : 0) +
+      nb += set_key_bytes(t) + (t.msg ? t.msg_len : 0) +
             (t.sig ? t.sig_len : 0);
     }
   pk.n_sets = ns;
@@ -2119,7 +2204,7 @@ PendingPkg copy_pkg(const lsg_job* jobs, size_t n_jobs, uint64_t seed) {
     pk.jobs[j].sets = pk.sets.data() + si;
     for (uint32_t q = 0; q < jobs[j].n_sets; q++, si++) {
       lsg_set t = jobs[j].sets[q];
-      t.pks = put(t.pks, t.pks ? (size_t)t.n_pks * (t.pk_len == LSG_PK_INDEX ? 4 : t.pk_len) : 0);
+      t.pks = put(t.pks, set_key_bytes(t));
       t.msg = put(t.msg, t.msg ? t.msg_len : 0);
       t.sig = put(t.sig, t.sig ? t.sig_len : 0);
       pk.sets[si] = t;
@@ -2424,6 +2509,9 @@ void dev_destroy(Dev* d) {
   slot_destroy(&d->util);
   free_dev(d->d_pktab);
   free_dev(d->d_pktab_ok);
+  free_dev(d->d_cm_idx);
+  free_dev(d->d_cm_off);
+  free_dev(d->d_cm_sum);
   free_dev(d->d_dep_in);
   free_dev(d->d_dep_roots);
   if (d->s_util) (void)hipStreamDestroy(d->s_util);
@@ -2616,6 +2704,14 @@ int lsg_reserve(lsg_ctx* c, size_t max_sets, size_t max_pks, size_t max_msg_byte
       LSG_RC(size_inputs(s, max_sets, max_pks, max_msg_bytes));
       // groups: as many as sets (the per-job phase of a failing package of single-set jobs)
       LSG_RC(size_state(s, max_sets, max_pks, max_sets, max_sets / 256 + 1, 1));
+      // the bit arena of committee + bits sets, once the context has committees (a context that
+      // never registers one reserves what it did before): a bits set of n bits counts
+      // 16 + ceil(n / 32) toward max_pks, which covers its 4 ceil(n / 32) arena bytes here and
+      // its plan words (6 + up to 32 lane pairs) below
+      if (!c->cm_ok.empty()) {
+        LSG_RC(ensure_host(s, s->h_cbits, 4 * max_pks));
+        LSG_RC(ensure(s, s->d_cbits, 4 * max_pks));
+      }
       LSG_RC(ensure_host(s, s->h_mode, std::max(max_sets, (size_t)1)));
       const size_t plan_words = 16 * max_sets + 4 * max_pks + 64 * 1024;
       LSG_RC(ensure_host(s, s->h_plan, 4 * plan_words));
@@ -2865,7 +2961,8 @@ int lsg_batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_t s
   const SetStatus ss = read_status(s);
   *any_error = 0;
   for (size_t i = 0; i < n_sets; i++) {
-    const int32_t e = set_error(ss, i);
+    int32_t e = set_error(ss, i);
+    if (!s->shape.bits_kerr.empty() && s->shape.bits_kerr[i]) e = s->shape.bits_kerr[i];
     if (set_err) set_err[i] = e;
     if (e) *any_error = 1;
   }
@@ -3011,7 +3108,8 @@ int lsg_aggregate_pubkeys(lsg_ctx* c, const uint8_t* pks, uint32_t pk_len, size_
 int lsg_aggregate_pubkeys_multi(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint8_t* out96, int32_t* err) {
   if (!c || (n_sets && (!sets || !out96 || !err)) || n_sets > 0x7fffffffull) return LSG_ERR_INVALID_ARG;
   for (size_t i = 0; i < n_sets; i++)
-    if (sets[i].n_pks && (!sets[i].pks || (sets[i].pk_len != 48 && sets[i].pk_len != 96 && sets[i].pk_len != LSG_PK_INDEX)))
+    if (sets[i].n_pks && (!sets[i].pks || (sets[i].pk_len != 48 && sets[i].pk_len != 96 && sets[i].pk_len != LSG_PK_INDEX &&
+                                            sets[i].pk_len != LSG_PK_BITS)))
       return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);
   Dev* d = c->dev[0];
@@ -3027,22 +3125,24 @@ int lsg_aggregate_pubkeys_multi(lsg_ctx* c, const lsg_set* sets, size_t n_sets, 
     ks[i].n_pks = sets[i].n_pks;
     sp[i] = &ks[i];
   }
-  LSG_RC(stage_sets(s, sp.data(), n_sets, 0, false));
+  LSG_RC(stage_sets(s, sp.data(), n_sets, 0, false, nullptr, false, true));
   const size_t np = s->n_pks;
   LSG_RC(size_state(s, n_sets, np, 1, 0));
   s->plan.clear();
-  const bool tree = np >= AGG_TREE_MIN_KEYS && agg_tree_on();
+  const bool tree = np >= AGG_TREE_MIN_KEYS && agg_tree_on() && s->bits_sets.empty();
   s->single_keys = false;
   if (tree)
     s->agg = plan_agg_tree(s);
-  else
+  else if (!s->pk_all_bits)
     s->pkagg = plan_pk_agg(s);
+  s->bplan = plan_bits(s->plan, s->bits_sets);
   LSG_RC(upload_plan(s));
   if (tree) {
     LSG_RC(launch_agg_tree(s, s->agg, P_<uint32_t>(s->d_agg)));
   } else if (np) {
     LSG_RC(run_pk_seg(s, s->pkagg, P_<uint32_t>(s->d_agg)));
   }
+  LSG_RC(run_pk_bits(s, P_<uint32_t>(s->d_agg)));
   LSG_RC(ensure(s, s->d_aux, 96 * n_sets));
   KL(s, "k_g1p_to_bytes", lsgk::g1p_to_bytes(S_(s), (int)n_sets, P_<uint32_t>(s->d_agg), P_<uint8_t>(s->d_aux)));
   std::vector<int32_t> pkerr(std::max(np, (size_t)1));
@@ -3052,6 +3152,8 @@ int lsg_aggregate_pubkeys_multi(lsg_ctx* c, const lsg_set* sets, size_t n_sets, 
   keep_times(s);
   for (size_t i = 0; i < n_sets; i++) {
     err[i] = s->shape.pk_cnt[i] == 0 ? LSG_ERR_EMPTY_AGGREGATE : 0;
+    if (!s->shape.bits_p.empty() && s->shape.bits_p[i] >= 0)
+      err[i] = s->shape.bits_kerr[i] ? s->shape.bits_kerr[i] : (s->shape.bits_p[i] ? 0 : LSG_ERR_EMPTY_AGGREGATE);
     for (uint32_t q = 0; q < s->shape.pk_cnt[i] && !err[i]; q++) err[i] = pkerr[s->shape.pk_first[i] + q];
   }
   return LSG_OK;
@@ -3062,11 +3164,150 @@ int lsg_pubkey_table_set(lsg_ctx* c, size_t first, const uint8_t* pks, uint32_t 
   std::unique_lock<std::shared_mutex> tab(c->tab_mu);  // no package is being staged from the table
   LSG_ENTER(c);
   if (n == 0) return LSG_OK;
+  // a rewritten row may be a member of a registered committee, whose stored sum would then be
+  // stale: every committee is unset (appends leave them alone)
+  if (first < c->dev[0]->pktab_n) std::fill(c->cm_ok.begin(), c->cm_ok.end(), (uint8_t)0);
   std::vector<int32_t> pkerr;
   for (int d = 0; d < c->n_dev; d++) LSG_RC(dev_pktab_set(c->dev[d], first, pks, pk_len, n, pkerr));
   (void)hipSetDevice(c->dev[0]->device);
   if (err)
     for (size_t k = 0; k < n; k++) err[k] = pkerr[k];
+  return LSG_OK;
+}
+
+int lsg_committees_set(lsg_ctx* c, uint32_t first_id, const uint32_t* indices, const uint32_t* offsets, size_t n,
+                       int32_t* err) {
+  if (!c || (n && !offsets) || first_id > COMMITTEE_MAX_ID || n > COMMITTEE_MAX_ID - first_id) return LSG_ERR_INVALID_ARG;
+  if (n == 0) return LSG_OK;
+  if (offsets[0] != 0) return LSG_ERR_INVALID_ARG;
+  for (size_t k = 0; k < n; k++)
+    if (offsets[k + 1] < offsets[k] || offsets[k + 1] - offsets[k] > COMMITTEE_MAX_LEN) return LSG_ERR_INVALID_ARG;
+  const size_t total = offsets[n];
+  if ((total && !indices) || total > 0x7fffffffull) return LSG_ERR_INVALID_ARG;
+  std::unique_lock<std::shared_mutex> tab(c->tab_mu);  // no package is being staged from the committees
+  LSG_ENTER(c);
+  // host rows: the new committees appended; the rows they replace become dead words
+  const size_t ids = std::max(c->cm_ok.size(), (size_t)first_id + n);
+  c->cm_len.resize(ids, 0);
+  c->cm_off.resize(ids, 0);
+  c->cm_ok.resize(ids, 0);
+  for (size_t k = 0; k < n; k++) {
+    c->cm_dead += c->cm_len[first_id + k];
+    c->cm_len[first_id + k] = 0;
+    c->cm_ok[first_id + k] = 0;
+  }
+  if (c->cm_dead > c->cm_rows.size() / 2 + 65536) {  // compact: the live committees in id order
+    std::vector<uint32_t> rows;
+    rows.reserve(c->cm_rows.size() - c->cm_dead + total);
+    for (size_t id = 0; id < ids; id++) {
+      const uint32_t o = c->cm_off[id];
+      c->cm_off[id] = (uint32_t)rows.size();
+      if (c->cm_ok[id]) rows.insert(rows.end(), c->cm_rows.begin() + o, c->cm_rows.begin() + o + c->cm_len[id]);
+      else c->cm_len[id] = 0;
+    }
+    c->cm_rows.swap(rows);
+    c->cm_dead = 0;
+  }
+  const size_t base = c->cm_rows.size();
+  if (base + total > 0xffffffffull) {
+    c->err = "lsg_committees_set: more than 2^32 committee members registered";
+    return LSG_ERR_INVALID_ARG;
+  }
+  if (total) c->cm_rows.insert(c->cm_rows.end(), indices, indices + total);
+  // the sums: the aggregation over index keys, one set per committee, on every device
+  std::vector<lsg_set> ks(n);
+  std::vector<const lsg_set*> sp(n);
+  for (size_t k = 0; k < n; k++) {
+    memset(&ks[k], 0, sizeof(lsg_set));
+    ks[k].pks = (const uint8_t*)(indices + offsets[k]);
+    ks[k].pk_len = LSG_PK_INDEX;
+    ks[k].n_pks = offsets[k + 1] - offsets[k];
+    sp[k] = &ks[k];
+  }
+  std::vector<int32_t> cerr(n, 0), pkerr(std::max(total, (size_t)1));
+  for (int di = 0; di < c->n_dev; di++) {
+    Dev* d = c->dev[di];
+    Slot* s = &d->util;
+    LSG_HIPC(c, hipSetDevice(d->device));
+    // packages in flight read the rows and sums: drain the device before they move or change
+    LSG_HIPC(c, hipDeviceSynchronize());
+    timer_reset(s);
+    // grow (copying what is there), then rewrite the whole index arena when it was compacted
+    auto grow = [&](DevBuf& b, size_t bytes) -> int {
+      if (b.cap >= bytes) return LSG_OK;
+      DevBuf nb;
+      const size_t cap = std::max(bytes + bytes / 2, (size_t)65536);
+      LSG_HIPC(c, hipMalloc(&nb.p, cap));
+      g_allocs++;
+      trace_alloc("device", cap);
+      nb.cap = cap;
+      if (b.p) LSG_HIPC(c, hipMemcpy(nb.p, b.p, b.cap, hipMemcpyDeviceToDevice));
+      free_dev(b);
+      b = nb;
+      return LSG_OK;
+    };
+    LSG_RC(grow(d->d_cm_idx, 4 * c->cm_rows.size()));
+    LSG_RC(grow(d->d_cm_off, 4 * ids));
+    LSG_RC(grow(d->d_cm_sum, 4 * W_G1P * ids));
+    LSG_RC(stage_sets(s, sp.data(), n, 0, false));
+    LSG_RC(size_state(s, n, 0, 1, 0));  // (no projective copy of the keys: the fold fetches them)
+    LSG_RC(ensure(s, s->d_pkerr, 4 * total));
+    s->plan.clear();
+    s->single_keys = false;
+    s->pkagg = plan_pk_agg(s);
+    LSG_RC(upload_plan(s));
+    LSG_RC(run_pk_seg(s, s->pkagg, P_<uint32_t>(s->d_agg)));
+    if (total) LSG_HIP(s, hipMemcpyAsync(pkerr.data(), s->d_pkerr.p, 4 * total, hipMemcpyDeviceToHost, s->st[0]));
+    LSG_HIP(s, hipMemcpyAsync(P_<uint32_t>(d->d_cm_sum) + W_G1P * (size_t)first_id, s->d_agg.p, 4 * W_G1P * n,
+                              hipMemcpyDeviceToDevice, s->st[0]));
+    LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+    keep_times(s);
+    for (size_t k = 0; k < n; k++) {
+      int32_t e = offsets[k + 1] == offsets[k] ? LSG_ERR_EMPTY_AGGREGATE : 0;
+      for (uint32_t q = offsets[k]; q < offsets[k + 1] && !e; q++) e = pkerr[q];
+      if (e && !cerr[k]) cerr[k] = e;
+    }
+  }
+  for (size_t k = 0; k < n; k++) {
+    c->cm_off[first_id + k] = (uint32_t)(base + offsets[k]);
+    if (cerr[k]) {  // stays unset: its rows are dead at once
+      c->cm_dead += offsets[k + 1] - offsets[k];
+      continue;
+    }
+    c->cm_len[first_id + k] = offsets[k + 1] - offsets[k];
+    c->cm_ok[first_id + k] = 1;
+  }
+  for (int di = 0; di < c->n_dev; di++) {
+    Dev* d = c->dev[di];
+    LSG_HIPC(c, hipSetDevice(d->device));
+    // (after a compaction every offset moved: the whole arena and offset list go up again)
+    LSG_HIPC(c, hipMemcpy(d->d_cm_idx.p, c->cm_rows.data(), 4 * c->cm_rows.size(), hipMemcpyHostToDevice));
+    LSG_HIPC(c, hipMemcpy(d->d_cm_off.p, c->cm_off.data(), 4 * ids, hipMemcpyHostToDevice));
+  }
+  (void)hipSetDevice(c->dev[0]->device);
+  if (err)
+    for (size_t k = 0; k < n; k++) err[k] = cerr[k];
+  return LSG_OK;
+}
+
+int lsg_committees_clear(lsg_ctx* c, uint32_t first_id, size_t n) {
+  if (!c || first_id > COMMITTEE_MAX_ID || n > COMMITTEE_MAX_ID - first_id) return LSG_ERR_INVALID_ARG;
+  std::unique_lock<std::shared_mutex> tab(c->tab_mu);
+  std::lock_guard<std::mutex> lk(c->mu);
+  for (size_t id = first_id; id < (size_t)first_id + n && id < c->cm_ok.size(); id++) {
+    c->cm_dead += c->cm_len[id];
+    c->cm_len[id] = 0;
+    c->cm_ok[id] = 0;
+  }
+  return LSG_OK;
+}
+
+int lsg_committee_count(lsg_ctx* c, size_t* n) {
+  if (!c || !n) return LSG_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  size_t hi = c->cm_ok.size();
+  while (hi && !c->cm_ok[hi - 1]) hi--;
+  *n = hi;
   return LSG_OK;
 }
 

@@ -3,6 +3,7 @@
 // KeyValidate (8f(2), block/processDeposit.ts:57-65), the RLC scaling [r_i] aggPK_i of blst
 // mul_n_aggregate (8a M4) and G1 serialisation.
 #include "lsg_kcommon.hpp"
+#include "lsg_bits.h"
 namespace {
 #include "lsg_inv.hpp"
 }  // namespace
@@ -92,6 +93,75 @@ __global__ void LSG_KERNEL_ATTR k_pk_agg_seg(int n_chunks, int ips_log2, const i
       lane_store(dst, (size_t)out, acc);
     else
       lane_store(tmp, (size_t)(-out - 1), acc);
+  }
+}
+
+// PublicKey.aggregate of sets given as committee id + participation bits (LSG_PK_BITS; SURVEY.md
+// 8f(5)): the committees' index rows and full sums are resident (lsg_committees_set), a set
+// stages its bitfield only.  Lane pair `item` works for plan entry pair_set[item] (lsg_plan.hpp
+// plan_bits: committee, arena word, n_bits, mode | pairs log2 << 8, output slot, first pair).
+// The set's pairs share its WANTED members round robin (lsg_bits.h: the set bits, or in
+// complement mode the clear bits below n_bits), each folding its own with complete mixed
+// additions -- the member's table row gathered through the committee's index row, the next
+// row in flight while this one is added, as in k_pk_agg_seg -- then a butterfly over the
+// set's pairs.  In complement mode the lead pair finishes with sum[committee] - acc, one
+// complete addition (RCB 2016 algorithm 7 has no exceptional case: acc or the sum at
+// infinity, acc == sum and acc == -sum included).  n_bits == 0 writes the identity.
+__global__ void LSG_KERNEL_ATTR k_pk_agg_bits(int n_pairs, const int32_t* __restrict__ pair_set,
+                                              const int32_t* __restrict__ plan, const uint32_t* __restrict__ bits,
+                                              const uint32_t* __restrict__ cm_idx, const uint32_t* __restrict__ cm_off,
+                                              const uint32_t* __restrict__ cm_sum, const uint32_t* __restrict__ tab,
+                                              const uint8_t* __restrict__ tab_ok, uint32_t tab_n,
+                                              uint32_t* __restrict__ dst) {
+  lsg_lane_setup();
+  const size_t item = gtid() / LSG_GROUP;
+  const bool active = item < (size_t)n_pairs;
+  g1p_t acc = proj_inf<fp_t>();
+  int ips = 1, j = 0, out = 0;
+  uint32_t cid = 0;
+  bool complement = false;
+  if (active) {
+    const int32_t* q = plan + LSG_BITS_PLAN_WORDS * (size_t)pair_set[item];
+    cid = (uint32_t)q[0];
+    const uint32_t* field = bits + (uint32_t)q[1];
+    const uint32_t n_bits = (uint32_t)q[2];
+    complement = (q[3] & 1) != 0;
+    ips = 1 << (q[3] >> 8);
+    out = q[4];
+    j = (int)item - q[5];
+    if (n_bits) {
+      const uint32_t inv = complement ? ~0u : 0u;
+      const uint32_t* row = cm_idx + cm_off[cid];
+      auto fetch = [&](int32_t m, g1a_t& a) {  // member m's key: false for the infinity key
+        const uint32_t idx = row[m];
+        const uint8_t ok = idx < tab_n ? tab_ok[idx] : 0;
+        a = lane_load<g1a_t>(tab + (size_t)(ok == 1 ? idx : 0) * lsgl::W_TAB, 0);
+        return ok == 1;
+      };
+      lsg_bits_walk w = lsg_bits_begin(field, n_bits, inv, (uint32_t)j);
+      g1a_t a;
+      bool fin = false;
+      int32_t m = lsg_bits_next(field, n_bits, inv, (uint32_t)ips, w);
+      if (m >= 0) fin = fetch(m, a);
+#pragma unroll 1
+      while (m >= 0) {
+        const g1a_t cur = a;
+        const bool cur_fin = fin;
+        m = lsg_bits_next(field, n_bits, inv, (uint32_t)ips, w);
+        if (m >= 0) fin = fetch(m, a);
+        if (cur_fin) acc = proj_is_inf(acc) ? proj_from_aff(cur) : g1_add_mixed(acc, cur);
+      }
+    }
+  }
+  // every lane shuffles; a lane adds while the partner is one of its own set's pairs
+#pragma unroll 1
+  for (int o = 16; o >= 1; o >>= 1) {
+    const g1p_t t = shfl_xor_t(acc, LSG_GROUP * o);
+    if (o < ips) acc = g1_add(acc, t);
+  }
+  if (active && j == 0) {
+    if (complement) acc = g1_add(lane_load<g1p_t>(cm_sum, (size_t)cid), proj_neg(acc));
+    lane_store(dst, (size_t)out, acc);
   }
 }
 
@@ -500,6 +570,12 @@ hipError_t pk_agg_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t*
                       uint32_t* dst, uint32_t* tmp) {
   LSG_LAUNCH_ITEMS(k_pk_agg_seg, (size_t)n_chunks << ips_log2, st, n_chunks, ips_log2, chunks, pk, stride, pk_len, err,
                    tab, tab_ok, tab_n, dst, tmp);
+}
+hipError_t pk_agg_bits(hipStream_t st, int n_pairs, const int32_t* pair_set, const int32_t* plan, const uint32_t* bits,
+                       const uint32_t* cm_idx, const uint32_t* cm_off, const uint32_t* cm_sum, const uint32_t* tab,
+                       const uint8_t* tab_ok, uint32_t tab_n, uint32_t* dst) {
+  LSG_LAUNCH_ITEMS(k_pk_agg_bits, n_pairs, st, n_pairs, pair_set, plan, bits, cm_idx, cm_off, cm_sum, tab, tab_ok, tab_n,
+                   dst);
 }
 hipError_t agg_leaf(hipStream_t st, const AggTreeArgs& a) {
   if (a.L <= 0) return hipSuccess;

@@ -68,6 +68,13 @@ hipError_t pk_gather_aff(hipStream_t st, int n, const uint8_t* pk, uint32_t stri
 hipError_t pk_agg_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t* chunks, const uint8_t* pk, uint32_t stride,
                       const uint32_t* pk_len, int32_t* err, const uint32_t* tab, const uint8_t* tab_ok, uint32_t tab_n,
                       uint32_t* dst, uint32_t* tmp);
+// PublicKey.aggregate of the sets given as committee id + participation bits (k_pk_agg_bits;
+// plan: lsg_plan.hpp plan_bits, n_pairs lane pairs): pair_set / plan are the plan's two arena
+// ranges, bits the staged bit arena, cm_* the device's committee store (lsg_committees_set:
+// index rows, each id's first row word, each id's projective sum), dst the aggregates
+hipError_t pk_agg_bits(hipStream_t st, int n_pairs, const int32_t* pair_set, const int32_t* plan, const uint32_t* bits,
+                       const uint32_t* cm_idx, const uint32_t* cm_off, const uint32_t* cm_sum, const uint32_t* tab,
+                       const uint8_t* tab_ok, uint32_t tab_n, uint32_t* dst);
 // the batch-affine aggregation tree (lsg_k_pk.hip k_agg_*; plan: lsg_host.hip plan_agg_tree).
 // Level 0 holds every tree set's keys at an offset aligned to 2^L, padded with infinity up to
 // the next multiple (N0 points); level t + 1 point q is the sum of level t points 2q and

@@ -9,12 +9,15 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string.h>
+
 #include <algorithm>
 #include <functional>
 #include <utility>
 #include <vector>
 
 #include "../../include/lodestar_bls.h"
+#include "lsg_bits.h"
 
 namespace lsgp {
 
@@ -381,6 +384,11 @@ struct PkgShape {
   // the device (LSG_JOB_VALIDATE_KEYS; empty when the package has no such key)
   std::vector<uint32_t> pk_cnt, pk_first;
   std::vector<uint8_t> kv_set;
+  // sets whose keys are a committee id + participation bits (LSG_PK_BITS; both empty when the
+  // package has none): bits_p[i] = the set's participant count, -1 for a set of another kind
+  // (such a set stages no key slots: pk_cnt[i] == 0); bits_kerr[i] = its set-level key error
+  // resolved on the host (LSG_ERR_BAD_COMMITTEE), routed like a key that does not deserialize
+  std::vector<int32_t> bits_p, bits_kerr;
 };
 
 // Staging order of jobs `ids` of `jobs` (batchable jobs first, each kind in caller order) and
@@ -492,6 +500,10 @@ inline int32_t first_key_error(const PkgShape& sh, const int32_t* pkerr, size_t 
     const JobRec& J = sh.jobs[k];
     for (size_t i = J.first; i < J.first + J.count; i++) {
       if (!sh.kv_set.empty() && sh.kv_set[i]) continue;
+      if (!sh.bits_kerr.empty() && sh.bits_kerr[i]) {
+        *job = k;
+        return sh.bits_kerr[i];
+      }
       for (uint32_t q = 0; q < sh.pk_cnt[i]; q++)
         if (const int32_t e = pkerr[sh.pk_first[i] + q]) {
           *job = k;
@@ -500,6 +512,125 @@ inline int32_t first_key_error(const PkgShape& sh, const int32_t* pkerr, size_t 
     }
   }
   return 0;
+}
+
+// ---- committee-resident keys: a set given as committee id + participation
+// bits (LSG_PK_BITS).  The device holds every registered committee's index row and its full
+// sum; a set's aggregate is either the sum of its participants (direct mode) or the committee
+// sum minus the sum of its absentees (complement mode), whichever takes fewer additions.
+//
+// Limits of lsg_committees_set
+constexpr uint32_t COMMITTEE_MAX_ID = 1u << 20;   // ids are below this
+constexpr uint32_t COMMITTEE_MAX_LEN = 131072;    // members per committee
+
+// Mode rule: p participants among n_bits, a = n_bits - p absentees.  Complement mode costs a
+// mixed additions plus the final full addition with the committee sum, direct mode p.
+inline bool bits_complement(uint32_t n_bits, uint32_t p) { return (uint64_t)(n_bits - p) + 1 < (uint64_t)p; }
+inline uint32_t bits_wanted(uint32_t n_bits, uint32_t p) { return bits_complement(n_bits, p) ? n_bits - p : p; }
+
+// Lane pairs of one set (log2): each pair folds at most `fold` wanted members serially before
+// the butterfly, up to a wave's 32 pairs (a set never straddles a wave); beyond 32 * fold wanted
+// members the serial fold grows instead.  fold is BITS_FOLD (~5 absentees: 2 pairs) unless the
+// launch is work-bound, as in plan_seg: while the sets together would take more than
+// BITS_WIDE_PAIRS lane pairs, every butterfly level costs each of them one full addition the
+// chip has no idle lanes for, so the fold doubles, up to BITS_FOLD_WIDE (plan_bits).
+constexpr int BITS_FOLD = 4;
+constexpr int BITS_FOLD_WIDE = 64;
+constexpr size_t BITS_WIDE_PAIRS = SEG_WIDE_PAIRS;
+constexpr int BITS_MAX_PAIRS_LOG2 = 5;
+inline int bits_pairs_log2(uint32_t wanted, int fold = BITS_FOLD) {
+  int l = 0;
+  while (l < BITS_MAX_PAIRS_LOG2 && ((uint32_t)fold << l) < wanted) l++;
+  return l;
+}
+
+// Staged bit arena: set after set, each field starting on a 32-bit word and taking
+// ceil(n_bits / 32) words (lsg_bits.h: the caller's bytes as they are, the tail of the last
+// word zeroed).  Hosts are little-endian, as the device is.
+inline size_t bits_words(uint32_t n_bits) { return ((size_t)n_bits + 31) >> 5; }
+inline void bits_stage(uint32_t* dst, const uint8_t* src, uint32_t n_bits) {
+  const size_t nw = bits_words(n_bits), nb = ((size_t)n_bits + 7) >> 3;
+  if (nw) dst[nw - 1] = 0;
+  if (nb) memcpy(dst, src, nb);
+}
+// participants: set bits among the first n_bits of an SSZ bitvector
+inline uint32_t bits_count(const uint8_t* src, uint32_t n_bits) {
+  uint32_t p = 0;
+  const size_t full = n_bits >> 3;
+  for (size_t k = 0; k < full; k++) p += (uint32_t)__builtin_popcount(src[k]);
+  if (n_bits & 7) p += (uint32_t)__builtin_popcount(src[full] & ((1u << (n_bits & 7)) - 1u));
+  return p;
+}
+
+// One bits set as staged: n_bits == 0 means "write the identity" (a set whose error the host
+// already knows, or with no participant).
+struct BitsSet {
+  uint32_t committee = 0;
+  uint32_t word_off = 0;  // its field's first word in the bit arena
+  uint32_t n_bits = 0;
+  uint32_t p = 0;         // participants
+  int32_t out = 0;        // aggregate slot (the set's staging position)
+};
+// A set of a registered committee as the stager records it: its field appended to the arena
+// (*words in use) -- or, with no participant, the identity entry and nothing staged.
+inline BitsSet bits_stage_set(uint32_t committee, const uint8_t* bits, uint32_t n_bits, int32_t out, uint32_t* arena,
+                              size_t* words) {
+  BitsSet b;
+  b.out = out;
+  const uint32_t p = bits_count(bits, n_bits);
+  if (!p) return b;
+  b.committee = committee;
+  b.word_off = (uint32_t)*words;
+  b.n_bits = n_bits;
+  b.p = p;
+  bits_stage(arena + *words, bits, n_bits);
+  *words += bits_words(n_bits);
+  return b;
+}
+// Per-set plan words of k_pk_agg_bits: committee id, arena word offset, n_bits, mode (bit 0:
+// complement) | pairs log2 << 8, output slot, first lane pair.
+constexpr int BITS_PLAN_WORDS = LSG_BITS_PLAN_WORDS;
+struct BitsPlan {
+  size_t n_sets = 0, n_pairs = 0;
+  int fold = BITS_FOLD;  // serial folds per lane pair the widths were chosen for
+  size_t plan_off = 0;  // n_sets x BITS_PLAN_WORDS words in the arena
+  size_t pair_off = 0;  // n_pairs words: the plan entry each lane pair works for
+};
+// Sets are laid out over the launch's lane pairs widest first, so every set starts on a
+// multiple of its own (power of two) width: it never straddles a wave and its butterfly
+// partners are its own pairs.
+inline BitsPlan plan_bits(std::vector<int32_t>& A, const std::vector<BitsSet>& sets) {
+  BitsPlan P;
+  P.n_sets = sets.size();
+  if (sets.empty()) return P;
+  std::vector<uint32_t> order(sets.size());
+  std::vector<int> lg(sets.size());
+  for (;; P.fold *= 2) {
+    size_t pairs = 0;
+    for (size_t i = 0; i < sets.size(); i++) {
+      order[i] = (uint32_t)i;
+      lg[i] = sets[i].n_bits ? bits_pairs_log2(bits_wanted(sets[i].n_bits, sets[i].p), P.fold) : 0;
+      pairs += (size_t)1 << lg[i];
+    }
+    if (pairs <= BITS_WIDE_PAIRS || P.fold >= BITS_FOLD_WIDE) break;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lg[a] > lg[b]; });
+  P.plan_off = A.size();
+  size_t pair = 0;
+  for (uint32_t i : order) {
+    const BitsSet& b = sets[i];
+    A.push_back((int32_t)b.committee);
+    A.push_back((int32_t)b.word_off);
+    A.push_back((int32_t)b.n_bits);
+    A.push_back((b.n_bits && bits_complement(b.n_bits, b.p) ? 1 : 0) | (lg[i] << 8));
+    A.push_back(b.out);
+    A.push_back((int32_t)pair);
+    pair += (size_t)1 << lg[i];
+  }
+  P.n_pairs = pair;
+  P.pair_off = A.size();
+  for (size_t e = 0; e < order.size(); e++) A.insert(A.end(), (size_t)1 << lg[order[e]], (int32_t)e);
+  return P;
 }
 
 // ---- phase-A groups

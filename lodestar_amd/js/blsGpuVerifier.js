@@ -84,6 +84,7 @@ const BLST_NAMES = {
 function errorMessage(code) {
   if (code === 100) return "Empty signature set"; // maybeBatch.ts:29-31
   if (code === 101) return "EMPTY_AGGREGATE_ARRAY"; // PublicKey.aggregate([])
+  if (code === 103) return "Unknown committee or bit length mismatch"; // LSG_ERR_BAD_COMMITTEE
   return "BLST_ERROR: " + (BLST_NAMES[code] || "BLST_UNKNOWN_" + code);
 }
 
@@ -132,6 +133,11 @@ function pubkeyBytes(pk) {
 /** ISignatureSet -> the addon's set (utils.ts:5-17 getAggregatedPubkey, with the sum done on
  * the GPU instead of the main thread). */
 function serializeSet(set) {
+  // signers named by a committee loaded with loadCommittees() plus participation bits (8f(5))
+  if (set.committee !== undefined) {
+    checkBitsSet(set);
+    return {committee: set.committee, bits: set.bits, bitLen: set.bitLen, message: set.signingRoot, signature: set.signature};
+  }
   // signers named by validator index into the device pubkey table (SURVEY 8f(1)):
   // loadPubkeys() mirrors index2pubkey; the set carries its attesting indices
   if (set.pubkeyIndices !== undefined) {
@@ -191,11 +197,72 @@ function verifyDirect(addon, ctx, sets, seed, validate = false) {
   return p;
 }
 
+/** Limits of lsg_committees_set (include/lodestar_bls.h) */
+const MAX_COMMITTEE_ID = 1 << 20;
+const MAX_COMMITTEE_LEN = 131072;
+const PK_BITS = 8; // LSG_PK_BITS
+
+/** A set that names its signers as {committee, bits, bitLen}: committee is an id given to
+ * loadCommittees, bits the participation bitfield in SSZ order without a delimiter bit (member k
+ * is bit k & 7 of byte k >> 3, e.g. a BitArray's uint8Array), bitLen the committee's length. */
+function checkBitsSet(set) {
+  if (!Number.isInteger(set.committee) || set.committee < 0 || set.committee >= MAX_COMMITTEE_ID) {
+    throw Error("committee must be an id below 2^20");
+  }
+  if (!Number.isInteger(set.bitLen) || set.bitLen < 0 || set.bitLen > MAX_COMMITTEE_LEN) {
+    throw Error("bitLen must be the committee's length");
+  }
+  if (!(set.bits instanceof Uint8Array) || set.bits.length < ((set.bitLen + 7) >> 3)) {
+    throw Error("bits must be a Uint8Array of at least ceil(bitLen / 8) bytes");
+  }
+}
+
+/** participants of a {committee, bits, bitLen} set: the set bits among the first bitLen */
+function countBits(bits, bitLen) {
+  let n = 0;
+  const full = bitLen >> 3;
+  for (let i = 0; i <= full && i < bits.length; i++) {
+    let b = i < full ? bits[i] : bits[i] & ((1 << (bitLen & 7)) - 1);
+    for (; b; b &= b - 1) n++;
+  }
+  return n;
+}
+
+/** loadCommittees' arguments -> (indices, offsets) of lsg_committees_set */
+function flattenCommittees(firstId, committees) {
+  if (!Number.isInteger(firstId) || firstId < 0 || !Array.isArray(committees) || firstId + committees.length > MAX_COMMITTEE_ID) {
+    throw Error("loadCommittees(firstId, committees): ids must stay below 2^20");
+  }
+  const offsets = new Uint32Array(committees.length + 1);
+  for (let c = 0; c < committees.length; c++) {
+    const m = committees[c];
+    if (!(m instanceof Uint32Array) && !Array.isArray(m)) throw Error("a committee must be an array of validator indices");
+    if (m.length > MAX_COMMITTEE_LEN) throw Error("a committee has at most 131072 members");
+    offsets[c + 1] = offsets[c] + m.length;
+  }
+  const indices = new Uint32Array(offsets[committees.length]);
+  for (let c = 0; c < committees.length; c++) {
+    const m = committees[c];
+    for (let k = 0; k < m.length; k++) {
+      if (!Number.isInteger(m[k]) || m[k] < 0 || m[k] > 0xffffffff) throw Error("a committee member must be a validator index");
+      indices[offsets[c] + k] = m[k];
+    }
+  }
+  return {indices, offsets};
+}
+
+function loadCommitteesSync(addon, ctx, firstId, committees) {
+  const {indices, offsets} = flattenCommittees(firstId, committees);
+  if (typeof addon.committeesSet !== "function") throw Error("the addon does not support loadCommittees");
+  return Array.from(addon.committeesSet(ctx, firstId, indices, offsets));
+}
+
 /** utils.ts:19-26 */
 function getAggregatedPubkeysCount(sets) {
   let n = 0;
   for (const set of sets) {
-    if (set.pubkeyIndices !== undefined) n += set.pubkeyIndices.length;
+    if (set.committee !== undefined) n += set.bits instanceof Uint8Array ? countBits(set.bits, set.bitLen) : 0;
+    else if (set.pubkeyIndices !== undefined) n += set.pubkeyIndices.length;
     else if (set.type === SignatureSetType.aggregate) n += set.pubkeys.length;
   }
   return n;
@@ -237,6 +304,10 @@ function loadAddon() {
 
 /** Reference set shape check done at call time, as serializeSet throws there (index.ts:177). */
 function checkSet(set) {
+  if (set.committee !== undefined) {
+    checkBitsSet(set);
+    return;
+  }
   if (set.pubkeyIndices === undefined && set.type !== SignatureSetType.single && set.type !== SignatureSetType.aggregate) {
     throw Error("Unknown signature set type");
   }
@@ -417,10 +488,11 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
         for (let si = 0; si < sets.length; si++) {
           const set = sets[si];
           const d = SET_DESC_WORDS * k;
-          const pk1 = set.pubkeyIndices === undefined && set.type === SignatureSetType.single ? set.pubkey : null;
+          const pk1 =
+            set.committee === undefined && set.pubkeyIndices === undefined && set.type === SignatureSetType.single ? set.pubkey : null;
           const root = set.signingRoot;
           const sig = set.signature;
-          if (pk1 instanceof Uint8Array && off + pk1.length + root.length + sig.length <= cap) {
+          if (pk1 instanceof Uint8Array && pk1.length !== PK_BITS && off + pk1.length + root.length + sig.length <= cap) {
             // the common shape (one raw key): three copies, no helper calls
             arena.set(pk1, off);
             sd[d] = off;
@@ -438,7 +510,15 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
             k++;
             continue;
           }
-          if (set.pubkeyIndices !== undefined) {
+          if (set.committee !== undefined) {
+            // committee id (host byte order), then the first ceil(bitLen / 8) bytes of the bitfield
+            checkBitsSet(set);
+            const id = new Uint32Array([set.committee]);
+            sd[d] = put(new Uint8Array(id.buffer));
+            put(set.bits.subarray(0, (set.bitLen + 7) >> 3));
+            sd[d + 1] = PK_BITS;
+            sd[d + 2] = set.bitLen;
+          } else if (set.pubkeyIndices !== undefined) {
             const ix = set.pubkeyIndices instanceof Uint32Array ? set.pubkeyIndices : Uint32Array.from(set.pubkeyIndices);
             sd[d] = put(new Uint8Array(ix.buffer, ix.byteOffset, 4 * ix.length));
             sd[d + 1] = 4; // LSG_PK_INDEX
@@ -446,7 +526,7 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
           } else if (set.type === SignatureSetType.single) {
             const pk = pubkeyBytes(set.pubkey);
             sd[d] = put(pk);
-            sd[d + 1] = pk.length;
+            sd[d + 1] = pk.length === PK_BITS ? 0 : pk.length; // (8 bytes: an unknown key length, not LSG_PK_BITS)
             sd[d + 2] = 1;
           } else if (set.type === SignatureSetType.aggregate) {
             const pks = set.pubkeys;
@@ -457,7 +537,7 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
               if (b.length !== len) throw Error("every pubkey of an aggregate set must have the same encoding");
               put(b);
             }
-            sd[d + 1] = len;
+            sd[d + 1] = len === PK_BITS ? 0 : len;
             sd[d + 2] = pks.length;
           } else {
             throw Error("Unknown signature set type");
@@ -573,6 +653,21 @@ class BlsGpuVerifier {
    * `pubkeyIndices` instead of PublicKeys.  Returns per-key BLST codes (0 = loaded). */
   loadPubkeys(firstIndex, pubkeys) {
     return this.addon.pubkeyTableSet(this.ctx, firstIndex, pubkeys.map(pubkeyBytes));
+  }
+
+  /** Register committees on the device (SURVEY 8f(5); call where the node fills its shuffling
+   * and sync-committee caches): committee firstId + c <- committees[c], validator indices in
+   * committee order (rows loaded with loadPubkeys).  An aggregate set may then carry
+   * {committee, bits, bitLen} instead of pubkeys or pubkeyIndices.  Returns per-committee codes
+   * (0 = registered; 102: a member names an unloaded index; 101: an empty committee). */
+  loadCommittees(firstId, committees) {
+    return loadCommitteesSync(this.addon, this.ctx, firstId, committees);
+  }
+
+  /** Unset committees firstId .. firstId + n - 1 (an epoch's committees that are no longer used). */
+  clearCommittees(firstId, n) {
+    if (typeof this.addon.committeesClear !== "function") throw Error("the addon does not support clearCommittees");
+    this.addon.committeesClear(this.ctx, firstId, n);
   }
 
   /** Op-pool aggregation (SURVEY 8f(4)): bls.Signature.aggregate(sigs.map(signatureFromBytesNoCheck))
@@ -914,6 +1009,12 @@ class BlsGpuSingleThreadVerifier {
     return valid;
   }
 
+  /** as BlsGpuVerifier.loadCommittees */
+  loadCommittees(firstId, committees) {
+    if (!this.ctx) throw new QueueError({code: QueueErrorCode.QUEUE_ABORTED});
+    return loadCommitteesSync(this.addon, this.ctx, firstId, committees);
+  }
+
   /** processDeposit.ts:47-66 for a list of deposits, as BlsGpuVerifier.verifyDeposits */
   async verifyDeposits(depositDatas, domain) {
     if (!this.ctx) throw new QueueError({code: QueueErrorCode.QUEUE_ABORTED});
@@ -948,6 +1049,7 @@ module.exports = {
   chunkifyMaximizeChunkSize,
   errorMessage,
   packJobs,
+  getAggregatedPubkeysCount,
   DEFAULT_MAX_SIGS_PER_PACKAGE,
   MAX_SIGNATURE_SETS_PER_JOB,
   MAX_BUFFERED_SIGS,

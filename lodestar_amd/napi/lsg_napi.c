@@ -36,7 +36,10 @@
  *   verifyDeposits(ctx, data: n x 184 B, domain: 32 B) -> {valid: Uint8Array, err: Int32Array}
  *                                                                      lsg_verify_deposits
  *   pubkeyValidate(ctx, pks: n x pkLen B, pkLen) -> Int32Array         lsg_pubkey_validate
- *       (these two throw "not supported" when the loaded library lacks the entry point)
+ *   committeesSet(ctx, firstId, indices: Uint32Array, offsets: Uint32Array) -> Int32Array
+ *   committeesClear(ctx, firstId, n)                                   lsg_committees_set / _clear
+ *       (a set descriptor may then have pk_len 8 = LSG_PK_BITS: committee id + bits, n_pks bits)
+ *       (these four throw "does not support" when the loaded library lacks the entry point)
  * Failures of the library itself (not verdicts) throw an Error carrying lsg_last_error().
  */
 #include <node_api.h>
@@ -53,6 +56,9 @@ extern int lsg_verify_deposits(lsg_ctx* ctx, const uint8_t* data184, size_t n, c
                                uint8_t* valid, int32_t* err) __attribute__((weak));
 extern int lsg_pubkey_validate(lsg_ctx* ctx, const uint8_t* pks, uint32_t pk_len, size_t n, uint8_t* out96,
                                int32_t* err) __attribute__((weak));
+extern int lsg_committees_set(lsg_ctx* ctx, uint32_t first_id, const uint32_t* indices, const uint32_t* offsets,
+                              size_t n_committees, int32_t* err) __attribute__((weak));
+extern int lsg_committees_clear(lsg_ctx* ctx, uint32_t first_id, size_t n) __attribute__((weak));
 
 #define LSG_NAPI_THREADS 16 /* package threads per context: one outstanding package each */
 
@@ -189,7 +195,8 @@ static int view_sets(napi_env env, napi_value arr, set_view* out) {
       napi_value k0;
       napi_get_element(env, pk, 0, &k0);
       if (get_bytes(env, k0, &d, &len)) goto bad;
-      q->pk_len = (uint32_t)len;
+      /* (an 8-byte "key" is an unknown key length, never a committee + bits set: LSG_PK_BITS) */
+      q->pk_len = len == LSG_PK_BITS ? 0 : (uint32_t)len;
       if (npk == 1) {
         q->pks = d;
       } else {
@@ -371,7 +378,8 @@ static int build_jobs(pkg_req* r, lsg_set** sets_out, lsg_job** jobs_out) {
   for (uint32_t i = 0; i < r->n_sets; i++) {
     const uint32_t* d = r->sdesc + 7 * (size_t)i;
     lsg_set* q = &sets[i];
-    const uint64_t pk_bytes = (uint64_t)d[1] * d[2];
+    /* a committee + bits set (LSG_PK_BITS): the committee id, then ceil(n_pks / 8) bytes of bits */
+    const uint64_t pk_bytes = d[1] == LSG_PK_BITS ? 4 + (((uint64_t)d[2] + 7) >> 3) : (uint64_t)d[1] * d[2];
     if ((uint64_t)d[0] + pk_bytes > L || (uint64_t)d[3] + d[4] > L || (uint64_t)d[5] + d[6] > L) {
       free(sets);
       free(jobs);
@@ -972,6 +980,59 @@ static napi_value js_pubkey_validate(napi_env env, napi_callback_info info) {
   return e;
 }
 
+/* committeesSet(ctx, firstId, indices: Uint32Array, offsets: Uint32Array(n + 1)) -> Int32Array(n):
+ * lsg_committees_set -- committee firstId + c <- indices[offsets[c] .. offsets[c + 1]) (rows of
+ * the pubkey table), per-committee codes (0 = registered).  committeesClear(ctx, firstId, n). */
+static napi_value js_committees_set(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  lsg_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  uint32_t first = 0;
+  const uint32_t *ix, *offs;
+  size_t nix, noffs;
+  if (argc < 4 || napi_get_value_uint32(env, argv[1], &first) != napi_ok || get_u32s(env, argv[2], &ix, &nix) ||
+      get_u32s(env, argv[3], &offs, &noffs) || noffs < 1 || offs[0] != 0 || offs[noffs - 1] != nix) {
+    napi_throw_type_error(env, NULL,
+                          "lsg_napi: committeesSet(ctx, firstId, indices: Uint32Array, offsets: Uint32Array(n + 1))");
+    return NULL;
+  }
+  if (!lsg_committees_set) {
+    napi_throw_error(env, NULL, "lsg_napi: the loaded library does not support committeesSet (no lsg_committees_set)");
+    return NULL;
+  }
+  const size_t n = noffs - 1;
+  void* ep;
+  napi_value eab, e;
+  NAPI_CALL(env, napi_create_arraybuffer(env, 4 * (n ? n : 1), &ep, &eab));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_int32_array, n, eab, 0, &e));
+  int rc = n ? lsg_committees_set(ctx, first, ix, offs, n, (int32_t*)ep) : LSG_OK;
+  if (rc) return throw_lsg(env, ctx, "lsg_committees_set", rc);
+  return e;
+}
+
+static napi_value js_committees_clear(napi_env env, napi_callback_info info) {
+  size_t argc = 3;
+  napi_value argv[3];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  lsg_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  uint32_t first = 0, n = 0;
+  if (argc < 3 || napi_get_value_uint32(env, argv[1], &first) != napi_ok ||
+      napi_get_value_uint32(env, argv[2], &n) != napi_ok) {
+    napi_throw_type_error(env, NULL, "lsg_napi: committeesClear(ctx, firstId, n)");
+    return NULL;
+  }
+  if (!lsg_committees_clear) {
+    napi_throw_error(env, NULL, "lsg_napi: the loaded library does not support committeesClear (no lsg_committees_clear)");
+    return NULL;
+  }
+  int rc = lsg_committees_clear(ctx, first, n);
+  if (rc) return throw_lsg(env, ctx, "lsg_committees_clear", rc);
+  return NULL;
+}
+
 /* sign(ctx, sks: Uint8Array(32n, big-endian), msgs: Uint8Array(32n)) -> Uint8Array(96n) and
  * skToPk(ctx, sks) -> Uint8Array(96n): test/bench input generation on the GPU (lsg_sign,
  * lsg_sk_to_pk), not on the verify path */
@@ -1039,6 +1100,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"attestationSigningRoots", NULL, js_attestation_signing_roots, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyDeposits", NULL, js_verify_deposits, NULL, NULL, NULL, napi_enumerable, NULL},
       {"pubkeyValidate", NULL, js_pubkey_validate, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"committeesSet", NULL, js_committees_set, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"committeesClear", NULL, js_committees_clear, NULL, NULL, NULL, napi_enumerable, NULL},
   };
   NAPI_CALL(env, napi_define_properties(env, exports, sizeof props / sizeof props[0], props));
   return exports;
