@@ -86,6 +86,34 @@ extern "C" {
  * length there.  LSG_JOB_VALIDATE_KEYS leaves such sets alone, as it leaves index sets alone. */
 #define LSG_PK_BITS 8u
 
+/* or'ed into lsg_set.msg_len: msg points at an SSZ-serialized object followed by its 32-byte
+ * domain; the message signed is computeSigningRoot(object, domain)
+ * (state-transition/src/util/signingRoot.ts:7-13), computed on the device as the package's first
+ * stage (k_msg_roots).  The payload length msg_len & ~LSG_MSG_OBJECT selects the
+ * kind:
+ *    40  uint64 (Slot, Epoch: randao reveal, selection proof)
+ *    48  two uint64 fields (phase0.VoluntaryExit; altair.SyncAggregatorSelectionData)
+ *    64  Root (any object whose hashTreeRoot the caller has: block proposer, sync committee)
+ *   108  capella.BLSToExecutionChange (validatorIndex u64, fromBlsPubkey 48, toExecutionAddress 20)
+ *   120  phase0.DepositMessage (pubkey 48, withdrawalCredentials 32, amount u64)
+ *   144  phase0.BeaconBlockHeader (slot, proposerIndex, parentRoot, stateRoot, bodyRoot)
+ *   160  phase0.AttestationData (slot, index, beaconBlockRoot, source, target)
+ * Such a set behaves exactly as the same set with msg = the 32-byte signing root and msg_len = 32:
+ * verdicts, error codes and their precedence, the batch counters and the exported partial.
+ * Honoured wherever sets are staged with a message -- lsg_submit_jobs / lsg_wait_jobs /
+ * lsg_verify_jobs, lsg_verify_sets, lsg_batch_partial, coalesced packages, every device of a
+ * multi-device context, the node protocol; a package, and a job, may mix object sets with plain
+ * messages of any length, and the form combines with byte, index and bits keys and with
+ * LSG_JOB_VALIDATE_KEYS.  A marked set with another payload length or with msg == NULL is a
+ * caller bug, not data: the entry point returns LSG_ERR_INVALID_ARG before anything is staged
+ * and the context stays usable.  lsg_hash_to_g2 and lsg_sign reject a marked length with
+ * LSG_ERR_INVALID_ARG; lsg_aggregate_pubkeys_multi ignores messages as before.  Messages are
+ * deduplicated on the staged bytes (object, domain and marker): sets naming the same object and
+ * domain share one root, one hash_to_G2 and one Miller pair.  The payload bytes count toward
+ * lsg_reserve's max_msg_bytes.  A package with no marked set stages, allocates and launches
+ * exactly what it did without the form. */
+#define LSG_MSG_OBJECT 0x80000000u
+
 /* ---- job verdicts (WorkResult<boolean>, multithread/types.ts:21-24) */
 #define LSG_INVALID 0 /* {code: success, result: false} */
 #define LSG_VALID 1   /* {code: success, result: true}  */
@@ -377,6 +405,12 @@ int lsg_attestation_signing_roots(lsg_ctx* ctx, const uint8_t* data128, size_t n
  * GENESIS_FORK_VERSION, ZERO_HASH) is one constant per network. */
 int lsg_deposit_signing_roots(lsg_ctx* ctx, const uint8_t* msgs88, size_t n, const uint8_t* domain32,
                               uint32_t domain_stride, uint8_t* out32);
+/* Any object kind of LSG_MSG_OBJECT by its serialized length: objs = n objects of obj_len bytes
+ * each, obj_len one of 8, 16, 32, 76, 88, 112, 128 (another length: LSG_ERR_INVALID_ARG).  The
+ * roots are those a package computes for marked sets (one dispatcher, lsg_ssz.hpp); for 32, 128
+ * and 88 they equal the three calls above. */
+int lsg_object_signing_roots(lsg_ctx* ctx, const uint8_t* objs, uint32_t obj_len, size_t n, const uint8_t* domain32,
+                             uint32_t domain_stride, uint8_t* out32);
 
 /* processDeposit.ts:47-66 for n deposits in one device pass, synchronous, any n.  data184 = n
  * SSZ-serialized DepositData (184 bytes each: pubkey 48, withdrawalCredentials 32, amount u64,

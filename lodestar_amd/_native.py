@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("LSG_LIB", os.path.join(HERE, "liblodestar_bls.so"))  
 AB_LIB_PATH = os.path.join(HERE, "liblodestar_bls_ab.so")
 
 LSG_OK = 0
+LSG_ERR_INVALID_ARG = 1
 LSG_ERR_NO_DEVICE = 2
 LSG_ERR_BUSY = 6
 LSG_ERR_ENTROPY = 7
@@ -39,6 +40,7 @@ LSG_ERR_BAD_INDEX = 102
 LSG_ERR_BAD_COMMITTEE = 103
 LSG_PK_INDEX = 4  # lsg_set.pk_len for keys named by pubkey-table index
 LSG_PK_BITS = 8  # lsg_set.pk_len for keys named by committee id + participation bits
+LSG_MSG_OBJECT = 0x80000000  # or'ed into lsg_set.msg_len: msg is an SSZ object + its 32-byte domain
 
 
 def error_message(code):
@@ -103,6 +105,33 @@ def _key_form(pks):
     return pk_len, len(pks), b"".join(pks)
 
 
+class MsgObject:
+    """A set's message given as the SSZ serialization of the signed object plus its 32-byte
+    domain (lsg_set.msg_len | LSG_MSG_OBJECT): the signing root computeSigningRoot(obj, domain)
+    is computed on the device as the package's first stage.  The object's length selects its
+    kind: 8 (uint64), 16 (two uint64 fields), 32 (Root), 76 (BLSToExecutionChange), 88
+    (DepositMessage), 112 (BeaconBlockHeader), 128 (AttestationData); the library answers
+    another length with LSG_ERR_INVALID_ARG.  Accepted wherever a set's message goes."""
+
+    def __init__(self, obj, domain):
+        self.obj = bytes(obj)
+        self.domain = bytes(domain)
+
+    def __len__(self):
+        return len(self.obj) + len(self.domain)
+
+    def tobytes(self):
+        return self.obj + self.domain
+
+
+def _msg_form(msg):
+    """(bytes, lsg_set.msg_len) of a set's message: plain bytes or a MsgObject"""
+    if isinstance(msg, MsgObject):
+        b = msg.tobytes()
+        return b, len(b) | LSG_MSG_OBJECT
+    return msg, len(msg)
+
+
 class LsgSet(ctypes.Structure):
     _fields_ = [
         ("pks", ctypes.c_void_p), ("pk_len", ctypes.c_uint32), ("n_pks", ctypes.c_uint32),
@@ -144,6 +173,7 @@ EXPORTS = [
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
+    "lsg_object_signing_roots",
 ]
 
 
@@ -201,6 +231,7 @@ def load_library(path=LIB_PATH):
         lib.lsg_signing_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
         lib.lsg_attestation_signing_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
         lib.lsg_deposit_signing_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
+        lib.lsg_object_signing_roots.argtypes = [vp, ctypes.c_char_p, u32, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
         lib.lsg_verify_deposits.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u64, ctypes.c_char_p, pi32]
         lib.lsg_aggregate_signatures.argtypes = [vp, ctypes.c_char_p, u32, ctypes.POINTER(u32), sz,
                                                  ctypes.c_char_p, pi32]
@@ -228,6 +259,7 @@ class SetBuffer:
         self.arr = (LsgSet * max(len(sets), 1))()
         for i, (pks, msg, sig) in enumerate(sets):
             pk_len, n_pks, pkb = _key_form(pks)
+            msg, msg_len = _msg_form(msg)
             for b in (pkb, msg, sig):
                 self._keep.append(b)
             s = self.arr[i]
@@ -235,7 +267,7 @@ class SetBuffer:
             s.pk_len = pk_len
             s.n_pks = n_pks
             s.msg = ctypes.cast(ctypes.c_char_p(msg), ctypes.c_void_p) if msg else None
-            s.msg_len = len(msg)
+            s.msg_len = msg_len
             s.sig = ctypes.cast(ctypes.c_char_p(sig), ctypes.c_void_p) if sig else None
             s.sig_len = len(sig)
         self.n = len(sets)
@@ -277,7 +309,9 @@ class PreparedJobs:
             return buf, offs, lens
 
         self._pk, pk_off, _ = pack(pk_parts)
-        self._msg, msg_off, msg_len = pack([m for _, m, _ in flat])
+        forms = [_msg_form(m) for _, m, _ in flat]
+        self._msg, msg_off, msg_len = pack([b for b, _ in forms])
+        msg_word = np.array([w for _, w in forms] or [0], np.uint32)
         self._sig, sig_off, sig_len = pack([s for _, _, s in flat])
         self.sets = (LsgSet * max(n, 1))()
         dt = np.dtype({"names": ["pks", "pk_len", "n_pks", "msg", "msg_len", "sig", "sig_len"],
@@ -291,7 +325,7 @@ class PreparedJobs:
             v["pk_len"][:n] = pk_len[:n]
             v["n_pks"][:n] = n_pks[:n]
             v["msg"][:n] = np.where(msg_len[:n] > 0, self._msg.ctypes.data + msg_off[:n], 0)
-            v["msg_len"][:n] = msg_len[:n]
+            v["msg_len"][:n] = msg_word[:n]
             v["sig"][:n] = np.where(sig_len[:n] > 0, self._sig.ctypes.data + sig_off[:n], 0)
             v["sig_len"][:n] = sig_len[:n]
         self.n_jobs = len(jobs)
@@ -577,6 +611,27 @@ class Context:
     def deposit_signing_roots(self, msgs88, domains):
         """computeSigningRoot(DepositMessage) from SSZ-serialized DepositMessage (88 B each)."""
         return self._signing_roots("lsg_deposit_signing_roots", msgs88, 88, domains)
+
+    def object_signing_roots(self, objs, domains):
+        """computeSigningRoot of SSZ-serialized objects of one kind, selected by their common
+        length as for MsgObject (8, 16, 32, 76, 88, 112 or 128 bytes): the roots a package
+        computes for MsgObject messages.  `domains` is one 32-byte domain or a list."""
+        n = len(objs)
+        if n == 0:
+            return []
+        size = len(objs[0])
+        assert all(len(o) == size for o in objs)
+        if isinstance(domains, (bytes, bytearray)):
+            dom, stride = bytes(domains), 0
+        else:
+            assert len(domains) == n
+            dom, stride = b"".join(domains), 32
+        assert len(dom) == (32 if stride == 0 else 32 * n)
+        out = ctypes.create_string_buffer(32 * n)
+        self._check(self.lib.lsg_object_signing_roots(self.h, b"".join(objs), size, n, dom, stride, out),
+                    "lsg_object_signing_roots")
+        raw = out.raw
+        return [raw[32 * i:32 * i + 32] for i in range(n)]
 
     def verify_deposits(self, data184s, domain, seed=0):
         """processDeposit.ts:47-66 for SSZ-serialized DepositData (184 B each) under one deposit

@@ -7,60 +7,8 @@
 #pragma once
 #include "lsg_curve.hpp"
 
-// ------------------------------------------------------------------ SHA-256
-LSG_CONST uint32_t SHA_K[64] = {
-    0x428a2f98u, 0x71374491u, 0xb5c0fbcfu, 0xe9b5dba5u, 0x3956c25bu, 0x59f111f1u, 0x923f82a4u, 0xab1c5ed5u,
-    0xd807aa98u, 0x12835b01u, 0x243185beu, 0x550c7dc3u, 0x72be5d74u, 0x80deb1feu, 0x9bdc06a7u, 0xc19bf174u,
-    0xe49b69c1u, 0xefbe4786u, 0x0fc19dc6u, 0x240ca1ccu, 0x2de92c6fu, 0x4a7484aau, 0x5cb0a9dcu, 0x76f988dau,
-    0x983e5152u, 0xa831c66du, 0xb00327c8u, 0xbf597fc7u, 0xc6e00bf3u, 0xd5a79147u, 0x06ca6351u, 0x14292967u,
-    0x27b70a85u, 0x2e1b2138u, 0x4d2c6dfcu, 0x53380d13u, 0x650a7354u, 0x766a0abbu, 0x81c2c92eu, 0x92722c85u,
-    0xa2bfe8a1u, 0xa81a664bu, 0xc24b8b70u, 0xc76c51a3u, 0xd192e819u, 0xd6990624u, 0xf40e3585u, 0x106aa070u,
-    0x19a4c116u, 0x1e376c08u, 0x2748774cu, 0x34b0bcb5u, 0x391c0cb3u, 0x4ed8aa4au, 0x5b9cca4fu, 0x682e6ff3u,
-    0x748f82eeu, 0x78a5636fu, 0x84c87814u, 0x8cc70208u, 0x90befffau, 0xa4506cebu, 0xbef9a3f7u, 0xc67178f2u};
-
-LSG_INL uint32_t rotr32(uint32_t x, int n) { return (x >> n) | (x << (32 - n)); }
-
-LSG_BIGFN void sha256_compress(uint32_t* st, const uint32_t* blk) {
-  uint32_t w[16];
-#pragma unroll
-  for (int i = 0; i < 16; i++) w[i] = blk[i];
-  uint32_t a = st[0], b = st[1], c = st[2], d = st[3], e = st[4], f = st[5], g = st[6], h = st[7];
-#pragma unroll
-  for (int i = 0; i < 64; i++) {
-    uint32_t wi;
-    if (i < 16) {
-      wi = w[i];
-    } else {
-      uint32_t w15 = w[(i + 1) & 15], w2 = w[(i + 14) & 15];
-      uint32_t s0 = rotr32(w15, 7) ^ rotr32(w15, 18) ^ (w15 >> 3);
-      uint32_t s1 = rotr32(w2, 17) ^ rotr32(w2, 19) ^ (w2 >> 10);
-      wi = w[i & 15] + s0 + w[(i + 9) & 15] + s1;
-      w[i & 15] = wi;
-    }
-    uint32_t S1 = rotr32(e, 6) ^ rotr32(e, 11) ^ rotr32(e, 25);
-    uint32_t ch = (e & f) ^ (~e & g);
-    uint32_t t1 = h + S1 + ch + SHA_K[i] + wi;
-    uint32_t S0 = rotr32(a, 2) ^ rotr32(a, 13) ^ rotr32(a, 22);
-    uint32_t mj = (a & b) ^ (a & c) ^ (b & c);
-    uint32_t t2 = S0 + mj;
-    h = g;
-    g = f;
-    f = e;
-    e = d + t1;
-    d = c;
-    c = b;
-    b = a;
-    a = t1 + t2;
-  }
-  st[0] += a;
-  st[1] += b;
-  st[2] += c;
-  st[3] += d;
-  st[4] += e;
-  st[5] += f;
-  st[6] += g;
-  st[7] += h;
-}
+// SHA-256 (SHA_K, sha256_compress, be_words_to_bytes) and the SSZ signing roots built on it
+#include "lsg_ssz.hpp"
 
 // Streaming SHA-256 over bytes (messages here are < 2^32 bits).
 struct sha256_ctx {
@@ -108,15 +56,6 @@ LSG_INL void sha256_final(sha256_ctx& c, uint32_t* out8) {
   c.blk[15] = bits;
   sha256_compress(c.st, c.blk);
   for (int i = 0; i < 8; i++) out8[i] = c.st[i];
-}
-
-LSG_INL void be_words_to_bytes(uint8_t* out, const uint32_t* w, int nw) {
-  for (int i = 0; i < nw; i++) {
-    out[4 * i] = (uint8_t)(w[i] >> 24);
-    out[4 * i + 1] = (uint8_t)(w[i] >> 16);
-    out[4 * i + 2] = (uint8_t)(w[i] >> 8);
-    out[4 * i + 3] = (uint8_t)w[i];
-  }
 }
 
 // expand_message_xmd(msg, DST, 256) -> 256 bytes   (RFC 9380 section 5.3.1)

@@ -199,6 +199,7 @@ struct Slot {
   // msg_dedup when some sets share one (a committee's attestations sign one AttestationData)
   size_t n_msgs = 0;
   bool msg_dedup = false;
+  bool msg_objs = false;  // a staged message is an SSZ object + domain (LSG_MSG_OBJECT)
   std::vector<uint32_t> mtab, mfirst;
   std::vector<uint64_t> mkey;
   std::vector<uint32_t> msg_id;  // host copy of the set -> message map (msg_dedup)
@@ -898,9 +899,11 @@ int launch_hash(Slot* s, int n, uint32_t* H, uint8_t* hinf) {
 
 // ---- staging: the package's sets into the slot's pinned arena (order given by `order`),
 // randomizers drawn here (seed == 0: OS CSPRNG; else deterministic, for tests)
-// 64-bit mix of a message (its length and 8-byte words; signing roots are SHA-256 outputs)
-static uint64_t msg_key(const uint8_t* m, uint32_t len) {
-  uint64_t h = 0x9e3779b97f4a7c15ull ^ len;
+// 64-bit mix of a message (its length and 8-byte words; signing roots are SHA-256 outputs).
+// msg_len as the set carries it: an LSG_MSG_OBJECT marker goes into the mix, not the byte count
+static uint64_t msg_key(const uint8_t* m, uint32_t msg_len) {
+  uint64_t h = 0x9e3779b97f4a7c15ull ^ msg_len;
+  const uint32_t len = msg_bytes(msg_len);
   uint32_t k = 0;
   for (; k + 8 <= len; k += 8) {
     uint64_t w;
@@ -921,11 +924,13 @@ static uint64_t msg_key(const uint8_t* m, uint32_t len) {
 int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, bool scale,
                const std::vector<uint8_t>* noscale = nullptr, bool dedup = false, bool bits_ok = false) {
   size_t npk = 0, msg_total = 0, n_bits_sets = 0, bit_words = 0;
+  bool any_obj = false;   // a message is an SSZ object + domain (LSG_MSG_OBJECT): k_msg_roots runs
   bool all_index = true;  // every key names a table row: 4-byte key slots (a block body's
                           // ~3.7M signers cross PCIe as 15 MB instead of 355 MB)
   auto is_bits = [&](const lsg_set* q) { return bits_ok && q->pk_len == LSG_PK_BITS; };
   for (size_t i = 0; i < n; i++) {
-    msg_total += sets[i]->msg_len;
+    msg_total += msg_bytes(sets[i]->msg_len);
+    any_obj = any_obj || msg_marked(sets[i]->msg_len);
     if (is_bits(sets[i])) {
       n_bits_sets++;
       bit_words += bits_words(sets[i]->n_pks);
@@ -1025,7 +1030,7 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
         }
         if (s->mkey[h] != key) continue;
         const lsg_set* r = sets[s->mfirst[e]];
-        if (r->msg_len == q->msg_len && (q->msg_len == 0 || memcmp(r->msg, q->msg, q->msg_len) == 0)) {
+        if (r->msg_len == q->msg_len && (q->msg_len == 0 || memcmp(r->msg, q->msg, msg_bytes(q->msg_len)) == 0)) {
           id = e;
           break;
         }
@@ -1034,9 +1039,10 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
     mid[i] = id;
     if (id == nm) {  // a new message: staged once
       msgoff[nm] = (uint32_t)mo;
-      msglen[nm] = q->msg_len;
-      if (q->msg_len) memcpy(A + o_msg + mo, q->msg, q->msg_len);
-      mo += q->msg_len;
+      msglen[nm] = q->msg_len;  // (with its marker: k_msg_roots turns the payload into a 32-byte message)
+      const uint32_t mb = msg_bytes(q->msg_len);
+      if (mb) memcpy(A + o_msg + mo, q->msg, mb);
+      mo += mb;
       nm++;
     }
     if (is_bits(q)) {
@@ -1079,6 +1085,7 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   }
   s->single_keys = single && n > 0;
   s->n_msgs = nm;
+  s->msg_objs = any_obj;
   s->msg_dedup = nm < n;
   if (s->msg_dedup) s->msg_id.assign(mid, mid + n);
   if (scale && n) {
@@ -1293,6 +1300,9 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
   s->cur = 0;
   // hash_to_G2 once per distinct message, then each set's point gathered from its message's
   const int nm = (int)s->n_msgs;
+  if (s->msg_objs)  // LSG_MSG_OBJECT messages: object + domain -> the 32-byte signing root, in place
+    KL(s, "k_msg_roots", lsgk::msg_roots(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
+                                         P_<uint32_t>(s->d_msglen)));
   KL(s, "k_expand_msg", lsgk::expand_msg(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
                                          P_<uint32_t>(s->d_msglen), P_<uint8_t>(s->d_dst), DST_POP_LEN,
                                          P_<uint8_t>(s->d_ub)));
@@ -2185,7 +2195,7 @@ PendingPkg copy_pkg(const lsg_job* jobs, size_t n_jobs, uint64_t seed) {
     for (uint32_t q = 0; q < jobs[j].n_sets; q++) {
       const lsg_set& t = jobs[j].sets[q];
       ns++;
-      nb += set_key_bytes(t) + (t.msg ? t.msg_len : 0) +
+      nb += set_key_bytes(t) + (t.msg ? msg_bytes(t.msg_len) : 0) +
             (t.sig ? t.sig_len : 0);
     }
   pk.n_sets = ns;
@@ -2205,7 +2215,7 @@ PendingPkg copy_pkg(const lsg_job* jobs, size_t n_jobs, uint64_t seed) {
     for (uint32_t q = 0; q < jobs[j].n_sets; q++, si++) {
       lsg_set t = jobs[j].sets[q];
       t.pks = put(t.pks, set_key_bytes(t));
-      t.msg = put(t.msg, t.msg ? t.msg_len : 0);
+      t.msg = put(t.msg, t.msg ? msg_bytes(t.msg_len) : 0);
       t.sig = put(t.sig, t.sig ? t.sig_len : 0);
       pk.sets[si] = t;
     }
@@ -2745,6 +2755,9 @@ int lsg_submit_jobs(lsg_ctx* c, const lsg_job* jobs, size_t n_jobs, uint64_t see
   if (!c || !ticket || (n_jobs && !jobs)) return LSG_ERR_INVALID_ARG;
   for (size_t j = 0; j < n_jobs; j++)
     if (jobs[j].n_sets && !jobs[j].sets) return LSG_ERR_INVALID_ARG;
+  // an LSG_MSG_OBJECT set that selects no kind or has no bytes is a caller bug, refused before a
+  // slot is taken (lsg_verify_jobs and lsg_verify_sets come through here)
+  if (!msg_jobs_ok(jobs, n_jobs)) return LSG_ERR_INVALID_ARG;
   CtxLock lk(c->mu);
   LSG_HIPC(c, hipSetDevice(c->dev[0]->device));
   bool prio = false;
@@ -2937,6 +2950,7 @@ int lsg_batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_t s
     c->err = "lsg_batch_partial: single-device contexts only";
     return LSG_ERR_INVALID_ARG;
   }
+  if (!msg_sets_ok(sets, n_sets)) return LSG_ERR_INVALID_ARG;
   lsg_ticket t;
   {
     CtxLock lk(c->mu);
@@ -3341,7 +3355,8 @@ int lsg_pubkey_validate(lsg_ctx* c, const uint8_t* pks, uint32_t pk_len, size_t 
 
 int lsg_hash_to_g2(lsg_ctx* c, const uint8_t* msgs, uint32_t msg_len, size_t n, const uint8_t* dst,
                    uint32_t dst_len, uint8_t* out192) {
-  if (!c || !out192 || (n && msg_len && !msgs) || dst_len > 255 || (dst_len && !dst)) return LSG_ERR_INVALID_ARG;
+  if (!c || !out192 || (n && msg_len && !msgs) || dst_len > 255 || (dst_len && !dst) || msg_marked(msg_len))
+    return LSG_ERR_INVALID_ARG;  // (these are plain messages: LSG_MSG_OBJECT is a set form)
   LSG_ENTER(c);
   Dev* d = c->dev[0];
   Slot* s = &d->util;
@@ -3451,10 +3466,12 @@ int lsg_aggregate_signatures(lsg_ctx* c, const uint8_t* sigs, uint32_t sig_len, 
 }
 
 // SSZ signing roots; kind 0: object roots given, 1: AttestationData bytes,
-// 2: DepositMessage bytes
+// 2: DepositMessage bytes, 3: any kind of LSG_MSG_OBJECT by its serialized length obj_len
+// (the dispatcher of lsg_ssz.hpp that k_msg_roots runs)
 static int signing_roots(lsg_ctx* c, int kind, const uint8_t* objs, size_t n, const uint8_t* domain, uint32_t dstride,
-                         uint8_t* out32) {
-  const size_t ob = kind == 2 ? 88 : (kind ? 128 : 32);
+                         uint8_t* out32, uint32_t obj_len = 0) {
+  const size_t ob = kind == 3 ? obj_len : (kind == 2 ? 88 : (kind ? 128 : 32));
+  if (kind == 3 && msg_object_kind(LSG_MSG_OBJECT | (obj_len + 32)) != obj_len) return LSG_ERR_INVALID_ARG;
   if (!c || !domain || (dstride != 0 && dstride != 32) || (n && (!objs || !out32)) || n > 0x7fffffffull)
     return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);
@@ -3470,7 +3487,10 @@ static int signing_roots(lsg_ctx* c, int kind, const uint8_t* objs, size_t n, co
   LSG_HIP(s, hipMemcpyAsync(d_obj, objs, ob * n, hipMemcpyHostToDevice, s->st[0]));
   LSG_HIP(s, hipMemcpyAsync(d_dom, domain, 32 * nd, hipMemcpyHostToDevice, s->st[0]));
   const int nn = (int)n;
-  if (kind == 2)
+  if (kind == 3)
+    KL(s, "k_object_signing_root",
+       lsgk::object_signing_root(S_(s), nn, d_obj, obj_len, d_dom, dstride, P_<uint8_t>(s->d_Fb)));
+  else if (kind == 2)
     KL(s, "k_deposit_signing_root",
        lsgk::deposit_signing_root(S_(s), nn, d_obj, 88, d_dom, dstride, P_<uint8_t>(s->d_Fb)));
   else if (kind)
@@ -3497,6 +3517,11 @@ int lsg_attestation_signing_roots(lsg_ctx* c, const uint8_t* data128, size_t n, 
 int lsg_deposit_signing_roots(lsg_ctx* c, const uint8_t* msgs88, size_t n, const uint8_t* domain32,
                               uint32_t domain_stride, uint8_t* out32) {
   return signing_roots(c, 2, msgs88, n, domain32, domain_stride, out32);
+}
+
+int lsg_object_signing_roots(lsg_ctx* c, const uint8_t* objs, uint32_t obj_len, size_t n, const uint8_t* domain32,
+                             uint32_t domain_stride, uint8_t* out32) {
+  return signing_roots(c, 3, objs, n, domain32, domain_stride, out32, obj_len);
 }
 
 // processDeposit.ts:47-66 for n deposits: signing roots on the device, then one single-set
@@ -3600,7 +3625,7 @@ int lsg_verify_deposits(lsg_ctx* c, const uint8_t* data184, size_t n, const uint
 }
 
 int lsg_sign(lsg_ctx* c, const uint8_t* sks32, const uint8_t* msgs, uint32_t msg_len, size_t n, uint8_t* out96) {
-  if (!c || !out96 || (n && (!sks32 || !msgs))) return LSG_ERR_INVALID_ARG;
+  if (!c || !out96 || (n && (!sks32 || !msgs)) || msg_marked(msg_len)) return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);
   Slot* s = &c->dev[0]->util;
   timer_reset(s);

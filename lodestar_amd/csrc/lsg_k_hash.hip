@@ -219,106 +219,63 @@ __global__ void LSG_KERNEL_ATTR k_h2c_affine(int n, const uint32_t* __restrict__
   lane_store(H, item, a);
 }
 
-// ---- SSZ signing roots, one thread per object.  Chunks are 8 big-endian
-// SHA-256 words; every node is SHA-256 of exactly 64 bytes, so its second block is the
-// constant padding block of a 512-bit message.
-LSG_INL void ssz_hash2(const uint32_t* a, const uint32_t* b, uint32_t* out) {
-  uint32_t st[8] = {0x6a09e667u, 0xbb67ae85u, 0x3c6ef372u, 0xa54ff53au,
-                    0x510e527fu, 0x9b05688cu, 0x1f83d9abu, 0x5be0cd19u};
-  uint32_t blk[16];
-  for (int k = 0; k < 8; k++) {
-    blk[k] = a[k];
-    blk[8 + k] = b[k];
-  }
-  sha256_compress(st, blk);
-  for (int k = 0; k < 16; k++) blk[k] = 0;
-  blk[0] = 0x80000000u;
-  blk[15] = 512;
-  sha256_compress(st, blk);
-  for (int k = 0; k < 8; k++) out[k] = st[k];
-}
-
-// `len` (<= 32) bytes at p as a zero-padded SSZ chunk
-LSG_INL void ssz_chunk(uint32_t* w, const uint8_t* p, int len) {
-  for (int k = 0; k < 8; k++) {
-    uint32_t v = 0;
-    for (int j = 0; j < 4; j++) v = (v << 8) | (4 * k + j < len ? p[4 * k + j] : 0u);
-    w[k] = v;
-  }
-}
-
-LSG_INL void ssz_store(uint8_t* out, const uint32_t* w) { be_words_to_bytes(out, w, 8); }
-
-// hash_tree_root(SigningData{objectRoot, domain}) (util/signingRoot.ts:7-13)
+// ---- SSZ signing roots, one thread per object: the trees are the
+// functions of lsg_ssz.hpp (hash_tree_root(SigningData{objectRoot, domain}),
+// util/signingRoot.ts:7-13), which tests/native/sszcheck.cpp runs on the CPU.
 __global__ void __launch_bounds__(64) k_signing_root(int n, const uint8_t* __restrict__ roots,
                                                      const uint8_t* __restrict__ domains, uint32_t dstride,
                                                      uint8_t* __restrict__ out32) {
   size_t i = gtid();
   if (i >= (size_t)n) return;
-  uint32_t r[8], d[8], o[8];
-  ssz_chunk(r, roots + 32 * i, 32);
-  ssz_chunk(d, domains + dstride * i, 32);
-  ssz_hash2(r, d, o);
-  ssz_store(out32 + 32 * i, o);
+  ssz_signing_root_chunk(roots + 32 * i, 32, domains + dstride * i, out32 + 32 * i);
 }
 
 // getAttestationDataSigningRoot (signatureSets/indexedAttestation.ts:11-19) from the SSZ
-// serialization of phase0.AttestationData (128 bytes: slot u64, index u64, beaconBlockRoot,
-// source {epoch u64, root}, target {epoch u64, root}): 5 fields -> 8 leaves, 3 levels, then
-// SigningData -- 10 node hashes per object
+// serialization of phase0.AttestationData (128 bytes)
 __global__ void __launch_bounds__(64) k_attestation_signing_root(int n, const uint8_t* __restrict__ data,
                                                                  const uint8_t* __restrict__ domains,
                                                                  uint32_t dstride, uint8_t* __restrict__ out32) {
   size_t i = gtid();
   if (i >= (size_t)n) return;
-  const uint8_t* a = data + 128 * i;
-  uint32_t l0[8], l1[8], l2[8], l3[8], l4[8], t[8], z[8], z1[8], h01[8], h23[8], h45[8];
-  for (int k = 0; k < 8; k++) z[k] = 0;
-  ssz_chunk(l0, a, 8);        // slot
-  ssz_chunk(l1, a + 8, 8);    // index
-  ssz_chunk(l2, a + 16, 32);  // beaconBlockRoot
-  ssz_chunk(t, a + 48, 8);    // source = Checkpoint{epoch, root}
-  ssz_chunk(l3, a + 56, 32);
-  ssz_hash2(t, l3, l3);
-  ssz_chunk(t, a + 88, 8);  // target
-  ssz_chunk(l4, a + 96, 32);
-  ssz_hash2(t, l4, l4);
-  ssz_hash2(z, z, z1);  // leaves 5..7 are zero chunks
-  ssz_hash2(l0, l1, h01);
-  ssz_hash2(l2, l3, h23);
-  ssz_hash2(l4, z, h45);
-  ssz_hash2(h01, h23, h01);
-  ssz_hash2(h45, z1, h45);
-  ssz_hash2(h01, h45, t);  // AttestationData.hashTreeRoot
-  ssz_chunk(z, domains + dstride * i, 32);
-  ssz_hash2(t, z, t);
-  ssz_store(out32 + 32 * i, t);
+  ssz_signing_root_attestation(data + 128 * i, domains + dstride * i, out32 + 32 * i);
 }
 
 // computeSigningRoot(ssz.phase0.DepositMessage, msg, domain) (block/processDeposit.ts:49-54)
-// from the SSZ serialization of DepositMessage (88 bytes: pubkey 48, withdrawalCredentials 32,
-// amount u64) at data + stride i (stride 184: the head of a DepositData): the Bytes48 key is
-// two chunks under one node, 3 fields -> 4 leaves, 2 levels, then SigningData -- 5 node
-// hashes per object
+// from the SSZ serialization of DepositMessage (88 bytes) at data + stride i (stride 184: the
+// head of a DepositData)
 __global__ void __launch_bounds__(64) k_deposit_signing_root(int n, const uint8_t* __restrict__ data, uint32_t stride,
                                                              const uint8_t* __restrict__ domains, uint32_t dstride,
                                                              uint8_t* __restrict__ out32) {
   size_t i = gtid();
   if (i >= (size_t)n) return;
-  const uint8_t* a = data + (size_t)stride * i;
-  uint32_t l0[8], l1[8], t[8], z[8];
-  for (int k = 0; k < 8; k++) z[k] = 0;
-  ssz_chunk(l0, a, 32);  // pubkey
-  ssz_chunk(t, a + 32, 16);
-  ssz_hash2(l0, t, l0);
-  ssz_chunk(l1, a + 48, 32);  // withdrawalCredentials
-  ssz_hash2(l0, l1, l0);
-  ssz_chunk(t, a + 80, 8);  // amount; leaf 3 is a zero chunk
-  ssz_hash2(t, z, l1);
-  ssz_hash2(l0, l1, t);  // DepositMessage.hashTreeRoot
-  ssz_chunk(z, domains + dstride * i, 32);
-  ssz_hash2(t, z, t);
-  ssz_store(out32 + 32 * i, t);
+  ssz_signing_root_deposit(data + (size_t)stride * i, domains + dstride * i, out32 + 32 * i);
+}
+
+// any kind of lsg_object_signing_roots: n objects of obj_len bytes back to back
+__global__ void __launch_bounds__(64) k_object_signing_root(int n, const uint8_t* __restrict__ objs, uint32_t obj_len,
+                                                            const uint8_t* __restrict__ domains, uint32_t dstride,
+                                                            uint8_t* __restrict__ out32) {
+  size_t i = gtid();
+  if (i >= (size_t)n) return;
+  ssz_object_signing_root(obj_len, objs + (size_t)obj_len * i, domains + dstride * i, out32 + 32 * i);
+}
+
+// First stage of a package with LSG_MSG_OBJECT sets, one thread per distinct
+// staged message.  A message whose staged length carries the marker is an SSZ object followed
+// by its domain: its signing root goes over the first 32 bytes of its own payload (payloads
+// are disjoint and at least 40 bytes; the root is stored after the whole payload is read) and
+// its length word becomes 32, so k_expand_msg finds an ordinary 32-byte message.  Unmarked
+// messages are left alone.  The stager admits only the payload lengths of the table
+// (lsgp::msg_object_kind); another one would leave an empty message.
+__global__ void __launch_bounds__(64) k_msg_roots(int n, uint8_t* msg, const uint32_t* __restrict__ msg_off,
+                                                  uint32_t* __restrict__ msg_len) {
+  size_t i = gtid();
+  if (i >= (size_t)n) return;
+  const uint32_t l = msg_len[i];
+  if (!(l & LSG_MSG_OBJECT)) return;
+  const uint32_t obj_len = (l & ~LSG_MSG_OBJECT) - 32u;
+  uint8_t* p = msg + msg_off[i];
+  msg_len[i] = ssz_object_signing_root(obj_len, p, p + obj_len, p) ? 32u : 0u;
 }
 
 namespace lsgk {
@@ -327,6 +284,18 @@ hipError_t deposit_signing_root(hipStream_t st, int n, const uint8_t* data, uint
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_deposit_signing_root, dim3((n + 63) / 64), dim3(64), 0, st, n, data, stride, domains, dstride,
                      out32);
+  return hipGetLastError();
+}
+hipError_t object_signing_root(hipStream_t st, int n, const uint8_t* objs, uint32_t obj_len, const uint8_t* domains,
+                               uint32_t dstride, uint8_t* out32) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_object_signing_root, dim3((n + 63) / 64), dim3(64), 0, st, n, objs, obj_len, domains, dstride,
+                     out32);
+  return hipGetLastError();
+}
+hipError_t msg_roots(hipStream_t st, int n, uint8_t* msg, const uint32_t* off, uint32_t* len) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_msg_roots, dim3((n + 63) / 64), dim3(64), 0, st, n, msg, off, len);
   return hipGetLastError();
 }
 hipError_t expand_msg(hipStream_t st, int n, const uint8_t* msg, const uint32_t* off, const uint32_t* len,

@@ -27,6 +27,12 @@ hipError_t attestation_signing_root(hipStream_t st, int n, const uint8_t* data, 
 // DepositMessage signing roots: object i is the 88 bytes at data + stride * i
 hipError_t deposit_signing_root(hipStream_t st, int n, const uint8_t* data, uint32_t stride, const uint8_t* domains,
                                 uint32_t dstride, uint8_t* out32);
+// any object kind by its serialized length (lsg_ssz.hpp): n objects of obj_len bytes back to back
+hipError_t object_signing_root(hipStream_t st, int n, const uint8_t* objs, uint32_t obj_len, const uint8_t* domains,
+                               uint32_t dstride, uint8_t* out32);
+// the staged messages marked LSG_MSG_OBJECT (len[m] & marker) become their 32-byte signing roots
+// in place, len[m] = 32; the others are left alone
+hipError_t msg_roots(hipStream_t st, int n, uint8_t* msg, const uint32_t* off, uint32_t* len);
 
 // ---- signatures (lsg_k_sig.hip)                                       SURVEY 8a M2, M4
 hipError_t sig_decode(hipStream_t st, int n, const uint8_t* sig, const uint32_t* sig_len, uint32_t* sig_aff,

@@ -364,6 +364,40 @@ inline void plan_phase(std::vector<int32_t>& A, const std::vector<uint64_t>& rnd
   Ph.prod = plan_seg(A, 2, poff, plen, true, pidx, 0, sw.seg_fold_wide);
 }
 
+// ---- messages given as an SSZ object + domain (LSG_MSG_OBJECT)
+// the bytes behind lsg_set.msg: msg_len without the marker
+inline uint32_t msg_bytes(uint32_t msg_len) { return msg_len & ~LSG_MSG_OBJECT; }
+inline bool msg_marked(uint32_t msg_len) { return (msg_len & LSG_MSG_OBJECT) != 0; }
+// The object's serialized length (the kind, as ssz_object_signing_root of lsg_ssz.hpp takes it)
+// that a marked msg_len selects by its payload length, object + 32-byte domain; 0: none -- an
+// unmarked length, or a payload length outside the table.
+inline uint32_t msg_object_kind(uint32_t msg_len) {
+  if (!msg_marked(msg_len)) return 0;
+  switch (msg_bytes(msg_len)) {
+    case 40: return 8;     // uint64
+    case 48: return 16;    // two uint64 fields
+    case 64: return 32;    // Root
+    case 108: return 76;   // capella.BLSToExecutionChange
+    case 120: return 88;   // phase0.DepositMessage
+    case 144: return 112;  // phase0.BeaconBlockHeader
+    case 160: return 128;  // phase0.AttestationData
+    default: return 0;
+  }
+}
+// A marked set must select a kind and carry its bytes: anything else is a caller bug, answered
+// with LSG_ERR_INVALID_ARG before a slot is taken.  Unmarked sets pass as they are.
+inline bool msg_set_ok(const lsg_set& t) { return !msg_marked(t.msg_len) || (t.msg && msg_object_kind(t.msg_len)); }
+inline bool msg_sets_ok(const lsg_set* sets, size_t n) {
+  for (size_t i = 0; i < n; i++)
+    if (!msg_set_ok(sets[i])) return false;
+  return true;
+}
+inline bool msg_jobs_ok(const lsg_job* jobs, size_t n_jobs) {
+  for (size_t j = 0; j < n_jobs; j++)
+    if (jobs[j].n_sets && jobs[j].sets && !msg_sets_ok(jobs[j].sets, jobs[j].n_sets)) return false;
+  return true;
+}
+
 // ---- one device's share of a package
 struct JobRec {
   size_t first = 0, count = 0;  // staged set range

@@ -133,6 +133,13 @@ function pubkeyBytes(pk) {
 /** ISignatureSet -> the addon's set (utils.ts:5-17 getAggregatedPubkey, with the sum done on
  * the GPU instead of the main thread). */
 function serializeSet(set) {
+  if (set.signingObject !== undefined) {
+    checkMsgObject(set);
+    const message = new Uint8Array(set.signingObject.length + 32);
+    message.set(set.signingObject, 0);
+    message.set(set.domain, set.signingObject.length);
+    return {...serializeSet({...set, signingObject: undefined, signingRoot: message}), messageObject: true};
+  }
   // signers named by a committee loaded with loadCommittees() plus participation bits (8f(5))
   if (set.committee !== undefined) {
     checkBitsSet(set);
@@ -302,8 +309,26 @@ function loadAddon() {
   return require("../napi/lsg_napi.node");
 }
 
+/** A set may give its message as the SSZ serialization of the signed object plus its domain
+ * ({signingObject, domain} instead of signingRoot; LSG_MSG_OBJECT, SURVEY.md 8f(6)): the
+ * signing root is computed on the GPU as the package's first stage.  The object's length
+ * selects its kind: uint64, two uint64 fields, Root, BLSToExecutionChange, DepositMessage,
+ * BeaconBlockHeader, AttestationData. */
+const MSG_OBJECT = 0x80000000; // LSG_MSG_OBJECT
+const MSG_OBJECT_LENGTHS = [8, 16, 32, 76, 88, 112, 128];
+function checkMsgObject(set) {
+  const obj = set.signingObject;
+  if (!(obj instanceof Uint8Array) || !MSG_OBJECT_LENGTHS.includes(obj.length)) {
+    throw Error(`signingObject must be a Uint8Array of ${MSG_OBJECT_LENGTHS.join(", ")} bytes`);
+  }
+  if (!(set.domain instanceof Uint8Array) || set.domain.length !== 32) {
+    throw Error("domain must be a Uint8Array of 32 bytes");
+  }
+}
+
 /** Reference set shape check done at call time, as serializeSet throws there (index.ts:177). */
 function checkSet(set) {
+  if (set.signingObject !== undefined) checkMsgObject(set);
   if (set.committee !== undefined) {
     checkBitsSet(set);
     return;
@@ -449,6 +474,9 @@ const SET_DESC_WORDS = 7; // pkOff, pkLen, nPks, msgOff, msgLen, sigOff, sigLen 
  * (fresh multi-MB typed arrays per package cost GC time).  Packed jobs drop their sets.
  */
 function packJobs(ranges, nSigs, into, minSigs = 0) {
+  // 224 bytes per set: one raw key, a 32-byte root, a signature.  Sets that carry more (aggregate
+  // keys, signingObject + domain: up to 160 message bytes) grow the arena in put(); the grown
+  // buffer comes back as arenaBuf, so a verifier's later packages of that kind reuse it
   let cap = Math.max(nSigs, minSigs) * 224 + 256;
   let arena = into && into.arenaBuf.length >= cap ? into.arenaBuf : new Uint8Array(cap);
   cap = arena.length;
@@ -490,9 +518,14 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
           const d = SET_DESC_WORDS * k;
           const pk1 =
             set.committee === undefined && set.pubkeyIndices === undefined && set.type === SignatureSetType.single ? set.pubkey : null;
-          const root = set.signingRoot;
+          // the message: the signing root, or the signed object followed by its domain
+          const dom = set.signingObject === undefined ? null : set.domain;
+          if (dom !== null) checkMsgObject(set);
+          const root = dom === null ? set.signingRoot : set.signingObject;
+          const msgWord = dom === null ? root.length : MSG_OBJECT + root.length + 32;
           const sig = set.signature;
-          if (pk1 instanceof Uint8Array && pk1.length !== PK_BITS && off + pk1.length + root.length + sig.length <= cap) {
+          const msgBytes = dom === null ? root.length : root.length + 32;
+          if (pk1 instanceof Uint8Array && pk1.length !== PK_BITS && off + pk1.length + msgBytes + sig.length <= cap) {
             // the common shape (one raw key): three copies, no helper calls
             arena.set(pk1, off);
             sd[d] = off;
@@ -501,8 +534,12 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
             off += pk1.length;
             arena.set(root, off);
             sd[d + 3] = off;
-            sd[d + 4] = root.length;
+            sd[d + 4] = msgWord;
             off += root.length;
+            if (dom !== null) {
+              arena.set(dom, off);
+              off += 32;
+            }
             arena.set(sig, off);
             sd[d + 5] = off;
             sd[d + 6] = sig.length;
@@ -543,7 +580,8 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
             throw Error("Unknown signature set type");
           }
           sd[d + 3] = put(root);
-          sd[d + 4] = root.length;
+          if (dom !== null) put(dom);
+          sd[d + 4] = msgWord;
           sd[d + 5] = put(sig);
           sd[d + 6] = sig.length;
           k++;
@@ -581,7 +619,7 @@ class BlsGpuVerifier {
    * @param {{blsVerifyAllMultiThread?: boolean, device?: number, devices?: number[], seed?: number,
    *          maxSigsPerPackage?: number, eagerPackages?: number, minSigsWhenBusy?: number,
    *          maxPendingSigs?: number, bufferWaitMs?: number, reserveSets?: number,
-   *          reservePubkeys?: number}} options
+   *          reservePubkeys?: number, reserveMsgBytes?: number}} options
    * @param {{logger?: object, metrics?: object|null, addon?: object}} modules  addon is
    *        injectable (tests drive the queue logic with a mock of the addon's surface)
    *
@@ -618,7 +656,10 @@ class BlsGpuVerifier {
     if (options.reserveSets && this.addon.reserve) {
       // preallocate every pipeline slot for packages of up to reserveSets sets (lsg_reserve)
       const pks = options.reservePubkeys || options.reserveSets;
-      this.addon.reserve(this.ctx, options.reserveSets, pks, 32 * options.reserveSets, this.poolSize);
+      // message bytes: 32 per set for signing roots; signingObject sets stage object + domain
+      // (up to 160 bytes, an AttestationData): callers that send them say so (reserveMsgBytes)
+      const msgBytes = options.reserveMsgBytes || 32 * options.reserveSets;
+      this.addon.reserve(this.ctx, options.reserveSets, pks, msgBytes, this.poolSize);
     }
     this.jobs = new Fifo(); // queued pages (index.ts `jobs`)
     this.priorityPages = []; // pages of priority jobs: a stack, drained first
@@ -995,6 +1036,7 @@ class BlsGpuSingleThreadVerifier {
 
   async verifySignatureSets(sets, opts = {}) {
     if (this.metrics && this.metrics.bls) this.metrics.bls.aggregatedPubkeys.inc(getAggregatedPubkeysCount(sets));
+    for (let i = 0; i < sets.length; i++) if (sets[i].signingObject !== undefined) checkMsgObject(sets[i]);
     // Count time after aggregating (serialisation happens inside verifyDirect)
     const startNs = process.hrtime.bigint();
     const valid = await verifyDirect(this.addon, this.ctx, sets, this.seed, opts.validatePubkeys === true);

@@ -39,7 +39,12 @@
  *   committeesSet(ctx, firstId, indices: Uint32Array, offsets: Uint32Array) -> Int32Array
  *   committeesClear(ctx, firstId, n)                                   lsg_committees_set / _clear
  *       (a set descriptor may then have pk_len 8 = LSG_PK_BITS: committee id + bits, n_pks bits)
- *       (these four throw "does not support" when the loaded library lacks the entry point)
+ *   objectSigningRoots(ctx, objs: n x objLen B, objLen, domain: 32 B | n x 32 B) -> Uint8Array(n x 32)
+ *                                                                      lsg_object_signing_roots
+ *       (these five throw "does not support" when the loaded library lacks the entry point)
+ *   A set's message may be an SSZ object followed by its 32-byte domain (LSG_MSG_OBJECT): the
+ *   descriptor's msgLen word of verifyPacked carries 0x80000000 | length; a set of verifySets
+ *   carries messageObject: true beside message.
  * Failures of the library itself (not verdicts) throw an Error carrying lsg_last_error().
  */
 #include <node_api.h>
@@ -59,6 +64,9 @@ extern int lsg_pubkey_validate(lsg_ctx* ctx, const uint8_t* pks, uint32_t pk_len
 extern int lsg_committees_set(lsg_ctx* ctx, uint32_t first_id, const uint32_t* indices, const uint32_t* offsets,
                               size_t n_committees, int32_t* err) __attribute__((weak));
 extern int lsg_committees_clear(lsg_ctx* ctx, uint32_t first_id, size_t n) __attribute__((weak));
+extern int lsg_object_signing_roots(lsg_ctx* ctx, const uint8_t* objs, uint32_t obj_len, size_t n,
+                                    const uint8_t* domain32, uint32_t domain_stride, uint8_t* out32)
+    __attribute__((weak));
 
 #define LSG_NAPI_THREADS 16 /* package threads per context: one outstanding package each */
 
@@ -166,9 +174,14 @@ static int view_sets(napi_env env, napi_value arr, set_view* out) {
     const uint8_t* d;
     size_t len;
     napi_value m = get_prop(env, s, "message"), g = get_prop(env, s, "signature"), pk = get_prop(env, s, "pubkeys");
-    if (!m || get_bytes(env, m, &d, &len)) goto bad;
+    if (!m || get_bytes(env, m, &d, &len) || len >= LSG_MSG_OBJECT) goto bad;
     q->msg = d;
     q->msg_len = (uint32_t)len;
+    /* messageObject: true -- message is an SSZ object followed by its 32-byte domain (LSG_MSG_OBJECT) */
+    napi_value mo = get_prop(env, s, "messageObject");
+    bool is_obj = false;
+    if (mo && napi_coerce_to_bool(env, mo, &mo) == napi_ok) napi_get_value_bool(env, mo, &is_obj);
+    if (is_obj) q->msg_len |= LSG_MSG_OBJECT;
     if (!g || get_bytes(env, g, &d, &len)) goto bad;
     q->sig = d;
     q->sig_len = (uint32_t)len;
@@ -380,7 +393,9 @@ static int build_jobs(pkg_req* r, lsg_set** sets_out, lsg_job** jobs_out) {
     lsg_set* q = &sets[i];
     /* a committee + bits set (LSG_PK_BITS): the committee id, then ceil(n_pks / 8) bytes of bits */
     const uint64_t pk_bytes = d[1] == LSG_PK_BITS ? 4 + (((uint64_t)d[2] + 7) >> 3) : (uint64_t)d[1] * d[2];
-    if ((uint64_t)d[0] + pk_bytes > L || (uint64_t)d[3] + d[4] > L || (uint64_t)d[5] + d[6] > L) {
+    /* the length word of a message may carry LSG_MSG_OBJECT: its bytes are the masked length */
+    const uint64_t msg_bytes = d[4] & ~LSG_MSG_OBJECT;
+    if ((uint64_t)d[0] + pk_bytes > L || (uint64_t)d[3] + msg_bytes > L || (uint64_t)d[5] + d[6] > L) {
       free(sets);
       free(jobs);
       return LSG_ERR_INVALID_ARG;
@@ -907,6 +922,39 @@ static napi_value js_attestation_signing_roots(napi_env env, napi_callback_info 
   return out;
 }
 
+/* objectSigningRoots(ctx, objs: Uint8Array (n x objLen B), objLen, domain: Uint8Array (32 B shared,
+ * or n x 32 B)) -> Uint8Array(n x 32): computeSigningRoot for n objects of the kind objLen selects
+ * (8, 16, 32, 76, 88, 112, 128; 8f(6), lsg_object_signing_roots) */
+static napi_value js_object_signing_roots(napi_env env, napi_callback_info info) {
+  size_t argc = 4;
+  napi_value argv[4];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  lsg_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  const uint8_t *d, *dom;
+  size_t dl, doml;
+  uint32_t ol = 0;
+  if (argc < 4 || get_bytes(env, argv[1], &d, &dl) || napi_get_value_uint32(env, argv[2], &ol) != napi_ok || ol == 0 ||
+      get_bytes(env, argv[3], &dom, &doml) || dl % ol || (doml != 32 && doml != 32 * (dl / ol))) {
+    napi_throw_type_error(env, NULL, "lsg_napi: objectSigningRoots(ctx, objs: n x objLen B, objLen, domain: 32 B | n x 32 B)");
+    return NULL;
+  }
+  if (!lsg_object_signing_roots) {
+    napi_throw_error(env, NULL,
+                     "lsg_napi: the loaded library does not support objectSigningRoots (no lsg_object_signing_roots)");
+    return NULL;
+  }
+  const size_t n = dl / ol;
+  void* outp;
+  napi_value ab, out;
+  NAPI_CALL(env, napi_create_arraybuffer(env, 32 * n, &outp, &ab));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, 32 * n, ab, 0, &out));
+  uint32_t stride = doml == 32 ? 0 : 32;
+  int rc = n ? lsg_object_signing_roots(ctx, d, ol, n, dom, stride, (uint8_t*)outp) : LSG_OK;
+  if (rc) return throw_lsg(env, ctx, "lsg_object_signing_roots", rc);
+  return out;
+}
+
 /* verifyDeposits(ctx, data: Uint8Array (n x 184 B SSZ DepositData), domain: Uint8Array(32)) ->
  * {valid: Uint8Array(n), err: Int32Array(n)}: processDeposit.ts:47-66 for n deposits
  * (lsg_verify_deposits; randomizers from the OS).  Synchronous: the calling thread is blocked for
@@ -1098,6 +1146,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"pubkeyTableSet", NULL, js_pubkey_table_set, NULL, NULL, NULL, napi_enumerable, NULL},
       {"aggregateSignatures", NULL, js_aggregate_signatures, NULL, NULL, NULL, napi_enumerable, NULL},
       {"attestationSigningRoots", NULL, js_attestation_signing_roots, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"objectSigningRoots", NULL, js_object_signing_roots, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyDeposits", NULL, js_verify_deposits, NULL, NULL, NULL, napi_enumerable, NULL},
       {"pubkeyValidate", NULL, js_pubkey_validate, NULL, NULL, NULL, napi_enumerable, NULL},
       {"committeesSet", NULL, js_committees_set, NULL, NULL, NULL, napi_enumerable, NULL},
