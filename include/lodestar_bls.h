@@ -442,6 +442,12 @@ int lsg_sk_to_pk(lsg_ctx* ctx, const uint8_t* sks32, size_t n, uint8_t* out96);
  * c0 + c1 u = (a0 + a1 u)(b0 + b1 u) / 2^406 mod p, raw (lazy, not canonical), same layout, 2
  * elements per item.  Not on the verification path. */
 int lsg_check_fp2_mul(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+/* Parity hooks of the device squaring leaves (tests only), same layout and raw outputs:
+ * lsg_check_fp_sqr takes one element a per item (14 words) and writes a^2 / 2^406 mod p (14
+ * words); lsg_check_fp2_sqr takes (a0, a1) (28 words) and writes c0, c1 with
+ * c0 + c1 u = (a0 + a1 u)^2 / 2^406 mod p (28 words).  Not on the verification path. */
+int lsg_check_fp_sqr(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+int lsg_check_fp2_sqr(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
 /* Integer-VALU roofline probe: runs a throughput kernel of dependent-free 381-bit
  * Montgomery multiplications; reports Fp-mul/s and v_mad_u64_u32/s (x300 per mul). */
 int lsg_probe_fp_mul_rate(lsg_ctx* ctx, double* fp_mul_per_s, double* mad_per_s);

@@ -171,6 +171,7 @@ EXPORTS = [
     "lsg_final_submit_groups", "lsg_final_wait_groups", "lsg_aggregate_signatures",
     "lsg_signing_roots", "lsg_attestation_signing_roots", "lsg_jobs_partial_device", "lsg_final_submit_device",
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
+    "lsg_check_fp_sqr", "lsg_check_fp2_sqr",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
     "lsg_object_signing_roots",
@@ -240,6 +241,8 @@ def load_library(path=LIB_PATH):
         lib.lsg_pipeline_slots.argtypes = [vp, pi32]
         lib.lsg_set_coalesce.argtypes = [vp, u32, i32]
         lib.lsg_check_fp2_mul.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_fp_sqr.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_fp2_sqr.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_probe_mad_peak.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         for name in EXPORTS:
             if name != "lsg_last_error":
@@ -747,6 +750,23 @@ class Context:
         src = struct.pack(f"<{len(words)}I", *words)
         self._check(self.lib.lsg_check_fp2_mul(self.h, src, n, out), "lsg_check_fp2_mul")
         return list(struct.unpack(f"<{28 * n}I", out.raw))
+
+    def _check_sqr(self, fn, words, per_item):
+        n = len(words) // per_item
+        assert len(words) == per_item * n
+        out = ctypes.create_string_buffer(4 * per_item * n)
+        src = struct.pack(f"<{len(words)}I", *words)
+        self._check(getattr(self.lib, fn)(self.h, src, n, out), fn)
+        return list(struct.unpack(f"<{per_item * n}I", out.raw))
+
+    def check_fp_sqr(self, words):
+        """lsg_check_fp_sqr: `words` = 14 u32 per item (a in the pair layout, lodestar_bls.h);
+        returns 14 u32 per item (a^2 / 2^406, raw)."""
+        return self._check_sqr("lsg_check_fp_sqr", words, 14)
+
+    def check_fp2_sqr(self, words):
+        """lsg_check_fp2_sqr: `words` = 28 u32 per item (a0, a1); returns 28 u32 per item (c0, c1, raw)."""
+        return self._check_sqr("lsg_check_fp2_sqr", words, 28)
 
     def probe_fp_mul_rate(self):
         a, b = ctypes.c_double(), ctypes.c_double()

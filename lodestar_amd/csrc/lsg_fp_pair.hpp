@@ -252,6 +252,100 @@ LSG_PFN void pair_mont_mul_n(fp_t* r, const fp_t* a, const fp_t* b) {
       t[n][0] += c;
       t[n][LSG_PL - 1] = (int64_t)mv;
     }
+#if LSG_PAIR_G == 1
+    // one lane holds every column for 14 steps; with the uncarried operands of the Fp2
+    // squaring (limbs up to 2^30 + 16) that is 14 (2^59.1 + 2^58) > 2^63: carry once
+    if (i == 6) {
+#pragma unroll
+      for (int n = 0; n < N; n++)
+#pragma unroll
+        for (int j = 0; j < LSG_PL - 1; j++) {
+          t[n][j + 1] += t[n][j] >> 29;
+          t[n][j] &= (int64_t)LSG_M29;
+        }
+    }
+#endif
+  }
+#pragma unroll
+  for (int n = 0; n < N; n++) pair_redc_tail(t[n], r[n], top);
+}
+// ---- Montgomery square: the same CIOS pass with every cross product a_i a_j computed once
+// At step s position k of lane h holds column s + k + 7h, and one mad t[i] += A[i] * bcast(a_s)
+// adds a_i a_s on lane 0 and a_{i+7} a_s on lane 1.  With s' = s mod 7 only i <= s' is issued
+// (56 mads per lane instead of 98): i = s' takes the plain broadcast, i < s' the doubled one.
+//   s < 7:  lane 0 low-low pairs {i, s} (the square at i = s), lane 1 mixed pairs {s, i+7}
+//   s >= 7: lane 0 mixed pairs {i, s'+7}, lane 1 high-high pairs {i+7, s}
+// so low-low and high-high pairs come once, doubled, with the plain squares on the diagonal; a
+// mixed pair {u, w+7} comes doubled on lane 1 at step u (w < u) or on lane 0 at step w + 7
+// (w > u), and with factor 1 on each lane when w = u.  Every term of column c is added at a step
+// <= c in the lane that holds c at that step (lane 1's share reaches lane 0 through the
+// hand-down of its low 29 bits), so t[0] is complete when step c reduces it: the accumulated
+// integer is a a + sum m_s p 2^(29 s) with the m sequence of pair_mont_mul_n(a, a), and after
+// pair_redc_tail the limbs are bit for bit those of the product.
+// Bound: a column takes at most one product term and one reduction term per step for 7 steps
+// per lane; for limbs in [-8, 2^29 + 8) and the doubled operand below 2^30 + 16 that is
+// |t| < 7 (2^59.1 + 2^58) < 2^62.3 plus the carries of < 2^34 that stay behind.  The one-lane
+// host build holds a column for 14 steps and carries once at mid-loop, as pair_sop2_n does.
+#ifndef LSG_SQR_STEP_FENCE  // A/B builds: 0 = the steps of a squaring scheduled freely
+#define LSG_SQR_STEP_FENCE 1
+#endif
+template <int N>
+LSG_PFN void pair_mont_sqr_n(fp_t* r, const fp_t* a) {
+  const bool top = pair_top();
+  uint32_t p[LSG_PL];
+#pragma unroll
+  for (int j = 0; j < LSG_PL; j++) p[j] = pair_pick(LSG_P, j);
+  int64_t t[N][LSG_PL];
+#pragma unroll
+  for (int n = 0; n < N; n++)
+#pragma unroll
+    for (int j = 0; j < LSG_PL; j++) t[n][j] = 0;
+  uint32_t m29 = LSG_M29, lmask = top ? 0u : LSG_M29;
+#if LSG_PAIR_G == 2
+  asm volatile("" : "+v"(m29), "+v"(lmask));  // register operands: the DPP moves fold into the ands
+#endif
+#pragma unroll
+  for (int i = 0; i < 14; i++) {
+#pragma unroll
+    for (int n = 0; n < N; n++) {
+      const uint32_t bs = a[n].l[i % LSG_PL];
+      const int32_t bi = (int32_t)(i / LSG_PL == 0 ? pbcast<0>(bs) : pbcast<LSG_GROUP - 1>(bs));
+      const int32_t bi2 = (int32_t)((uint32_t)bi + (uint32_t)bi);
+#pragma unroll
+      for (int j = 0; j < i % LSG_PL; j++) t[n][j] += (int64_t)(int32_t)a[n].l[j] * bi2;
+      t[n][i % LSG_PL] += (int64_t)(int32_t)a[n].l[i % LSG_PL] * bi;
+    }
+#pragma unroll
+    for (int n = 0; n < N; n++) {
+      const uint32_t m = pbcast0_and((uint32_t)t[n][0] * LSG_N0P, m29);
+#pragma unroll
+      for (int j = 0; j < LSG_PL; j++) t[n][j] += (int64_t)(int32_t)m * (int32_t)p[j];
+    }
+#pragma unroll
+    for (int n = 0; n < N; n++) {
+      const int64_t c = t[n][0] >> 29;
+      const uint32_t mv = pdown_and((uint32_t)t[n][0], lmask);
+#pragma unroll
+      for (int j = 0; j < LSG_PL - 1; j++) t[n][j] = t[n][j + 1];
+      t[n][0] += c;
+      t[n][LSG_PL - 1] = (int64_t)mv;
+    }
+#if LSG_PAIR_G == 2 && LSG_SQR_STEP_FENCE
+    // no step's work moved into another: without it pair_pow_plan and the kernels around it
+    // need two VGPRs more than with the product (195 against 193), with it 180
+    __builtin_amdgcn_sched_barrier(0);
+#endif
+#if LSG_PAIR_G == 1
+    if (i == 6) {  // one lane holds every column for 14 steps: carry once (value-preserving)
+#pragma unroll
+      for (int n = 0; n < N; n++)
+#pragma unroll
+        for (int j = 0; j < LSG_PL - 1; j++) {
+          t[n][j + 1] += t[n][j] >> 29;
+          t[n][j] &= (int64_t)LSG_M29;
+        }
+    }
+#endif
   }
 #pragma unroll
   for (int n = 0; n < N; n++) pair_redc_tail(t[n], r[n], top);
@@ -361,6 +455,15 @@ LSG_PLEAF fp_t pair_mont_mul(fp_t a, fp_t b) {
   LSG_COUNT_MUL();
   fp_t r;
   pair_mont_mul_n<1>(&r, &a, &b);
+  return r;
+}
+#ifndef LSG_NO_SQR_LEAF  // (A/B builds: -DLSG_NO_SQR_LEAF squares with the product leaf)
+#define LSG_SQR_LEAF 1   // fp_sqr and the power leaves call the squaring pass
+#endif
+LSG_PLEAF fp_t pair_mont_sqr(fp_t a) {
+  LSG_COUNT_MUL();
+  fp_t r;
+  pair_mont_sqr_n<1>(&r, &a);
   return r;
 }
 // Multi-product leaves.  Operands cross the call as 8-word vectors: the gfx950 call ABI
@@ -548,17 +651,30 @@ LSG_PLEAF fp_duo pair_fp2_sqr_v(fp_arg_t va0, fp_arg_t va1) {
   LSG_COUNT_MUL();
   LSG_COUNT_MUL();
   const fp_t a0 = fp_unpack(va0), a1 = fp_unpack(va1);
+  // s = a0 + a1, d = a0 - a1 and e = a1 + a1 limb by limb, with no carry round: they go
+  // straight into a product, whose mads take signed 32-bit operands.  Limbs of s and e lie in
+  // [-16, 2^30 + 16) and those of d in (-2^29 - 16, 2^29 + 16), so a partial product is below
+  // 2^59.1 and a column sums 7 of them and 7 reduction terms below 2^58 per lane:
+  // |t| < 2^62.5 (the one-lane host build carries at mid-loop in pair_mont_mul_n).  Both
+  // outputs leave through pair_redc_tail, normalised; for inputs |a| < 2^12.6 p they satisfy
+  // |c0| < 2p (|a0^2 - a1^2| <= max(a0^2, a1^2)) and |c1| < 3p.
+  fp_t s, d, e;
+#pragma unroll
+  for (int k = 0; k < LSG_PL; k++) {
+    s.l[k] = a0.l[k] + a1.l[k];
+    d.l[k] = a0.l[k] - a1.l[k];
+    e.l[k] = a1.l[k] + a1.l[k];
+  }
   fp_t t[2];
 #if LSG_LEAF_MODE == 2
-  const fp_t a[2] = {fp_add(a0, a1), a0}, b[2] = {fp_sub(a0, a1), a1};
+  const fp_t a[2] = {s, a0}, b[2] = {d, e};
   pair_mont_mul_n<2>(t, a, b);
 #else
-  const fp_t s = fp_add(a0, a1), d = fp_sub(a0, a1);
   pair_mont_mul_n<1>(&t[0], &s, &d);
   LSG_SCHED_FENCE();
-  pair_mont_mul_n<1>(&t[1], &a0, &a1);
+  pair_mont_mul_n<1>(&t[1], &a0, &e);
 #endif
-  return fp_duo{t[0], fp_add(t[1], t[1])};
+  return fp_duo{t[0], t[1]};
 }
 
 // a^e for a fixed public exponent e (12 little-endian words) in one call: the same sliding
@@ -572,10 +688,20 @@ LSG_PLEAF fp_t pair_pow_fixed(fp_t a, const uint32_t* __restrict__ e) {
     pair_mont_mul_n<1>(&r, &x, &y);
     return r;
   };
+  auto sq = [](const fp_t& x) {  // x^2 (-DLSG_NO_SQR_LEAF: as the product x x)
+    LSG_COUNT_MUL();
+    fp_t r;
+#ifdef LSG_SQR_LEAF
+    pair_mont_sqr_n<1>(&r, &x);
+#else
+    pair_mont_mul_n<1>(&r, &x, &x);
+#endif
+    return r;
+  };
   // T[k] = a^(2k+1), written out: a table loop the compiler declines to unroll would put T
   // in scratch with indexed access
   fp_t T[8];
-  const fp_t a2 = mul(a, a);
+  const fp_t a2 = sq(a);
   T[0] = a;
   T[1] = mul(T[0], a2);
   T[2] = mul(T[1], a2);
@@ -590,7 +716,7 @@ LSG_PLEAF fp_t pair_pow_fixed(fp_t a, const uint32_t* __restrict__ e) {
   bool started = false;
   while (i >= 0) {
     if (!((e[i >> 5] >> (i & 31)) & 1u)) {
-      r = mul(r, r);
+      r = sq(r);
       i--;
       continue;
     }
@@ -599,7 +725,7 @@ LSG_PLEAF fp_t pair_pow_fixed(fp_t a, const uint32_t* __restrict__ e) {
     uint32_t v = 0;
     for (int t = i; t >= j; t--) v = (v << 1) | ((e[t >> 5] >> (t & 31)) & 1u);
     if (started)
-      for (int t = i; t >= j; t--) r = mul(r, r);
+      for (int t = i; t >= j; t--) r = sq(r);
     fp_t tv = T[0];
 #pragma unroll
     for (int k = 1; k < 8; k++) tv = fp_select(v == (uint32_t)(2 * k + 1), T[k], tv);
@@ -690,6 +816,16 @@ LSG_PLEAF fp_t pair_pow_plan(fp_t a, int id) {
     pair_mont_mul_n<1>(&r, &x, &y);
     return r;
   };
+  auto sq = [](const fp_t& x) {  // x^2 (-DLSG_NO_SQR_LEAF: as the product x x)
+    LSG_COUNT_MUL();
+    fp_t r;
+#ifdef LSG_SQR_LEAF
+    pair_mont_sqr_n<1>(&r, &x);
+#else
+    pair_mont_mul_n<1>(&r, &x, &x);
+#endif
+    return r;
+  };
   auto pick = [](const fp_t* T, uint32_t k) {
     fp_t tv = T[0];
 #pragma unroll
@@ -697,7 +833,7 @@ LSG_PLEAF fp_t pair_pow_plan(fp_t a, int id) {
     return tv;
   };
   fp_t T[8];  // T[k] = a^(2k+1), written out as in pair_pow_fixed
-  const fp_t a2 = mul(a, a);
+  const fp_t a2 = sq(a);
   T[0] = a;
   T[1] = mul(T[0], a2);
   T[2] = mul(T[1], a2);
@@ -716,8 +852,7 @@ LSG_PLEAF fp_t pair_pow_plan(fp_t a, int id) {
     return x;
   };
   auto sqr = [&](const fp_t& x) {
-    const fp_t y = hide(x);
-    return mul(y, y);
+    return sq(hide(x));
   };
   fp_t r = pick(T, P.step[0] & 0xffu);
   const int n = P.n;

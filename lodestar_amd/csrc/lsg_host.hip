@@ -3670,6 +3670,28 @@ int lsg_check_fp2_mul(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
   return LSG_OK;
 }
 
+// the squaring hooks: E elements per item in, E out (E = 1: fp_sqr, E = 2: fp2_sqr)
+static int check_sqr(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out, int E) {
+  if (!c || (n && (!in || !out)) || n > 0x7fffffffull / (4 * W_FP)) return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  if (n == 0) return LSG_OK;
+  Slot* s = &c->dev[0]->util;
+  timer_reset(s);
+  const size_t bytes = 4 * (size_t)E * W_FP * n;
+  LSG_RC(ensure(s, s->d_aux, bytes));
+  LSG_RC(ensure(s, s->d_Fb, bytes));
+  LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, in, bytes, hipMemcpyHostToDevice, s->st[0]));
+  if (E == 1)
+    KL(s, "k_check_fp_sqr", lsgk::check_fp_sqr(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  else
+    KL(s, "k_check_fp2_sqr", lsgk::check_fp2_sqr(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  LSG_HIP(s, hipMemcpyAsync(out, s->d_Fb.p, bytes, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  return LSG_OK;
+}
+int lsg_check_fp_sqr(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_sqr(c, in, n, out, 1); }
+int lsg_check_fp2_sqr(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_sqr(c, in, n, out, 2); }
+
 int lsg_probe_fp_mul_rate(lsg_ctx* c, double* fp_mul_per_s, double* mad_per_s) {
   if (!c || !fp_mul_per_s || !mad_per_s) return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);

@@ -208,6 +208,19 @@ __global__ void LSG_KERNEL_ATTR k_check_fp2_mul(int n, const uint32_t* __restric
   lane_store(out, 2 * item, c.c0);
   lane_store(out, 2 * item + 1, c.c1);
 }
+// the same hooks for the squaring leaves (fp_sqr: pair_mont_sqr, fp2_sqr: pair_fp2_sqr_v)
+__global__ void LSG_KERNEL_ATTR k_check_fp_sqr(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  (void)lead;
+  lane_store(out, item, fp_sqr(lane_load<fp_t>(in, item)));
+}
+__global__ void LSG_KERNEL_ATTR k_check_fp2_sqr(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  (void)lead;
+  const fp2_t c = fp2_sqr(fp2_t(lane_load<fp_t>(in, 2 * item), lane_load<fp_t>(in, 2 * item + 1)));
+  lane_store(out, 2 * item, c.c0);
+  lane_store(out, 2 * item + 1, c.c1);
+}
 
 // roofline probe: 4 independent limb-parallel Montgomery chains per pair
 __global__ void LSG_KERNEL_ATTR k_probe_fp_mul(int n, int iters, uint32_t* __restrict__ io) {
@@ -279,6 +292,12 @@ hipError_t fp12_pow_u64(hipStream_t st, const uint8_t* in576, uint64_t r, uint8_
 }
 hipError_t check_fp2_mul(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
   LSG_LAUNCH_ITEMS(k_check_fp2_mul, n, st, n, in, out);
+}
+hipError_t check_fp_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_fp_sqr, n, st, n, in, out);
+}
+hipError_t check_fp2_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_fp2_sqr, n, st, n, in, out);
 }
 hipError_t probe_fp_mul(hipStream_t st, int items, int iters, uint32_t* io) {
   LSG_LAUNCH_ITEMS(k_probe_fp_mul, items, st, items, iters, io);

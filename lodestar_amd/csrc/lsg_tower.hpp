@@ -17,7 +17,11 @@
 // ------------------------------------------------------------------ Fp (backend-generic)
 LSG_INL fp_t fp_one() { return fp_t(FP_ONE); }
 LSG_INL fp_t fp_dbl(const fp_t& a) { return fp_add(a, a); }
+#ifdef LSG_SQR_LEAF  // the pair backend's squaring pass: every cross product once
+LSG_INL fp_t fp_sqr(const fp_t& a) { return pair_mont_sqr(a); }
+#else
 LSG_INL fp_t fp_sqr(const fp_t& a) { return fp_mul(a, a); }
+#endif
 LSG_INL fp_t fp_to_mont(const fp_t& a) { return fp_mul(a, fp_t(FP_R2)); }
 // canonical plain integer in [0, p) (fp_canonical is the identity for the fully reduced
 // backends; the lazy pair backend reduces here)
@@ -209,8 +213,12 @@ LSG_INL void fp2_sqr_n(fp2_t* r, const fp2_t* a) {
 LSG_INL fp2_t fp2_mul_xi(const fp2_t& a) { return fp2_t(fp_sub(a.c0, a.c1), fp_add(a.c0, a.c1)); }
 
 LSG_INL fp_t fp2_norm(const fp2_t& a) {
+#ifdef LSG_SQR_LEAF
+  const fp_t s0 = fp_sqr(a.c0), s1 = fp_sqr(a.c1);
+#else
   fp_t s0, s1;
   fp_mul2(s0, s1, a.c0, a.c0, a.c1, a.c1);
+#endif
   return fp_add(s0, s1);
 }
 
