@@ -448,6 +448,13 @@ int lsg_check_fp2_mul(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out)
  * c0 + c1 u = (a0 + a1 u)^2 / 2^406 mod p (28 words).  Not on the verification path. */
 int lsg_check_fp_sqr(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
 int lsg_check_fp2_sqr(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+/* Parity hook of the lazy sums (tests only), same layout and raw outputs: 12 elements per item
+ * in (the 12 n elements form a ring; item i works on the elements from 12 i on), 42 per item
+ * out: the maximal admissible sum, the small multiples, fp2_mul_b3, jac_dbl over Fp and Fp2,
+ * the G2 addition and one combination of the fused Miller kernel, each with the form that
+ * carries at every operation beside it (lsg_k_reduce.hip k_check_sums lists the slots).  Not
+ * on the verification path. */
+int lsg_check_sums(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
 /* Integer-VALU roofline probe: runs a throughput kernel of dependent-free 381-bit
  * Montgomery multiplications; reports Fp-mul/s and v_mad_u64_u32/s (x300 per mul). */
 int lsg_probe_fp_mul_rate(lsg_ctx* ctx, double* fp_mul_per_s, double* mad_per_s);

@@ -171,7 +171,7 @@ EXPORTS = [
     "lsg_final_submit_groups", "lsg_final_wait_groups", "lsg_aggregate_signatures",
     "lsg_signing_roots", "lsg_attestation_signing_roots", "lsg_jobs_partial_device", "lsg_final_submit_device",
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
-    "lsg_check_fp_sqr", "lsg_check_fp2_sqr",
+    "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
     "lsg_object_signing_roots",
@@ -243,6 +243,7 @@ def load_library(path=LIB_PATH):
         lib.lsg_check_fp2_mul.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_fp_sqr.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_fp2_sqr.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_sums.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_probe_mad_peak.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         for name in EXPORTS:
             if name != "lsg_last_error":
@@ -767,6 +768,15 @@ class Context:
     def check_fp2_sqr(self, words):
         """lsg_check_fp2_sqr: `words` = 28 u32 per item (a0, a1); returns 28 u32 per item (c0, c1, raw)."""
         return self._check_sqr("lsg_check_fp2_sqr", words, 28)
+
+    def check_sums(self, words):
+        """lsg_check_sums: `words` = 12 x 14 u32 per item; returns 42 x 14 u32 per item (raw)."""
+        n = len(words) // (12 * 14)
+        assert len(words) == 12 * 14 * n
+        out = ctypes.create_string_buffer(4 * 42 * 14 * n)
+        src = struct.pack(f"<{len(words)}I", *words)
+        self._check(self.lib.lsg_check_sums(self.h, src, n, out), "lsg_check_sums")
+        return list(struct.unpack(f"<{42 * 14 * n}I", out.raw))
 
     def probe_fp_mul_rate(self):
         a, b = ctypes.c_double(), ctypes.c_double()

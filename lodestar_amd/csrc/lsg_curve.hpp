@@ -17,6 +17,16 @@ LSG_INL fp_t fsqr(const fp_t& a) { return fp_sqr(a); }
 LSG_INL fp2_t fsqr(const fp2_t& a) { return fp2_sqr(a); }
 LSG_INL fp_t fneg(const fp_t& a) { return fp_neg(a); }
 LSG_INL fp2_t fneg(const fp2_t& a) { return fp2_neg(a); }
+// lazy sums (lsg_tower.hpp): lift, uncarried and carried small multiples, a - b - c
+LSG_INL fps_t<1, 0> fsum(const fp_t& a) { return fps(a); }
+LSG_INL fp2s_t<1, 0> fsum(const fp2_t& a) { return fp2s(a); }
+template <int K, int P, int N>
+LSG_INL fps_t<K * P, K * N> fsum_mulk(const fps_t<P, N>& a) { return fps_mulk<K>(a); }
+template <int K, int P0, int N0, int P1, int N1>
+LSG_INL fp2s_t<K * P0, K * N0, K * P1, K * N1> fsum_mulk(const fp2s_t<P0, N0, P1, N1>& a) { return fp2s_mulk<K>(a); }
+template <int K> LSG_INL fp_t fmulk(const fp_t& a) { return fp_mulk<K>(a); }
+template <int K> LSG_INL fp2_t fmulk(const fp2_t& a) { return fp2_mulk<K>(a); }
+template <class F> LSG_INL F fsub2(const F& a, const F& b, const F& c) { return (fsum(a) - b - c).carry(); }
 LSG_INL fp_t fmul_b3(const fp_t& a) { return fp_mul12(a); }
 LSG_INL fp2_t fmul_b3(const fp2_t& a) { return fp2_mul_b3(a); }
 LSG_INL bool fis_zero(const fp_t& a) { return fp_is_zero(a); }
@@ -83,17 +93,12 @@ LSG_INL proj_t<F> proj_add(const proj_t<F>& p, const proj_t<F>& q) {
   F t0 = fmul(p.X, q.X);
   F t1 = fmul(p.Y, q.Y);
   F t2 = fmul(p.Z, q.Z);
-  F t3 = fmul(fadd(p.X, p.Y), fadd(q.X, q.Y));
-  F t4 = fadd(t0, t1);
-  t3 = fsub(t3, t4);
-  t4 = fmul(fadd(p.Y, p.Z), fadd(q.Y, q.Z));
-  F X3 = fadd(t1, t2);
-  t4 = fsub(t4, X3);
-  X3 = fmul(fadd(p.X, p.Z), fadd(q.X, q.Z));
-  F Y3 = fadd(t0, t2);
-  Y3 = fsub(X3, Y3);
-  X3 = fadd(t0, t0);
-  t0 = fadd(X3, t0);
+  // the cross terms m - s - s' carry once, 3 t0 comes carried in one pass
+  F t3 = fsub2(fmul(fadd(p.X, p.Y), fadd(q.X, q.Y)), t0, t1);
+  F t4 = fsub2(fmul(fadd(p.Y, p.Z), fadd(q.Y, q.Z)), t1, t2);
+  F Y3 = fsub2(fmul(fadd(p.X, p.Z), fadd(q.X, q.Z)), t0, t2);
+  F X3;
+  t0 = fmulk<3>(t0);
   t2 = fmul_b3(t2);
   F Z3 = fadd(t1, t2);
   t1 = fsub(t1, t2);
@@ -119,13 +124,11 @@ template <class F>
 LSG_INL proj_t<F> proj_add_mixed(const proj_t<F>& p, const aff_t<F>& q) {
   F t0 = fmul(p.X, q.x);
   F t1 = fmul(p.Y, q.y);
-  F t3 = fmul(fadd(q.x, q.y), fadd(p.X, p.Y));
-  F t4 = fadd(t0, t1);
-  t3 = fsub(t3, t4);
-  t4 = fadd(fmul(q.y, p.Z), p.Y);
+  F t3 = fsub2(fmul(fadd(q.x, q.y), fadd(p.X, p.Y)), t0, t1);
+  F t4 = fadd(fmul(q.y, p.Z), p.Y);
   F Y3 = fadd(fmul(q.x, p.Z), p.X);
-  F X3 = fadd(t0, t0);
-  t0 = fadd(X3, t0);
+  F X3;
+  t0 = fmulk<3>(t0);
   F t2 = fmul_b3(p.Z);
   F Z3 = fadd(t1, t2);
   t1 = fsub(t1, t2);
@@ -150,22 +153,17 @@ LSG_INL proj_t<F> proj_add_mixed(const proj_t<F>& p, const aff_t<F>& q) {
 template <class F>
 LSG_INL proj_t<F> proj_dbl(const proj_t<F>& p) {
   F t0 = fsqr(p.Y);
-  F Z3 = fadd(t0, t0);
-  Z3 = fadd(Z3, Z3);
-  Z3 = fadd(Z3, Z3);
+  F Z3 = fmulk<8>(t0);
   F t1 = fmul(p.Y, p.Z);
   F t2 = fmul_b3(fsqr(p.Z));
   F X3 = fmul(t2, Z3);
   F Y3 = fadd(t0, t2);
   Z3 = fmul(t1, Z3);
-  t1 = fadd(t2, t2);
-  t2 = fadd(t1, t2);
-  t0 = fsub(t0, t2);
+  t0 = fsub(t0, fmulk<3>(t2));  // (as one lazy sum t0 - 3 t2, k_sign's scratch grew: 912 -> 944 B)
   Y3 = fmul(t0, Y3);
   Y3 = fadd(X3, Y3);
   t1 = fmul(p.X, p.Y);
-  X3 = fmul(t0, t1);
-  X3 = fadd(X3, X3);
+  X3 = fmulk<2>(fmul(t0, t1));
   proj_t<F> r;
   r.X = X3;
   r.Y = Y3;
@@ -302,18 +300,14 @@ LSG_INL jac_t<F> jac_dbl_t(const jac_t<F>& p) {
   F A = fsqr(p.X);
   F B = fsqr(p.Y);
   F C = fsqr(B);
-  F D = fsub(fsqr(fadd(p.X, B)), fadd(A, C));
-  D = fadd(D, D);
-  F E = fadd(fadd(A, A), A);
+  // D = 2 ((X + B)^2 - A - C): the doubling and the carry of the difference in one pass
+  F D = (fsum(fsqr(fadd(p.X, B))) - A - C).template carry_mul<2>();
+  F E = fmulk<3>(A);
   F Fq = fsqr(E);
   jac_t<F> r;
-  r.X = fsub(Fq, fadd(D, D));
-  F C8 = fadd(C, C);
-  C8 = fadd(C8, C8);
-  C8 = fadd(C8, C8);
-  r.Y = fsub(fmul(E, fsub(D, r.X)), C8);
-  F yz = fmul(p.Y, p.Z);
-  r.Z = fadd(yz, yz);
+  r.X = (fsum(Fq) - fsum_mulk<2>(fsum(D))).carry();
+  r.Y = fsub(fmul(E, fsub(D, r.X)), fmulk<8>(C));
+  r.Z = fmulk<2>(fmul(p.Y, p.Z));
   return r;
 }
 LSG_BIGFN jac_t<fp_t> jac_dbl(jac_t<fp_t> p) { return jac_dbl_t(p); }

@@ -3,7 +3,7 @@
 // Representation: 14 signed limbs of 29 bits (radix 2^29, Montgomery R = 2^406); lane h
 // (0/1) of a pair holds limbs 7h..7h+6, so a wave64 carries 32 field elements.  Values are
 // LAZY: an fp_t is any integer congruent to the element, |v| < 2^12 p, with every limb in
-// [-8, 2^29 + 8) except the signed top limb (limb 13).  Nothing is reduced mod p except
+// [-8, 2^29 + 8] except the signed top limb (limb 13).  Nothing is reduced mod p except
 // where a canonical value is needed (equality, zero tests, serialisation), so
 //   fp_add / fp_sub / fp_neg  = one limb-wise add + one parallel carry round (no carry
 //                               chains, no comparisons, no cross-lane lookahead)
@@ -117,6 +117,30 @@ LSG_PFN fp_t fp_from_arr(const uint32_t* c) {
   return r;
 }
 
+// The range of a carried limb 0..12 (closed; see "lazy sums" below) and, in the audit build
+// (-DLSG_SUM_AUDIT, host only), the check that a value entering a product or leaving a carry
+// is inside it.  The signed top limb is bounded by the value; the audit asks 25 bits of it.
+constexpr int64_t LSG_LIMB_MIN = -8, LSG_LIMB_MAX = ((int64_t)1 << 29) + 8;
+#ifdef LSG_SUM_AUDIT
+#include <stdio.h>
+#include <stdlib.h>
+inline void fps_audit_fail(const char* what, int k, long long v, long long lo, long long hi) {
+  fprintf(stderr, "LSG_SUM_AUDIT: %s: limb %d = %lld outside [%lld, %lld]\n", what, k, v, lo, hi);
+  abort();
+}
+inline void fps_audit_carried(const fp_t& a, const char* what) {
+  for (int k = 0; k < LSG_PL - 1; k++) {
+    const long long v = (int32_t)a.l[k];
+    if (v < LSG_LIMB_MIN || v > LSG_LIMB_MAX) fps_audit_fail(what, k, v, LSG_LIMB_MIN, LSG_LIMB_MAX);
+  }
+  const long long t = (int32_t)a.l[LSG_PL - 1];
+  if (t < -(1ll << 24) || t > (1ll << 24)) fps_audit_fail(what, LSG_PL - 1, t, -(1ll << 24), 1ll << 24);
+}
+#define LSG_AUDIT_CARRIED(a, what) fps_audit_carried(a, what)
+#else
+#define LSG_AUDIT_CARRIED(a, what) ((void)0)
+#endif
+
 // ---- carries
 // One parallel carry round: limb k keeps its low 29 bits plus the (signed) carry of limb
 // k-1; the top limb keeps everything above.  Value-preserving; inputs with |limb| < 2^31
@@ -211,6 +235,10 @@ LSG_PFN void pair_redc_tail(int64_t* t, fp_t& r, bool top) {
 // N independent products advance step by step together: in-order issue stalls a lone
 // product on its serial chain (t0 mad -> m -> DPP broadcast -> m*p mads -> retire) at the
 // one or two waves per SIMD the per-set kernels run at; N chains fill those stalls.
+// Operand limbs: carried, [-8, 2^29 + 8] (closed: carry_mul<12> reaches 2^29 + 8), or the
+// uncarried two-term sums of the Fp2 squaring leaf; a partial product is below
+// (2^29 + 8)^2 < 2^58.0001 (2^59.1 with one doubled operand), 7 of them and 7 reduction terms
+// of < 2^58 per column and lane: |t| < 2^62.5.
 template <int N>
 LSG_PFN void pair_mont_mul_n(fp_t* r, const fp_t* a, const fp_t* b) {
   const bool top = pair_top();
@@ -283,7 +311,7 @@ LSG_PFN void pair_mont_mul_n(fp_t* r, const fp_t* a, const fp_t* b) {
 // integer is a a + sum m_s p 2^(29 s) with the m sequence of pair_mont_mul_n(a, a), and after
 // pair_redc_tail the limbs are bit for bit those of the product.
 // Bound: a column takes at most one product term and one reduction term per step for 7 steps
-// per lane; for limbs in [-8, 2^29 + 8) and the doubled operand below 2^30 + 16 that is
+// per lane; for limbs in [-8, 2^29 + 8] and the doubled operand below 2^30 + 16 that is
 // |t| < 7 (2^59.1 + 2^58) < 2^62.3 plus the carries of < 2^34 that stay behind.  The one-lane
 // host build holds a column for 14 steps and carries once at mid-loop, as pair_sop2_n does.
 #ifndef LSG_SQR_STEP_FENCE  // A/B builds: 0 = the steps of a squaring scheduled freely
@@ -361,7 +389,8 @@ LSG_PFN void pair_mont_sqr_n(fp_t* r, const fp_t* a) {
 // reduction's overhead, its two additions and three subtractions (~330 other instructions per
 // lane instead of ~560).  Bounds: in the pair layout an accumulator lives at most 7 steps on
 // each lane (lane 1 hands only its low 29 bits down, the carry stays behind), so it sums at
-// most 7 x 3 terms of < 2^58.1: |t| < 2^62.6.  The one-lane host build (LSG_PAIR_G = 1) keeps
+// most 7 x 3 terms of < 2^58.1 (carried operands only, limbs in [-8, 2^29 + 8]: (2^29 + 8)^2 <
+// 2^58.0001; a lazy sum must be carried before it comes here): |t| < 2^62.6.  The one-lane host build (LSG_PAIR_G = 1) keeps
 // a column for 14 steps and carries once at mid-loop instead.  For inputs |x|, |y| < 2^12.6 p
 // the outputs satisfy |r| < 3p.
 template <int N, bool NEG0 = false>  // NEG0: output 0 takes xa ya - xb yb
@@ -453,6 +482,8 @@ LSG_PFN void pair_fp2_mul_sop(fp_t& c0, fp_t& c1, const fp_t& a0, const fp_t& a1
 
 LSG_PLEAF fp_t pair_mont_mul(fp_t a, fp_t b) {
   LSG_COUNT_MUL();
+  LSG_AUDIT_CARRIED(a, "product operand");
+  LSG_AUDIT_CARRIED(b, "product operand");
   fp_t r;
   pair_mont_mul_n<1>(&r, &a, &b);
   return r;
@@ -462,6 +493,7 @@ LSG_PLEAF fp_t pair_mont_mul(fp_t a, fp_t b) {
 #endif
 LSG_PLEAF fp_t pair_mont_sqr(fp_t a) {
   LSG_COUNT_MUL();
+  LSG_AUDIT_CARRIED(a, "squaring operand");
   fp_t r;
   pair_mont_sqr_n<1>(&r, &a);
   return r;
@@ -536,6 +568,10 @@ LSG_PLEAF fp_duo pair_mont_mul2_v(fp_arg_t a0, fp_arg_t b0, fp_arg_t a1, LSG_TAI
   LSG_COUNT_MUL();
   const fp_t x[2] = {fp_unpack(a0), fp_unpack(a1)}, y[2] = {fp_unpack(b0), LSG_TAIL_UNPACK(b1)};
   fp_t r[2];
+  for (int n = 0; n < 2; n++) {
+    LSG_AUDIT_CARRIED(x[n], "product operand");
+    LSG_AUDIT_CARRIED(y[n], "product operand");
+  }
 #if LSG_LEAF_MODE == 2
   pair_mont_mul_n<2>(r, x, y);
 #else
@@ -586,6 +622,173 @@ LSG_PFN fp_t fp_sub(const fp_t& a, const fp_t& b) {
   return pair_carry(r);
 }
 LSG_PFN fp_t fp_neg(const fp_t& a) { return fp_sub(fp_zero(), a); }
+
+// ---- lazy sums: linear combinations with ONE carry round
+// fp_add / fp_sub pay a carry round (23 of their ~30 instructions) per operation.  A lazy sum
+// fps_t<P, N> is an UNCARRIED limb vector: the limb-wise sum of at most P carried values minus
+// at most N carried values.  Building one costs limb additions only and the counts add up in
+// the type; carry() is the one place a carry round happens and the only way back to an fp_t
+// (there is no implicit conversion: products, selects, tests, canonical forms and stores take
+// carried values, so the compiler rejects a missing carry).
+// Bound rule.  Carried limbs 0..12 lie in [LSG_LIMB_MIN, LSG_LIMB_MAX] = [-8, 2^29 + 8]
+// (pair_carry gives [-4, 2^29 + 4), the reductions [0, 2^29), carry_mul at most 2^29 + 8), so
+// a limb of fps_t<P, N> lies in [fps_lo, fps_hi] = [-8 P - (2^29 + 8) N, (2^29 + 8) P + 8 N].
+// pair_carry needs |limb| < 2^31 (two's complement): P <= 3 and N <= 3, checked by
+// static_assert from these bounds; longer chains carry in groups.  The signed top limb is
+// bounded by the value instead (|v| < 2^12.6 p per term: below 2^17), far from 32 bits.
+// A carry round does not change the integer, so every product sees the operand integers of
+// the eager form and returns the same words.
+// -DLSG_EAGER_SUMS: the same API carrying at every operation (lsg_tower.hpp's fallback, which
+// the fully reduced backends use as well) -- the A/B build that computes as before.
+// -DLSG_SUM_AUDIT (host builds): every lazy limb shadowed in 64 bits; abort when a limb at a
+// carry is outside the range its type promises or a product operand outside the carried range.
+#define LSG_SUM_RULE 1
+constexpr int64_t fps_hi(int P, int N) { return P * LSG_LIMB_MAX - N * LSG_LIMB_MIN; }
+constexpr int64_t fps_lo(int P, int N) { return P * LSG_LIMB_MIN - N * LSG_LIMB_MAX; }
+constexpr int64_t fps_floor_shr(int64_t a, int sh) {
+  return a >= 0 ? a >> sh : -((-a + ((int64_t)1 << sh) - 1) >> sh);
+}
+constexpr bool fps_fits32(int64_t lo, int64_t hi) { return lo >= -((int64_t)1 << 31) && hi < ((int64_t)1 << 31); }
+// carry(): every limb fits pair_carry's precondition and comes out a carried limb
+constexpr bool fps_carry_ok(int P, int N) {
+  return fps_fits32(fps_lo(P, N), fps_hi(P, N)) && fps_floor_shr(fps_lo(P, N), 29) >= LSG_LIMB_MIN &&
+         ((int64_t)1 << 29) - 1 + fps_floor_shr(fps_hi(P, N), 29) <= LSG_LIMB_MAX;
+}
+// carry_mul<K>(), K = m 2^s with m = 1 or 3: t = m limb fits 32 bits, the low 29 - s bits of t
+// shifted up by s plus the carry t >> (29 - s) of the limb below is a carried limb
+constexpr int fps_mulk_m(int K) { return K % 3 == 0 ? 3 : 1; }
+constexpr int fps_mulk_s(int K) {
+  int s = 0;
+  for (int q = K / fps_mulk_m(K); q > 1; q >>= 1) s++;
+  return s;
+}
+constexpr bool fps_mulk_valid(int K) { return K >= 1 && (fps_mulk_m(K) << fps_mulk_s(K)) == K && fps_mulk_s(K) <= 3; }
+constexpr bool fps_carry_mul_ok(int K, int P, int N) {
+  const int64_t m = fps_mulk_m(K);
+  const int s = fps_mulk_s(K);
+  return fps_mulk_valid(K) && fps_fits32(m * fps_lo(P, N), m * fps_hi(P, N)) &&
+         fps_floor_shr(m * fps_lo(P, N), 29 - s) >= LSG_LIMB_MIN &&
+         ((int64_t)1 << 29) - ((int64_t)1 << s) + fps_floor_shr(m * fps_hi(P, N), 29 - s) <= LSG_LIMB_MAX;
+}
+static_assert(fps_carry_ok(3, 3) && !fps_carry_ok(4, 0) && !fps_carry_ok(0, 4), "carry(): P <= 3 and N <= 3");
+static_assert(fps_carry_mul_ok(12, 1, 0) && fps_carry_mul_ok(8, 1, 0) && fps_carry_mul_ok(3, 1, 0), "x12, x8, x3");
+static_assert(fps_carry_mul_ok(2, 3, 3) && fps_carry_mul_ok(4, 3, 1) && fps_carry_mul_ok(8, 2, 0), "x2, x4, x8 of sums");
+static_assert(!fps_carry_mul_ok(4, 1, 2) && !fps_carry_mul_ok(12, 2, 0) && !fps_carry_mul_ok(8, 1, 1), "limits");
+
+#ifndef LSG_EAGER_SUMS
+#define LSG_LAZY_SUMS 1
+template <int P, int N>
+struct fps_t {
+  uint32_t l[LSG_PL];
+#ifdef LSG_SUM_AUDIT
+  int64_t s[LSG_PL];  // the same limbs without wrap-around
+  void audit(const char* what, int64_t m) const {
+    for (int k = 0; k < LSG_PL; k++) {
+      const bool topk = k == LSG_PL - 1;
+      const int64_t lo = topk ? -((int64_t)1 << 24) : fps_lo(P, N), hi = topk ? ((int64_t)1 << 24) : fps_hi(P, N);
+      if (s[k] < lo || s[k] > hi) fps_audit_fail(what, k, s[k], lo, hi);
+      if (m * s[k] != (int64_t)(int32_t)((uint32_t)m * l[k])) fps_audit_fail("32-bit wrap", k, m * s[k], INT32_MIN, INT32_MAX);
+    }
+  }
+#endif
+  // the one carry round of the sum
+  LSG_PFN fp_t carry() const {
+    static_assert(fps_carry_ok(P, N), "lazy sum too long for one carry round: carry a group first (P <= 3, N <= 3)");
+#ifdef LSG_SUM_AUDIT
+    audit("carry()", 1);
+#endif
+    fp_t a;
+#pragma unroll
+    for (int k = 0; k < LSG_PL; k++) a.l[k] = l[k];
+    const fp_t o = pair_carry(a);
+    LSG_AUDIT_CARRIED(o, "carry() output");
+    return o;
+  }
+  // K times the sum, carried, in one pass (K = 2, 3, 4, 8, 12): 3 or 4 instructions per limb
+  template <int K>
+  LSG_PFN fp_t carry_mul() const {
+    static_assert(fps_carry_mul_ok(K, P, N), "small multiple of this sum does not come out carried: carry() first");
+    constexpr int m = fps_mulk_m(K), s = fps_mulk_s(K), sh = 29 - s;
+    constexpr uint32_t lowm = (1u << sh) - 1;
+#ifdef LSG_SUM_AUDIT
+    audit("carry_mul()", m);
+#endif
+    const bool top = pair_top();
+    uint32_t t[LSG_PL];
+    int32_t c[LSG_PL];
+#pragma unroll
+    for (int k = 0; k < LSG_PL; k++) {
+      t[k] = m == 3 ? l[k] + (l[k] << 1) : l[k];
+      c[k] = (int32_t)t[k] >> sh;
+    }
+    const uint32_t cin = pup((uint32_t)c[LSG_PL - 1]);
+    fp_t o;
+    o.l[0] = ((t[0] & lowm) << s) + cin;
+#pragma unroll
+    for (int k = 1; k < LSG_PL - 1; k++) o.l[k] = ((t[k] & lowm) << s) + (uint32_t)c[k - 1];
+    o.l[LSG_PL - 1] = ((top ? t[LSG_PL - 1] : (t[LSG_PL - 1] & lowm)) << s) + (uint32_t)c[LSG_PL - 2];
+    LSG_AUDIT_CARRIED(o, "carry_mul() output");
+    return o;
+  }
+};
+#ifdef LSG_SUM_AUDIT
+#define LSG_FPS_SHADOW(stmt) stmt
+#else
+#define LSG_FPS_SHADOW(stmt)
+#endif
+LSG_PFN fps_t<1, 0> fps(const fp_t& a) {
+  fps_t<1, 0> r;
+#pragma unroll
+  for (int k = 0; k < LSG_PL; k++) {
+    r.l[k] = a.l[k];
+    LSG_FPS_SHADOW(r.s[k] = (int32_t)a.l[k]);
+  }
+  return r;
+}
+template <int P, int N, int Q, int M>
+LSG_PFN fps_t<P + Q, N + M> operator+(const fps_t<P, N>& a, const fps_t<Q, M>& b) {
+  fps_t<P + Q, N + M> r;
+#pragma unroll
+  for (int k = 0; k < LSG_PL; k++) {
+    r.l[k] = a.l[k] + b.l[k];
+    LSG_FPS_SHADOW(r.s[k] = a.s[k] + b.s[k]);
+  }
+  return r;
+}
+template <int P, int N, int Q, int M>
+LSG_PFN fps_t<P + M, N + Q> operator-(const fps_t<P, N>& a, const fps_t<Q, M>& b) {
+  fps_t<P + M, N + Q> r;
+#pragma unroll
+  for (int k = 0; k < LSG_PL; k++) {
+    r.l[k] = a.l[k] - b.l[k];
+    LSG_FPS_SHADOW(r.s[k] = a.s[k] - b.s[k]);
+  }
+  return r;
+}
+template <int P, int N>
+LSG_PFN fps_t<N, P> operator-(const fps_t<P, N>& a) {
+  fps_t<N, P> r;
+#pragma unroll
+  for (int k = 0; k < LSG_PL; k++) {
+    r.l[k] = 0u - a.l[k];
+    LSG_FPS_SHADOW(r.s[k] = -a.s[k]);
+  }
+  return r;
+}
+// K times a sum, uncarried (the counts scale)
+template <int K, int P, int N>
+LSG_PFN fps_t<K * P, K * N> fps_mulk(const fps_t<P, N>& a) {
+  static_assert(K >= 1 && K <= 3, "uncarried small multiples up to 3");
+  fps_t<K * P, K * N> r;
+#pragma unroll
+  for (int k = 0; k < LSG_PL; k++) {
+    r.l[k] = a.l[k] * (uint32_t)K;
+    LSG_FPS_SHADOW(r.s[k] = a.s[k] * K);
+  }
+  return r;
+}
+#endif  // !LSG_EAGER_SUMS
+
 LSG_PFN fp_t fp_mul(const fp_t& a, const fp_t& b) { return pair_mont_mul(a, b); }
 #if LSG_LEAF_MODE == 0
 LSG_PFN void fp_mul2(fp_t& r0, fp_t& r1, const fp_t& a0, const fp_t& b0, const fp_t& a1, const fp_t& b1) {
@@ -626,6 +829,10 @@ LSG_PLEAF fp_duo pair_fp2_mul_v(fp_arg_t va0, fp_arg_t va1, fp_arg_t vb0, LSG_TA
   LSG_COUNT_MUL();
   LSG_COUNT_MUL();
   const fp_t a0 = fp_unpack(va0), a1 = fp_unpack(va1), b0 = fp_unpack(vb0), b1 = LSG_TAIL_UNPACK(vb1);
+  LSG_AUDIT_CARRIED(a0, "Fp2 product operand");
+  LSG_AUDIT_CARRIED(a1, "Fp2 product operand");
+  LSG_AUDIT_CARRIED(b0, "Fp2 product operand");
+  LSG_AUDIT_CARRIED(b1, "Fp2 product operand");
 #if LSG_FP2_SOP
   fp_duo d;
   pair_fp2_mul_sop(d.x, d.y, a0, a1, b0, b1);
@@ -651,6 +858,8 @@ LSG_PLEAF fp_duo pair_fp2_sqr_v(fp_arg_t va0, fp_arg_t va1) {
   LSG_COUNT_MUL();
   LSG_COUNT_MUL();
   const fp_t a0 = fp_unpack(va0), a1 = fp_unpack(va1);
+  LSG_AUDIT_CARRIED(a0, "Fp2 squaring operand");
+  LSG_AUDIT_CARRIED(a1, "Fp2 squaring operand");
   // s = a0 + a1, d = a0 - a1 and e = a1 + a1 limb by limb, with no carry round: they go
   // straight into a product, whose mads take signed 32-bit operands.  Limbs of s and e lie in
   // [-16, 2^30 + 16) and those of d in (-2^29 - 16, 2^29 + 16), so a partial product is below

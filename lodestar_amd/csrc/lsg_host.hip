@@ -3692,6 +3692,23 @@ static int check_sqr(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out, in
 int lsg_check_fp_sqr(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_sqr(c, in, n, out, 1); }
 int lsg_check_fp2_sqr(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_sqr(c, in, n, out, 2); }
 
+// the lazy-sum hook (k_check_sums): 12 elements per item in, 42 out
+int lsg_check_sums(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
+  constexpr size_t EIN = 12, EOUT = 42;
+  if (!c || (n && (!in || !out)) || n > 0x7fffffffull / (4 * W_FP * EOUT)) return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  if (n == 0) return LSG_OK;
+  Slot* s = &c->dev[0]->util;
+  timer_reset(s);
+  LSG_RC(ensure(s, s->d_aux, 4 * EIN * W_FP * n));
+  LSG_RC(ensure(s, s->d_Fb, 4 * EOUT * W_FP * n));
+  LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, in, 4 * EIN * W_FP * n, hipMemcpyHostToDevice, s->st[0]));
+  KL(s, "k_check_sums", lsgk::check_sums(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  LSG_HIP(s, hipMemcpyAsync(out, s->d_Fb.p, 4 * EOUT * W_FP * n, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  return LSG_OK;
+}
+
 int lsg_probe_fp_mul_rate(lsg_ctx* c, double* fp_mul_per_s, double* mad_per_s) {
   if (!c || !fp_mul_per_s || !mad_per_s) return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);

@@ -172,32 +172,28 @@ LSG_DEVI void mf_sqr(uint32_t* lds, int w) {
   __syncthreads();
   // Karatsuba Fp6 combination of t (V0..5): c0 = v0 + xi (m0 - v1 - v2), c1 = m1 - v0 - v1 + xi v2,
   // c2 = m2 - v0 - v2 + v1; likewise u (V6..11).  New f: c0 = u - t - v t, c1 = 2t.
-  auto fin = [&](int base, int j) {
-    const fp2_t v0 = mf_get2(lds, MF_VC(base)), v1 = mf_get2(lds, MF_VC(base + 1)), v2 = mf_get2(lds, MF_VC(base + 2));
-    if (j == 0) return fp2_add(v0, fp2_mul_xi(fp2_sub(fp2_sub(mf_get2(lds, MF_VC(base + 3)), v1), v2)));
-    if (j == 1) return fp2_add(fp2_sub(fp2_sub(mf_get2(lds, MF_VC(base + 4)), v0), v1), fp2_mul_xi(v2));
-    return fp2_add(fp2_sub(fp2_sub(mf_get2(lds, MF_VC(base + 5)), v0), v2), v1);
-  };
+  // The combinations are lazy sums regrouped for one carry per group (lsg_pairing.hpp mfc_sqr).
+  auto V = [&](int p) { return mf_get2(lds, MF_VC(p)); };
   fp2_t o0, o1, o2;
   if (w == 0) {  // c1 = 2t
-    o0 = fin(0, 0);
-    o1 = fin(0, 1);
-    o2 = fin(0, 2);
+    o0 = mfc_sqr<0>(V);
+    o1 = mfc_sqr<1>(V);
+    o2 = mfc_sqr<2>(V);
   } else if (w == 1) {  // c0.c0 = u0 - t0 - xi t2
-    o0 = fp2_sub(fp2_sub(fin(6, 0), fin(0, 0)), fp2_mul_xi(fin(0, 2)));
+    o0 = mfc_sqr<3>(V);
   } else if (w == 2) {  // c0.c1 = u1 - t1 - t0
-    o0 = fp2_sub(fp2_sub(fin(6, 1), fin(0, 1)), fin(0, 0));
+    o0 = mfc_sqr<4>(V);
   } else {  // c0.c2 = u2 - t2 - t1
-    o0 = fp2_sub(fp2_sub(fin(6, 2), fin(0, 2)), fin(0, 1));
+    o0 = mfc_sqr<5>(V);
   }
   // No barrier before or after the writes: f was last read in the product half (before the
   // barrier above) and the combination reads only the products; the next reader of f (the M
   // phase) and the next writer of the product slots (the P phase) both come after the L
   // phase's barrier.  (Round 4 kept two more barriers here.)
   if (w == 0) {
-    mf_put2(lds, MF_FC(3), fp2_add(o0, o0));
-    mf_put2(lds, MF_FC(4), fp2_add(o1, o1));
-    mf_put2(lds, MF_FC(5), fp2_add(o2, o2));
+    mf_put2(lds, MF_FC(3), o0);
+    mf_put2(lds, MF_FC(4), o1);
+    mf_put2(lds, MF_FC(5), o2);
   } else {
     mf_put2(lds, MF_FC(w - 1), o0);
   }
@@ -228,14 +224,14 @@ LSG_DEVI void mf_pair_lines(uint32_t* lds, int w) {
   }
   __syncthreads();
   // the lines of pair pi were read before the barrier: their slots take M
-  const fp2_t P0 = mf_get2(lds, MF_VC(6 * pi)), P1 = mf_get2(lds, MF_VC(6 * pi + 1)), P2 = mf_get2(lds, MF_VC(6 * pi + 2));
+  auto V = [&](int p) { return mf_get2(lds, MF_VC(6 * pi + p)); };
   if (h == 0) {
-    mf_put2(lds, MF_LC(2 * pi, 0), fp2_add(P0, fp2_mul_xi(P1)));
-    mf_put2(lds, MF_LC(2 * pi, 1), fp2_sub(fp2_sub(mf_get2(lds, MF_VC(6 * pi + 3)), P0), P2));
-    mf_put2(lds, MF_LC(2 * pi, 2), P2);
+    mf_put2(lds, MF_LC(2 * pi, 0), mfc_pair<0>(V));
+    mf_put2(lds, MF_LC(2 * pi, 1), mfc_pair<1>(V));
+    mf_put2(lds, MF_LC(2 * pi, 2), V(2));
   } else {
-    mf_put2(lds, MF_LC(2 * pi + 1, 0), fp2_sub(fp2_sub(mf_get2(lds, MF_VC(6 * pi + 4)), P0), P1));
-    mf_put2(lds, MF_LC(2 * pi + 1, 1), fp2_sub(fp2_sub(mf_get2(lds, MF_VC(6 * pi + 5)), P2), P1));
+    mf_put2(lds, MF_LC(2 * pi + 1, 0), mfc_pair<2>(V));
+    mf_put2(lds, MF_LC(2 * pi + 1, 1), mfc_pair<3>(V));
   }
   __syncthreads();
 }
@@ -287,40 +283,26 @@ LSG_DEVI void mf_mul_pair(uint32_t* lds, int w, int k) {
   }
   __syncthreads();
   auto V = [&](int p) { return mf_get2(lds, MF_VC(p)); };
-  // t0 = a M0, n = b (m4 + m5 v), t2 = s q (Karatsuba over Fp6, as in mf_sqr)
-  auto t0c = [&](int j) {
-    if (j == 0) return fp2_add(V(0), fp2_mul_xi(fp2_sub(fp2_sub(V(4), V(1)), V(2))));
-    if (j == 1) return fp2_add(fp2_sub(fp2_sub(V(3), V(0)), V(1)), fp2_mul_xi(V(2)));
-    return fp2_add(fp2_sub(fp2_sub(V(5), V(0)), V(2)), V(1));
-  };
-  auto t2c = [&](int j) {
-    if (j == 0) return fp2_add(V(11), fp2_mul_xi(fp2_sub(fp2_sub(V(15), V(12)), V(13))));
-    if (j == 1) return fp2_add(fp2_sub(fp2_sub(V(14), V(11)), V(12)), fp2_mul_xi(V(13)));
-    return fp2_add(fp2_sub(fp2_sub(V(16), V(11)), V(13)), V(12));
-  };
-  auto nc = [&](int j) {
-    if (j == 0) return fp2_add(V(6), fp2_mul_xi(V(10)));
-    if (j == 1) return fp2_sub(fp2_sub(V(8), V(6)), V(7));
-    return fp2_add(V(7), V(9));
-  };
-  // f'.c0 = t0 + v t1 = t0 + (xi n1, xi n2, n0);  f'.c1 = t2 - t0 - t1 = t2 - t0 - (xi n2, n0, n1)
+  // t0 = a M0, n = b (m4 + m5 v), t2 = s q (Karatsuba over Fp6, as in mf_sqr);
+  // f'.c0 = t0 + v t1 = t0 + (xi n1, xi n2, n0);  f'.c1 = t2 - t0 - t1 = t2 - t0 - (xi n2, n0, n1):
+  // each coefficient one regrouped lazy sum (lsg_pairing.hpp mfc_mul)
   fp2_t o0, o1;
   int j0, j1 = -1;
   if (w == 0) {  // c0.0, c0.1
-    o0 = fp2_add(t0c(0), fp2_mul_xi(nc(1)));
-    o1 = fp2_add(t0c(1), fp2_mul_xi(nc(2)));
+    o0 = mfc_mul<0>(V);
+    o1 = mfc_mul<1>(V);
     j0 = 0;
     j1 = 1;
   } else if (w == 1) {  // c0.2, c1.0
-    o0 = fp2_add(t0c(2), nc(0));
-    o1 = fp2_sub(fp2_sub(t2c(0), t0c(0)), fp2_mul_xi(nc(2)));
+    o0 = mfc_mul<2>(V);
+    o1 = mfc_mul<3>(V);
     j0 = 2;
     j1 = 3;
   } else if (w == 2) {  // c1.1
-    o0 = fp2_sub(fp2_sub(t2c(1), t0c(1)), nc(0));
+    o0 = mfc_mul<4>(V);
     j0 = 4;
   } else {  // c1.2
-    o0 = fp2_sub(fp2_sub(t2c(2), t0c(2)), nc(1));
+    o0 = mfc_mul<5>(V);
     j0 = 5;
   }
   // f's coefficients are not read in this half: write them at once
@@ -354,21 +336,18 @@ LSG_DEVI void mf_dbl_line(uint32_t* lds, int wl, bool use, const uint32_t* __res
     const fp2_t XX = fp2_sqr(X);
     v1 = fp2_mul(X, Y);
     const g1a_t Pk = lane_load<g1a_t>(P, sl);
-    mf_put_line(lds, wl, use, fp2_sub(t2, t0), fp2_mul_fp(fp2_add(fp2_add(XX, XX), XX), Pk.x),
-                fp2_mul_fp(fp2_neg(fp2_add(t1, t1)), Pk.y));
+    mf_put_line(lds, wl, use, fp2_sub(t2, t0), fp2_mul_fp(fp2_mulk<3>(XX), Pk.x),
+                fp2_mul_fp((-fp2s(t1)).carry_mul<2>(), Pk.y));
   }
-  fp2_t Z3 = fp2_add(t0, t0);
-  Z3 = fp2_add(Z3, Z3);
-  Z3 = fp2_add(Z3, Z3);
+  fp2_t Z3 = fp2_mulk<8>(t0);
   fp2_t X3 = fp2_mul(t2, Z3);
   fp2_t Y3 = fp2_add(t0, t2);
   mf_put2(lds, tb + 4, fp2_mul(t1, Z3));
-  const fp2_t u2 = fp2_add(fp2_add(t2, t2), t2);
-  const fp2_t s0 = fp2_sub(t0, u2);
+  const fp2_t s0 = (fp2s(t0) - fp2s_mulk<3>(fp2s(t2))).carry();  // t0 - 3 t2
   Y3 = fp2_mul(s0, Y3);
   mf_put2(lds, tb + 2, fp2_add(X3, Y3));
   X3 = fp2_mul(s0, v1);
-  mf_put2(lds, tb, fp2_add(X3, X3));
+  mf_put2(lds, tb, fp2_mulk<2>(X3));
 }
 LSG_DEVI void mf_add_line(uint32_t* lds, int wl, bool use, const uint32_t* __restrict__ P, const uint32_t* __restrict__ H,
                           size_t sl) {
@@ -388,7 +367,7 @@ LSG_DEVI void mf_add_line(uint32_t* lds, int wl, bool use, const uint32_t* __res
   const fp2_t E = fp2_mul(D, delta);
   const fp2_t F = fp2_mul(mf_get2(lds, tb + 4), C);
   const fp2_t G = fp2_mul(mf_get2(lds, tb), D);
-  const fp2_t Hs = fp2_sub(fp2_add(E, F), fp2_add(G, G));
+  const fp2_t Hs = (fp2s(E) + F - fp2s_mulk<2>(fp2s(G))).carry();  // E + F - 2G
   mf_put2(lds, tb, fp2_mul(delta, Hs));
   const fp2_t Y3 = fp2_sub(fp2_mul(theta, fp2_sub(G, Hs)), fp2_mul(E, mf_get2(lds, tb + 2)));
   mf_put2(lds, tb + 2, Y3);

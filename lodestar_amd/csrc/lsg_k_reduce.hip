@@ -190,8 +190,9 @@ __global__ void LSG_KERNEL_ATTR_W(1) k_fp12_pow_u64(const uint8_t* __restrict__ 
   while (top > 0 && !((r >> top) & 1u)) top--;
 #pragma unroll 1
   for (int b = top - 1; b >= 0; b--) {
-    acc = fp12_sqr(acc);
-    if ((r >> b) & 1u) acc = fp12_mul(acc, f);
+    // (the sums carried one operation at a time: as lazy sums this kernel's scratch grew, 784 -> 1056 B)
+    acc = fp12_sqr<false>(acc);
+    if ((r >> b) & 1u) acc = fp12_mul<false>(acc, f);
   }
   fp12_to_canon_bytes(out576, acc);
 }
@@ -220,6 +221,109 @@ __global__ void LSG_KERNEL_ATTR k_check_fp2_sqr(int n, const uint32_t* __restric
   const fp2_t c = fp2_sqr(fp2_t(lane_load<fp_t>(in, 2 * item), lane_load<fp_t>(in, 2 * item + 1)));
   lane_store(out, 2 * item, c.c0);
   lane_store(out, 2 * item + 1, c.c1);
+}
+// parity hook of the lazy sums (lsg_fp_pair.hpp fps_t, lsg_tower.hpp fp2s_t) at the lazy bounds.
+// The 12 n raw input elements form a ring; item i works on el(j) = element 12 i + j.  Per item
+// LSG_CHECK_SUMS_OUT elements, stored raw:
+//    0      (a + b + c - d - e - f).carry(), the maximal admissible chain
+//    1..5   2a, 3a, 4a, 8a, 12a (carry_mul)
+//    6..7   fp2_mul_b3(a + b u)
+//    8..10  jac_dbl over Fp of (a, b, c);          11..13  the same one carried operation at a time
+//   14..19  jac_dbl over Fp2 of (el 0..5);         20..25  the same one carried operation at a time
+//   26..31  proj_add over Fp2 of (el 0..5), (el 6..11);  32..37  the same one operation at a time
+//   38..39  mfc_mul<3> on V(p) = (el 2p, el 2p + 1), the fused Miller kernel's longest combination;
+//   40..41  its nested form
+template <class F>
+LSG_DEVI jac_t<F> check_jac_dbl_nested(const jac_t<F>& p) {
+  F A = fsqr(p.X), B = fsqr(p.Y), C = fsqr(B);
+  F D = fsub(fsqr(fadd(p.X, B)), fadd(A, C));
+  D = fadd(D, D);
+  F E = fadd(fadd(A, A), A);
+  F Fq = fsqr(E);
+  jac_t<F> r;
+  r.X = fsub(Fq, fadd(D, D));
+  F C8 = fadd(C, C);
+  C8 = fadd(C8, C8);
+  C8 = fadd(C8, C8);
+  r.Y = fsub(fmul(E, fsub(D, r.X)), C8);
+  F yz = fmul(p.Y, p.Z);
+  r.Z = fadd(yz, yz);
+  return r;
+}
+LSG_DEVI fp2_t check_b3_nested(const fp2_t& a) {
+  auto m12 = [](const fp_t& x) {
+    const fp_t x4 = fp_dbl(fp_dbl(x));
+    return fp_add(fp_dbl(x4), x4);
+  };
+  return fp2_t(m12(fp_sub(a.c0, a.c1)), m12(fp_add(a.c0, a.c1)));
+}
+LSG_DEVI g2p_t check_proj_add_nested(const g2p_t& p, const g2p_t& q) {
+  typedef fp2_t F;
+  F t0 = fmul(p.X, q.X), t1 = fmul(p.Y, q.Y), t2 = fmul(p.Z, q.Z);
+  F t3 = fmul(fadd(p.X, p.Y), fadd(q.X, q.Y));
+  F t4 = fadd(t0, t1);
+  t3 = fsub(t3, t4);
+  t4 = fmul(fadd(p.Y, p.Z), fadd(q.Y, q.Z));
+  F X3 = fadd(t1, t2);
+  t4 = fsub(t4, X3);
+  X3 = fmul(fadd(p.X, p.Z), fadd(q.X, q.Z));
+  F Y3 = fadd(t0, t2);
+  Y3 = fsub(X3, Y3);
+  X3 = fadd(t0, t0);
+  t0 = fadd(X3, t0);
+  t2 = check_b3_nested(t2);
+  F Z3 = fadd(t1, t2);
+  t1 = fsub(t1, t2);
+  Y3 = check_b3_nested(Y3);
+  X3 = fmul(t4, Y3);
+  t2 = fmul(t3, t1);
+  X3 = fsub(t2, X3);
+  Y3 = fmul(Y3, t0);
+  t1 = fmul(t1, Z3);
+  Y3 = fadd(t1, Y3);
+  t0 = fmul(t0, t3);
+  Z3 = fmul(Z3, t4);
+  Z3 = fadd(Z3, t0);
+  return g2p_t{X3, Y3, Z3};
+}
+constexpr int LSG_CHECK_SUMS_IN = 12, LSG_CHECK_SUMS_OUT = 42;
+__global__ void LSG_KERNEL_ATTR k_check_sums(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  (void)lead;
+  const size_t ring = (size_t)LSG_CHECK_SUMS_IN * (size_t)n;
+  auto el = [&](int j) { return lane_load<fp_t>(in, ((size_t)LSG_CHECK_SUMS_IN * item + (size_t)j) % ring); };
+  auto el2 = [&](int j) { return fp2_t(el(2 * j), el(2 * j + 1)); };
+  int o = 0;
+  auto put = [&](const fp_t& v) { lane_store(out, (size_t)LSG_CHECK_SUMS_OUT * item + (size_t)(o++), v); };
+  auto put2 = [&](const fp2_t& v) {
+    put(v.c0);
+    put(v.c1);
+  };
+  const fp_t a = el(0), b = el(1), c = el(2);
+  put((fps(a) + b + c - el(3) - el(4) - el(5)).carry());
+  put(fp_mulk<2>(a));
+  put(fp_mulk<3>(a));
+  put(fp_mulk<4>(a));
+  put(fp_mulk<8>(a));
+  put(fp_mulk<12>(a));
+  put2(fp2_mul_b3(fp2_t(a, b)));
+  const jac_t<fp_t> j1 = {a, b, c};
+  const jac_t<fp_t> r1 = jac_dbl(j1), n1 = check_jac_dbl_nested(j1);
+  put(r1.X), put(r1.Y), put(r1.Z);
+  put(n1.X), put(n1.Y), put(n1.Z);
+  const jac_t<fp2_t> j2 = {el2(0), el2(1), el2(2)};
+  const jac_t<fp2_t> r2 = jac_dbl(j2), n2 = check_jac_dbl_nested(j2);
+  put2(r2.X), put2(r2.Y), put2(r2.Z);
+  put2(n2.X), put2(n2.Y), put2(n2.Z);
+  const g2p_t p = {el2(0), el2(1), el2(2)}, q = {el2(3), el2(4), el2(5)};
+  const g2p_t r3 = g2_add(p, q), n3 = check_proj_add_nested(p, q);
+  put2(r3.X), put2(r3.Y), put2(r3.Z);
+  put2(n3.X), put2(n3.Y), put2(n3.Z);
+  // t2_0 - t0_0 - xi n2 of the M phase (lsg_k_miller.hip mf_mul_pair, lsg_pairing.hpp mfc_mul)
+  put2(mfc_mul<3>(el2));
+  const fp2_t t2c = fp2_add(el2(11), fp2_mul_xi(fp2_sub(fp2_sub(el2(15), el2(12)), el2(13))));
+  const fp2_t t0c = fp2_add(el2(0), fp2_mul_xi(fp2_sub(fp2_sub(el2(4), el2(1)), el2(2))));
+  put2(fp2_sub(fp2_sub(t2c, t0c), fp2_mul_xi(fp2_add(el2(7), el2(9)))));
 }
 
 // roofline probe: 4 independent limb-parallel Montgomery chains per pair
@@ -298,6 +402,9 @@ hipError_t check_fp_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out
 }
 hipError_t check_fp2_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
   LSG_LAUNCH_ITEMS(k_check_fp2_sqr, n, st, n, in, out);
+}
+hipError_t check_sums(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_sums, n, st, n, in, out);
 }
 hipError_t probe_fp_mul(hipStream_t st, int items, int iters, uint32_t* io) {
   LSG_LAUNCH_ITEMS(k_probe_fp_mul, items, st, items, iters, io);

@@ -156,5 +156,6 @@ hipError_t probe_fp_mul(hipStream_t st, int items, int iters, uint32_t* io);
 hipError_t check_fp2_mul(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t check_fp_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t check_fp2_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
+hipError_t check_sums(hipStream_t st, int n, const uint32_t* in, uint32_t* out);  // 12 elements in, 42 out per item
 hipError_t probe_mad(hipStream_t st, int blocks, int iters, uint32_t seed, uint64_t* io);
 }  // namespace lsgk

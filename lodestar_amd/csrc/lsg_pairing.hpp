@@ -21,22 +21,17 @@ LSG_BIGFN line_t ml_dbl_step_raw(g2p_t& T) {
   fp2_t XX = fp2_sqr(T.X);
   line_t L;
   L.l00 = fp2_sub(t2, t0);
-  L.l01 = fp2_add(fp2_add(XX, XX), XX);
-  L.l11 = fp2_neg(fp2_add(t1, t1));
-  fp2_t Z3 = fp2_add(t0, t0);
-  Z3 = fp2_add(Z3, Z3);
-  Z3 = fp2_add(Z3, Z3);
+  L.l01 = fp2_mulk<3>(XX);
+  L.l11 = (-fp2s(t1)).carry_mul<2>();  // -2 t1
+  fp2_t Z3 = fp2_mulk<8>(t0);
   fp2_t X3 = fp2_mul(t2, Z3);
   fp2_t Y3 = fp2_add(t0, t2);
   Z3 = fp2_mul(t1, Z3);
-  fp2_t u1 = fp2_add(t2, t2);
-  fp2_t u2 = fp2_add(u1, t2);
-  fp2_t s0 = fp2_sub(t0, u2);
+  fp2_t s0 = (fp2s(t0) - fp2s_mulk<3>(fp2s(t2))).carry();  // t0 - 3 t2
   Y3 = fp2_mul(s0, Y3);
   Y3 = fp2_add(X3, Y3);
   fp2_t v1 = fp2_mul(T.X, T.Y);
-  X3 = fp2_mul(s0, v1);
-  X3 = fp2_add(X3, X3);
+  X3 = fp2_mulk<2>(fp2_mul(s0, v1));
   T.X = X3;
   T.Y = Y3;
   T.Z = Z3;
@@ -57,7 +52,7 @@ LSG_BIGFN line_t ml_add_step_raw(g2p_t& T, g2a_t Q) {
   fp2_t E = fp2_mul(D, delta);
   fp2_t F = fp2_mul(T.Z, C);
   fp2_t G = fp2_mul(T.X, D);
-  fp2_t H = fp2_sub(fp2_add(E, F), fp2_add(G, G));
+  fp2_t H = (fp2s(E) + F - fp2s_mulk<2>(fp2s(G))).carry();  // E + F - 2G: one carry
   fp2_t X3 = fp2_mul(delta, H);
   fp2_t Y3 = fp2_sub(fp2_mul(theta, fp2_sub(G, H)), fp2_mul(E, T.Y));
   fp2_t Z3 = fp2_mul(E, T.Z);
@@ -72,6 +67,83 @@ LSG_INL line_t line_eval(line_t L, const fp_t& xP, const fp_t& yP) {
   L.l01 = fp2_mul_fp(L.l01, xP);
   L.l11 = fp2_mul_fp(L.l11, yP);
   return L;
+}
+
+// ---- Output combinations of the fused Miller kernel's phases (lsg_k_miller.hip: mf_sqr,
+// mf_pair_lines, mf_mul_pair), as functions of the phase's Fp2 products V(p).  Each output
+// coefficient is one linear combination of up to 11 products and their xi multiples; written
+// as lazy sums they are regrouped so that every carry takes a group of at most three added
+// and three subtracted values (the type rule): 2-5 carry rounds per component where the
+// nested fp2_add / fp2_sub form paid 6-14.  Regrouping an integer linear combination does not
+// change its value, so each result is the integer of the nested form (tests/native/sumcheck.cpp
+// holds those forms and compares).
+// S phase, f <- f^2: V0..5 the Karatsuba products of t = a b, V6..11 those of
+// u = (a + b)(a + v b).  J = 0..2: new c1.J = 2 t_J;  J = 3..5: new c0.(J-3) = (u - t - v t)_(J-3).
+template <int J, class G>
+LSG_INL fp2_t mfc_sqr(const G& V) {
+  if constexpr (J == 0) {
+    return fp6_kar_s0(V(0), V(1), V(2), V(3)).template carry_mul<2>();
+  } else if constexpr (J == 1) {
+    return fp6_kar_s1(V(0), V(1), V(2), V(4)).template carry_mul<2>();
+  } else if constexpr (J == 2) {
+    return fp6_kar_s2(V(0), V(1), V(2), V(5)).template carry_mul<2>();
+  } else if constexpr (J == 3) {  // u0 - t0 - xi t2
+    const fp2_t d = (fp6_kar_s0(V(6), V(7), V(8), V(9)) - fp6_kar_s0(V(0), V(1), V(2), V(3))).carry();
+    const fp2_t t2 = fp6_kar_s2(V(0), V(1), V(2), V(5)).carry();
+    return (fp2s(d) - fp2s_mul_xi(t2)).carry();
+  } else if constexpr (J == 4) {  // u1 - t1 - t0, with u1 - t1 = (m1' - v0' - v1') - (m1 - v0 - v1) + xi (v2' - v2)
+    const fp2_t d = ((fp2s(V(10)) - V(6) - V(7)) - (fp2s(V(4)) - V(0) - V(1))).carry();
+    const fp2_t e = (fp2s(d) + fp2s_mul_xi(fp2s(V(8)) - V(2))).carry();
+    return (fp2s(e) - fp6_kar_s0(V(0), V(1), V(2), V(3))).carry();
+  } else {  // u2 - t2 - t1, with u2 - t2 = (m2' - v0' - v2') - (m2 - v0 - v2) + v1' - v1
+    const fp2_t d = ((fp2s(V(11)) - V(6) - V(8)) - (fp2s(V(5)) - V(0) - V(2))).carry();
+    const fp2_t t1 = fp6_kar_s1(V(0), V(1), V(2), V(4)).carry();
+    return (fp2s(d) + V(7) - V(1) - t1).carry();
+  }
+}
+// P phase, M = l l' of two sparse lines from P0..P5 = V(0..5) (see mf_pair_lines):
+// J = 0: m0 = P0 + xi P1, 1: m1 = P3 - P0 - P2, 2: m4 = P4 - P0 - P1, 3: m5 = P5 - P2 - P1
+template <int J, class G>
+LSG_INL fp2_t mfc_pair(const G& V) {
+  if constexpr (J == 0) {
+    return (fp2s(V(0)) + fp2s_mul_xi(V(1))).carry();
+  } else if constexpr (J == 1) {
+    return fp2_sub2(V(3), V(0), V(2));
+  } else if constexpr (J == 2) {
+    return fp2_sub2(V(4), V(0), V(1));
+  } else {
+    return fp2_sub2(V(5), V(2), V(1));
+  }
+}
+// M phase, f <- f M from V0..16 (see mf_mul_pair): t0 = a M0 from V0..5 (m0 = V4, m1 = V3,
+// m2 = V5), n = b (m4 + m5 v): n0 = V6 + xi V10, n1 = V8 - V6 - V7, n2 = V7 + V9, t2 = s q from
+// V11..16 (m0 = V15, m1 = V14, m2 = V16).  J = 0..2: f'.c0.J = (t0 + v (v n))_J, i.e.
+// t0_0 + xi n1, t0_1 + xi n2, t0_2 + n0;  J = 3..5: f'.c1.(J-3) = (t2 - t0 - v n)_(J-3), i.e.
+// t2_0 - t0_0 - xi n2, t2_1 - t0_1 - n0, t2_2 - t0_2 - n1.
+template <int J, class G>
+LSG_INL fp2_t mfc_mul(const G& V) {
+  if constexpr (J == 0) {  // V0 + xi (V4 - V1 - V2 + V8 - V6 - V7)
+    const fp2_t g = (fp2s(V(4)) - V(1) - V(2) + V(8)).carry();
+    const fp2_t h = (fp2s(g) - V(6) - V(7)).carry();
+    return (fp2s(V(0)) + fp2s_mul_xi(h)).carry();
+  } else if constexpr (J == 1) {  // V3 - V0 - V1 + xi (V2 + V7 + V9)
+    const fp2_t h = (fp2s(V(2)) + V(7) + V(9)).carry();
+    return ((fp2s(V(3)) - V(0) - V(1)) + fp2s_mul_xi(h)).carry();
+  } else if constexpr (J == 2) {  // V5 - V0 - V2 + V1 + V6 + xi V10
+    const fp2_t n0 = (fp2s(V(6)) + fp2s_mul_xi(V(10))).carry();
+    return (fp2s(V(5)) - V(0) - V(2) + V(1) + n0).carry();
+  } else if constexpr (J == 3) {  // V11 - V0 + xi (V15 - V12 - V13 - V4 + V1 + V2 - V7 - V9)
+    const fp2_t g = (fp2s(V(15)) - V(12) - V(13) + V(1) + V(2)).carry();
+    const fp2_t h = (fp2s(g) - V(4) - V(7) - V(9)).carry();
+    return (fp2s(V(11)) - V(0) + fp2s_mul_xi(h)).carry();
+  } else if constexpr (J == 4) {  // (V14 - V11 - V12) - (V3 - V0 - V1) - V6 + xi (V13 - V2 - V10)
+    const fp2_t a = ((fp2s(V(14)) - V(11) - V(12)) - (fp2s(V(3)) - V(0) - V(1))).carry();
+    const fp2_t b = fp2_sub2(V(13), V(2), V(10));
+    return (fp2s(a) - V(6) + fp2s_mul_xi(b)).carry();
+  } else {  // V16 + V12 + V0 + V2 + V6 + V7 - V11 - V13 - V5 - V1 - V8
+    const fp2_t g = (fp2s(V(11)) + V(13) + V(5) - V(16) - V(12) - V(0)).carry();
+    return (fp2s(V(2)) + V(6) + V(7) - V(1) - V(8) - g).carry();
+  }
 }
 
 #ifdef LSG_ROW_SPLIT

@@ -86,12 +86,74 @@ LSG_BIGFN fp_t fp_pow_id(fp_t a, int id) {
 
 LSG_INL fp_t fp_inv(const fp_t& a) { return fp_pow_id(a, LSG_POW_INV); }  // inv(0) = 0
 
-LSG_INL fp_t fp_mul12(const fp_t& a) {
-  fp_t a2 = fp_dbl(a);
-  fp_t a4 = fp_dbl(a2);
-  fp_t a8 = fp_dbl(a4);
-  return fp_add(a8, a4);
+// ------------------------------------------------------------------ lazy sums
+// Linear combinations are written as sums whose carry (or reduction) is explicit:
+//   fps(a) lifts an fp_t; +, -, unary - and fps_mulk<K> combine sums; .carry() returns the
+//   fp_t; .carry_mul<K>() returns K times the sum (K = 2, 3, 4, 8, 12).
+// fps_t<P, N> counts the values added (P) and subtracted (N).  The pair backend
+// (lsg_fp_pair.hpp) keeps such a sum uncarried and pays one carry round at carry(); its bound
+// rule (P <= 3, N <= 3 per carry, and the admissible small multiples) is a static_assert
+// there.  Every other backend, and the pair backend under -DLSG_EAGER_SUMS, gets the
+// definitions below: each operation is the backend's own fp_add / fp_sub / fp_neg, carry() is
+// the identity -- the values and the operation order of the eager formulas -- under the same
+// static rule, so code that compiles here compiles for the lazy backend.
+#ifndef LSG_SUM_RULE
+constexpr bool fps_carry_ok(int P, int N) { return P <= 3 && N <= 3; }
+constexpr bool fps_carry_mul_ok(int K, int P, int N) {
+  return (K == 2 && P <= 3 && N <= 3) || (K == 4 && P <= 3 && N <= 1) || (K == 8 && P <= 2 && N == 0) ||
+         (K == 3 && P + N == 1) || (K == 12 && P == 1 && N == 0);  // what lsg_fp_pair.hpp's bounds admit
 }
+#endif
+#ifndef LSG_LAZY_SUMS
+template <int P, int N>
+struct fps_t {
+  fp_t v;
+  LSG_INL fp_t carry() const {
+    static_assert(fps_carry_ok(P, N), "lazy sum too long for one carry round: carry a group first (P <= 3, N <= 3)");
+    return v;
+  }
+  template <int K>
+  LSG_INL fp_t carry_mul() const {
+    static_assert(fps_carry_mul_ok(K, P, N), "small multiple of this sum does not come out carried: carry() first");
+    const fp_t a2 = fp_dbl(v);
+    if (K == 2) return a2;
+    if (K == 3) return fp_add(a2, v);
+    const fp_t a4 = fp_dbl(a2);
+    if (K == 4) return a4;
+    const fp_t a8 = fp_dbl(a4);
+    return K == 8 ? a8 : fp_add(a8, a4);
+  }
+};
+LSG_INL fps_t<1, 0> fps(const fp_t& a) { return fps_t<1, 0>{a}; }
+template <int P, int N, int Q, int M>
+LSG_INL fps_t<P + Q, N + M> operator+(const fps_t<P, N>& a, const fps_t<Q, M>& b) {
+  return fps_t<P + Q, N + M>{fp_add(a.v, b.v)};
+}
+template <int P, int N, int Q, int M>
+LSG_INL fps_t<P + M, N + Q> operator-(const fps_t<P, N>& a, const fps_t<Q, M>& b) {
+  return fps_t<P + M, N + Q>{fp_sub(a.v, b.v)};
+}
+template <int P, int N>
+LSG_INL fps_t<N, P> operator-(const fps_t<P, N>& a) {
+  return fps_t<N, P>{fp_neg(a.v)};
+}
+template <int K, int P, int N>
+LSG_INL fps_t<K * P, K * N> fps_mulk(const fps_t<P, N>& a) {
+  static_assert(K >= 1 && K <= 3, "uncarried small multiples up to 3");
+  const fp_t a2 = fp_dbl(a.v);
+  return fps_t<K * P, K * N>{K == 1 ? a.v : K == 2 ? a2 : fp_add(a2, a.v)};
+}
+#endif
+template <int P, int N>
+LSG_INL fps_t<P + 1, N> operator+(const fps_t<P, N>& a, const fp_t& b) { return a + fps(b); }
+template <int P, int N>
+LSG_INL fps_t<P, N + 1> operator-(const fps_t<P, N>& a, const fp_t& b) { return a - fps(b); }
+// K a, carried, in one pass (the pair backend: 3-4 instructions per limb instead of a chain
+// of carried additions)
+template <int K>
+LSG_INL fp_t fp_mulk(const fp_t& a) { return fps(a).template carry_mul<K>(); }
+
+LSG_INL fp_t fp_mul12(const fp_t& a) { return fp_mulk<12>(a); }
 
 // ------------------------------------------------------------------ Fp2
 struct fp2_t {
@@ -120,6 +182,59 @@ LSG_INL fp2_t fp2_sub(const fp2_t& a, const fp2_t& b) { return fp2_t(fp_sub(a.c0
 LSG_INL fp2_t fp2_dbl(const fp2_t& a) { return fp2_add(a, a); }
 LSG_INL fp2_t fp2_neg(const fp2_t& a) { return fp2_t(fp_neg(a.c0), fp_neg(a.c1)); }
 LSG_INL fp2_t fp2_conj(const fp2_t& a) { return fp2_t(a.c0, fp_neg(a.c1)); }
+
+// ---- lazy sums over Fp2: one fps_t per component, the counts kept apart because the
+// product by xi = 1 + u mixes them: (c0 - c1) + (c0 + c1) u
+template <int P0, int N0, int P1 = P0, int N1 = N0>
+struct fp2s_t {
+  fps_t<P0, N0> c0;
+  fps_t<P1, N1> c1;
+  LSG_INL fp2_t carry() const { return fp2_t(c0.carry(), c1.carry()); }
+  template <int K>
+  LSG_INL fp2_t carry_mul() const {
+    return fp2_t(c0.template carry_mul<K>(), c1.template carry_mul<K>());
+  }
+};
+LSG_INL fp2s_t<1, 0> fp2s(const fp2_t& a) { return fp2s_t<1, 0>{fps(a.c0), fps(a.c1)}; }
+template <int P0, int N0, int P1, int N1, int Q0, int M0, int Q1, int M1>
+LSG_INL fp2s_t<P0 + Q0, N0 + M0, P1 + Q1, N1 + M1> operator+(const fp2s_t<P0, N0, P1, N1>& a,
+                                                            const fp2s_t<Q0, M0, Q1, M1>& b) {
+  return fp2s_t<P0 + Q0, N0 + M0, P1 + Q1, N1 + M1>{a.c0 + b.c0, a.c1 + b.c1};
+}
+template <int P0, int N0, int P1, int N1, int Q0, int M0, int Q1, int M1>
+LSG_INL fp2s_t<P0 + M0, N0 + Q0, P1 + M1, N1 + Q1> operator-(const fp2s_t<P0, N0, P1, N1>& a,
+                                                            const fp2s_t<Q0, M0, Q1, M1>& b) {
+  return fp2s_t<P0 + M0, N0 + Q0, P1 + M1, N1 + Q1>{a.c0 - b.c0, a.c1 - b.c1};
+}
+template <int P0, int N0, int P1, int N1>
+LSG_INL fp2s_t<N0, P0, N1, P1> operator-(const fp2s_t<P0, N0, P1, N1>& a) {
+  return fp2s_t<N0, P0, N1, P1>{-a.c0, -a.c1};
+}
+template <int P0, int N0, int P1, int N1>
+LSG_INL fp2s_t<P0 + 1, N0, P1 + 1, N1> operator+(const fp2s_t<P0, N0, P1, N1>& a, const fp2_t& b) {
+  return a + fp2s(b);
+}
+template <int P0, int N0, int P1, int N1>
+LSG_INL fp2s_t<P0, N0 + 1, P1, N1 + 1> operator-(const fp2s_t<P0, N0, P1, N1>& a, const fp2_t& b) {
+  return a - fp2s(b);
+}
+template <int K, int P0, int N0, int P1, int N1>
+LSG_INL fp2s_t<K * P0, K * N0, K * P1, K * N1> fp2s_mulk(const fp2s_t<P0, N0, P1, N1>& a) {
+  return fp2s_t<K * P0, K * N0, K * P1, K * N1>{fps_mulk<K>(a.c0), fps_mulk<K>(a.c1)};
+}
+template <int P0, int N0, int P1, int N1>
+LSG_INL fp2s_t<P0 + N1, N0 + P1, P0 + P1, N0 + N1> fp2s_mul_xi(const fp2s_t<P0, N0, P1, N1>& a) {
+  return fp2s_t<P0 + N1, N0 + P1, P0 + P1, N0 + N1>{a.c0 - a.c1, a.c0 + a.c1};
+}
+LSG_INL fp2s_t<1, 1, 2, 0> fp2s_mul_xi(const fp2_t& a) { return fp2s_mul_xi(fp2s(a)); }
+template <int P0, int N0, int P1, int N1>
+LSG_INL fp2s_t<P0, N0, N1, P1> fp2s_conj(const fp2s_t<P0, N0, P1, N1>& a) {
+  return fp2s_t<P0, N0, N1, P1>{a.c0, -a.c1};
+}
+template <int K>
+LSG_INL fp2_t fp2_mulk(const fp2_t& a) { return fp2_t(fp_mulk<K>(a.c0), fp_mulk<K>(a.c1)); }
+// a - b - c with one carry per component
+LSG_INL fp2_t fp2_sub2(const fp2_t& a, const fp2_t& b, const fp2_t& c) { return (fp2s(a) - b - c).carry(); }
 
 // Karatsuba: 3 Fp multiplications
 LSG_INL fp2_t fp2_mul(const fp2_t& a, const fp2_t& b) {
@@ -210,7 +325,7 @@ LSG_INL void fp2_sqr_n(fp2_t* r, const fp2_t* a) {
 }
 
 // (a0 + a1 u)(1 + u) = (a0 - a1) + (a0 + a1) u
-LSG_INL fp2_t fp2_mul_xi(const fp2_t& a) { return fp2_t(fp_sub(a.c0, a.c1), fp_add(a.c0, a.c1)); }
+LSG_INL fp2_t fp2_mul_xi(const fp2_t& a) { return fp2s_mul_xi(a).carry(); }
 
 LSG_INL fp_t fp2_norm(const fp2_t& a) {
 #ifdef LSG_SQR_LEAF
@@ -228,10 +343,7 @@ LSG_INL fp2_t fp2_inv(const fp2_t& a) {
 }
 
 // 12 a (for b3 = 3 * 4(1+u))
-LSG_INL fp2_t fp2_mul_b3(const fp2_t& a) {
-  fp2_t t = fp2_mul_xi(a);
-  return fp2_t(fp_mul12(t.c0), fp_mul12(t.c1));
-}
+LSG_INL fp2_t fp2_mul_b3(const fp2_t& a) { return fp2_mulk<12>(fp2_mul_xi(a)); }
 
 // RFC 9380 sgn0 for Fp2 (a in Montgomery form)
 LSG_INL uint32_t fp2_sgn0(const fp2_t& a) {
@@ -315,26 +427,62 @@ LSG_INL void fp6_mul_prep(fp2_t* A, fp2_t* B, const fp6_t& a, const fp6_t& b) {
   A[5] = fp2_add(a.c0, a.c2);
   B[5] = fp2_add(b.c0, b.c2);
 }
+// The three output coefficients of the Karatsuba Fp6 product from v0 = a0 b0, v1 = a1 b1,
+// v2 = a2 b2 and m0 = (a1 + a2)(b1 + b2), m1 = (a0 + a1)(b0 + b1), m2 = (a0 + a2)(b0 + b2), as
+// sums for the caller to extend or carry:
+//   c0 = v0 + xi (m0 - v1 - v2)   (the inner difference carried: xi would make it <2, 4>)
+//   c1 = m1 - v0 - v1 + xi v2,    c2 = m2 - v0 - v2 + v1
+LSG_INL fp2s_t<2, 1, 3, 0> fp6_kar_s0(const fp2_t& v0, const fp2_t& v1, const fp2_t& v2, const fp2_t& m0) {
+  return fp2s(v0) + fp2s_mul_xi(fp2_sub2(m0, v1, v2));
+}
+LSG_INL fp2s_t<2, 3, 3, 2> fp6_kar_s1(const fp2_t& v0, const fp2_t& v1, const fp2_t& v2, const fp2_t& m1) {
+  return (fp2s(m1) - v0 - v1) + fp2s_mul_xi(v2);
+}
+LSG_INL fp2s_t<2, 2> fp6_kar_s2(const fp2_t& v0, const fp2_t& v1, const fp2_t& v2, const fp2_t& m2) {
+  return (fp2s(m2) - v0 - v2) + v1;
+}
 LSG_INL fp6_t fp6_mul_fin(const fp2_t* V) {
-  fp2_t c0 = fp2_add(V[0], fp2_mul_xi(fp2_sub(fp2_sub(V[3], V[1]), V[2])));
-  fp2_t c1 = fp2_add(fp2_sub(fp2_sub(V[4], V[0]), V[1]), fp2_mul_xi(V[2]));
-  fp2_t c2 = fp2_add(fp2_sub(fp2_sub(V[5], V[0]), V[2]), V[1]);
   fp6_t r;
-  r.c0 = c0;
-  r.c1 = c1;
-  r.c2 = c2;
+  r.c0 = fp6_kar_s0(V[0], V[1], V[2], V[3]).carry();
+  r.c1 = fp6_kar_s1(V[0], V[1], V[2], V[4]).carry();
+  r.c2 = fp6_kar_s2(V[0], V[1], V[2], V[5]).carry();
+  return r;
+}
+// a - b - c and a + v b, one carry per component
+LSG_INL fp6_t fp6_sub2(const fp6_t& a, const fp6_t& b, const fp6_t& c) {
+  fp6_t r;
+  r.c0 = fp2_sub2(a.c0, b.c0, c.c0);
+  r.c1 = fp2_sub2(a.c1, b.c1, c.c1);
+  r.c2 = fp2_sub2(a.c2, b.c2, c.c2);
+  return r;
+}
+LSG_INL fp6_t fp6_add_mul_v(const fp6_t& a, const fp6_t& b) {
+  fp6_t r;
+  r.c0 = (fp2s(a.c0) + fp2s_mul_xi(b.c2)).carry();
+  r.c1 = fp2_add(a.c1, b.c0);
+  r.c2 = fp2_add(a.c2, b.c1);
   return r;
 }
 #ifdef LSG_LEAN_TOWER
 // Quad backend: an Fp takes three VGPRs, so the products are issued one Fp2 product (three
 // interleaved Montgomery chains) at a time instead of in wide batches; same values.
+// SUMS = false: the combinations one carried operation at a time (same values).  A call site
+// whose kernel would otherwise gain scratch asks for it: k_fp12_pow_u64 (lsg_k_reduce.hip).
+template <bool SUMS = true>
 LSG_BIGFN fp6_t fp6_mul(fp6_t a, fp6_t b) {
   fp2_t v0 = fp2_mul(a.c0, b.c0);
   fp2_t v1 = fp2_mul(a.c1, b.c1);
   fp2_t v2 = fp2_mul(a.c2, b.c2);
-  fp2_t c0 = fp2_add(v0, fp2_mul_xi(fp2_sub(fp2_sub(fp2_mul(fp2_add(a.c1, a.c2), fp2_add(b.c1, b.c2)), v1), v2)));
-  fp2_t c1 = fp2_add(fp2_sub(fp2_sub(fp2_mul(fp2_add(a.c0, a.c1), fp2_add(b.c0, b.c1)), v0), v1), fp2_mul_xi(v2));
-  fp2_t c2 = fp2_add(fp2_sub(fp2_sub(fp2_mul(fp2_add(a.c0, a.c2), fp2_add(b.c0, b.c2)), v0), v2), v1);
+  fp2_t c0, c1, c2;
+  if (SUMS) {
+    c0 = fp6_kar_s0(v0, v1, v2, fp2_mul(fp2_add(a.c1, a.c2), fp2_add(b.c1, b.c2))).carry();
+    c1 = fp6_kar_s1(v0, v1, v2, fp2_mul(fp2_add(a.c0, a.c1), fp2_add(b.c0, b.c1))).carry();
+    c2 = fp6_kar_s2(v0, v1, v2, fp2_mul(fp2_add(a.c0, a.c2), fp2_add(b.c0, b.c2))).carry();
+  } else {
+    c0 = fp2_add(v0, fp2_mul_xi(fp2_sub(fp2_sub(fp2_mul(fp2_add(a.c1, a.c2), fp2_add(b.c1, b.c2)), v1), v2)));
+    c1 = fp2_add(fp2_sub(fp2_sub(fp2_mul(fp2_add(a.c0, a.c1), fp2_add(b.c0, b.c1)), v0), v1), fp2_mul_xi(v2));
+    c2 = fp2_add(fp2_sub(fp2_sub(fp2_mul(fp2_add(a.c0, a.c2), fp2_add(b.c0, b.c2)), v0), v2), v1);
+  }
   return fp6_make(c0, c1, c2);
 }
 #else
@@ -352,8 +500,8 @@ LSG_INL fp6_t fp6_mul_v(const fp6_t& a) { return fp6_make(fp2_mul_xi(a.c2), a.c0
 LSG_BIGFN fp6_t fp6_mul_01(fp6_t a, fp2_t b0, fp2_t b1) {
   fp2_t t0 = fp2_mul(a.c0, b0);
   fp2_t t1 = fp2_mul(a.c1, b1);
-  fp2_t c0 = fp2_add(fp2_mul_xi(fp2_mul(a.c2, b1)), t0);
-  fp2_t c1 = fp2_sub(fp2_sub(fp2_mul(fp2_add(a.c0, a.c1), fp2_add(b0, b1)), t0), t1);
+  fp2_t c0 = (fp2s_mul_xi(fp2_mul(a.c2, b1)) + t0).carry();
+  fp2_t c1 = fp2_sub2(fp2_mul(fp2_add(a.c0, a.c1), fp2_add(b0, b1)), t0, t1);
   fp2_t c2 = fp2_add(fp2_mul(a.c2, b0), t1);
   return fp6_make(c0, c1, c2);
 }
@@ -387,16 +535,28 @@ LSG_INL bool fp12_is_one(const fp12_t& a) {
 LSG_INL fp12_t fp12_conj(const fp12_t& a) { return fp12_make(a.c0, fp6_neg(a.c1)); }
 
 #ifdef LSG_LEAN_TOWER
+template <bool SUMS = true>
 LSG_BIGFN fp12_t fp12_mul(fp12_t a, fp12_t b) {
-  fp6_t t0 = fp6_mul(a.c0, b.c0);
-  fp6_t t1 = fp6_mul(a.c1, b.c1);
-  fp6_t t2 = fp6_mul(fp6_add(a.c0, a.c1), fp6_add(b.c0, b.c1));
-  return fp12_make(fp6_add(t0, fp6_mul_v(t1)), fp6_sub(fp6_sub(t2, t0), t1));
+  fp6_t t0 = fp6_mul<SUMS>(a.c0, b.c0);
+  fp6_t t1 = fp6_mul<SUMS>(a.c1, b.c1);
+  fp6_t t2 = fp6_mul<SUMS>(fp6_add(a.c0, a.c1), fp6_add(b.c0, b.c1));
+  if (!SUMS) return fp12_make(fp6_add(t0, fp6_mul_v(t1)), fp6_sub(fp6_sub(t2, t0), t1));
+  return fp12_make(fp6_add_mul_v(t0, t1), fp6_sub2(t2, t0, t1));
 }
+template <bool SUMS = true>
 LSG_BIGFN fp12_t fp12_sqr(fp12_t a) {
-  fp6_t t = fp6_mul(a.c0, a.c1);
-  fp6_t u = fp6_mul(fp6_add(a.c0, a.c1), fp6_add(a.c0, fp6_mul_v(a.c1)));
-  return fp12_make(fp6_sub(fp6_sub(u, t), fp6_mul_v(t)), fp6_add(t, t));
+  fp6_t t = fp6_mul<SUMS>(a.c0, a.c1);
+  if (!SUMS) {
+    fp6_t e = fp6_mul<SUMS>(fp6_add(a.c0, a.c1), fp6_add(a.c0, fp6_mul_v(a.c1)));
+    return fp12_make(fp6_sub(fp6_sub(e, t), fp6_mul_v(t)), fp6_add(t, t));
+  }
+  fp6_t u = fp6_mul<SUMS>(fp6_add(a.c0, a.c1), fp6_add_mul_v(a.c0, a.c1));
+  // c0 = u - t - v t (one carry per component), c1 = 2t
+  fp6_t c0;
+  c0.c0 = (fp2s(u.c0) - t.c0 - fp2s_mul_xi(t.c2)).carry();
+  c0.c1 = fp2_sub2(u.c1, t.c1, t.c0);
+  c0.c2 = fp2_sub2(u.c2, t.c2, t.c1);
+  return fp12_make(c0, fp6_make(fp2_mulk<2>(t.c0), fp2_mulk<2>(t.c1), fp2_mulk<2>(t.c2)));
 }
 #else
 // Karatsuba over Fp6: the three Fp6 products (18 Fp2 products) are issued as one batch
@@ -425,8 +585,8 @@ LSG_BIGFN fp12_t fp12_sqr(fp12_t a) {
 LSG_INL void fp4_square(fp2_t& c0, fp2_t& c1, const fp2_t& a, const fp2_t& b) {
   fp2_t t0 = fp2_sqr(a);
   fp2_t t1 = fp2_sqr(b);
-  c0 = fp2_add(fp2_mul_xi(t1), t0);
-  c1 = fp2_sub(fp2_sub(fp2_sqr(fp2_add(a, b)), t0), t1);
+  c0 = (fp2s_mul_xi(t1) + t0).carry();
+  c1 = fp2_sub2(fp2_sqr(fp2_add(a, b)), t0, t1);
 }
 
 // Granger-Scott squaring for f in the cyclotomic subgroup -- oracle/pairing.py:f12_cyclotomic_sqr
@@ -490,7 +650,7 @@ LSG_BIGFN fp12_t fp12_mul_line(fp12_t f, fp2_t l00, fp2_t l01, fp2_t l11) {
   fp6_t t0 = fp6_mul_01(f.c0, l00, l01);
   fp6_t u = fp6_mul_01(fp6_add(f.c0, f.c1), l00, fp2_add(l01, l11));
   fp6_t t1 = fp6_mul_1(f.c1, l11);
-  return fp12_make(fp6_add(t0, fp6_mul_v(t1)), fp6_sub(fp6_sub(u, t0), t1));
+  return fp12_make(fp6_add_mul_v(t0, t1), fp6_sub2(u, t0, t1));
 #else
   const fp6_t& a = f.c0;
   const fp6_t& c = f.c1;
