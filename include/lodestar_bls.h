@@ -249,6 +249,48 @@ int lsg_jobs_partial(lsg_ctx* ctx, lsg_ticket ticket, uint8_t* out576, int32_t* 
 int lsg_jobs_partial_device(lsg_ctx* ctx, lsg_ticket ticket, void* dev_out576, int32_t* has_batch);
 int lsg_wait_jobs_node(lsg_ctx* ctx, lsg_ticket ticket, int32_t node_valid, lsg_job_result* results,
                        lsg_stats* stats);
+/* A package that also returns, per caller-named group, the compressed sum of the signatures of
+ * the sets that verified: the op pools merge one 96-byte aggregate per
+ * (package, key) instead of decoding and adding one signature per attestation
+ * (opPools/attestationPool.ts:182-199).  lsg_set and lsg_job keep their layout; set_group has
+ * one word per set, in job order and then set order.
+ *   Values.  set_group[i] is below n_groups, or LSG_NO_GROUP for a set that joins no group.
+ *     Any other value is a caller bug: LSG_ERR_INVALID_ARG before a slot is taken, and the
+ *     context stays usable.  set_group == NULL or n_groups == 0 is exactly lsg_submit_jobs: it
+ *     stages, allocates and launches what that call does.
+ *   Included sets.  A set is included exactly when its job resolves to LSG_VALID: a multi-set
+ *     job is all or nothing, as its verdict is; a package rejected by a key error includes
+ *     nothing.
+ *   Aggregate.  agg96[g] is the ZCash-compressed sum of the included signatures of group g
+ *     (Signature.aggregate(sigs).toBytes()): the same point, hence the same bytes, as
+ *     lsg_aggregate_signatures over those signatures.  A sum at infinity is 0xc0 || 0^95.
+ *   Count.  agg_n[g] is how many signatures were summed.  With none included agg_n[g] = 0 and
+ *     agg96[g] is 96 zero bytes.
+ *   Duplicates.  A signature listed twice is added twice (the caller's business, as in
+ *     Signature.aggregate).  96- and 192-byte signatures may share a group.
+ *   Nothing else changes.  For a given seed, verdicts, error codes, their precedence, the batch
+ *     counters, lsg_stats and the exported partial are those of the same package through
+ *     lsg_submit_jobs.
+ *   Mixing wait calls.  lsg_wait_jobs on a grouped ticket resolves it and drops the aggregates
+ *     (as lsg_wait_jobs_grouped with agg96 or agg_n NULL does); lsg_wait_jobs_grouped on a plain
+ *     ticket writes no aggregate; lsg_poll works.  lsg_wait_jobs_grouped is the node_valid = -1
+ *     form only.
+ *   Scope.  A grouped package launches on its own: it is never held by lsg_set_coalesce and
+ *     does not flush what that holds, exactly as the packages of lsg_verify_deposits behave.
+ *     On a context over several devices a submit with n_groups > 0 returns
+ *     LSG_ERR_INVALID_ARG (a group can span devices; lsg_batch_partial and coalescing are
+ *     single-device too).
+ *   Allocation.  The per-slot buffers (group ids, gather list and chunk plan, projective sums,
+ *     96 * n_groups bytes of output) are allocated by the first grouped package.  lsg_reserve
+ *     sizes them for max_sets sets and max_sets groups once the context has seen a grouped
+ *     submit: the caller reserves again after that (the committee bit arena's rule), and a
+ *     reserved context within those bounds then allocates nothing.  A context that never groups
+ *     allocates what it did before. */
+#define LSG_NO_GROUP 0xffffffffu
+int lsg_submit_jobs_grouped(lsg_ctx* ctx, const lsg_job* jobs, size_t n_jobs, uint64_t seed,
+                            const uint32_t* set_group, size_t n_groups, lsg_ticket* ticket);
+int lsg_wait_jobs_grouped(lsg_ctx* ctx, lsg_ticket ticket, lsg_job_result* results, lsg_stats* stats,
+                          uint8_t* agg96 /* n_groups x 96 */, uint32_t* agg_n /* n_groups */);
 /* Coalescing of small packages (single-device contexts; off by default).  From this call on,
  * a package of at most max_sets sets submitted with lsg_submit_jobs is copied (the caller's
  * buffers are free on return) and, while max_inflight launches are on the device, held back;

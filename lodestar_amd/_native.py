@@ -175,6 +175,7 @@ EXPORTS = [
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
     "lsg_object_signing_roots",
+    "lsg_submit_jobs_grouped", "lsg_wait_jobs_grouped",
 ]
 
 
@@ -220,6 +221,9 @@ def load_library(path=LIB_PATH):
         pu64 = ctypes.POINTER(u64)
         lib.lsg_submit_jobs.argtypes = [vp, ctypes.POINTER(LsgJob), sz, u64, pu64]
         lib.lsg_wait_jobs.argtypes = [vp, u64, ctypes.POINTER(LsgJobResult), ctypes.POINTER(LsgStats)]
+        lib.lsg_submit_jobs_grouped.argtypes = [vp, ctypes.POINTER(LsgJob), sz, u64, ctypes.POINTER(u32), sz, pu64]
+        lib.lsg_wait_jobs_grouped.argtypes = [vp, u64, ctypes.POINTER(LsgJobResult), ctypes.POINTER(LsgStats),
+                                              ctypes.c_char_p, ctypes.POINTER(u32)]
         lib.lsg_poll.argtypes = [vp, u64, pi32]
         lib.lsg_pubkey_table_set.argtypes = [vp, sz, ctypes.c_char_p, u32, sz, pi32]
         lib.lsg_pubkey_table_size.argtypes = [vp, ctypes.POINTER(sz)]
@@ -349,6 +353,14 @@ class PreparedJobs:
             jv["flags"][:len(jobs)] = [f for _, f in jobs]
 
 
+LSG_NO_GROUP = 0xFFFFFFFF
+
+
+class GroupedTicket(tuple):
+    """(ticket, n_jobs) of a grouped package (Context.submit_jobs with groups); n_groups rides along"""
+    n_groups = 0
+
+
 class Context:
     """A device context (lsg_ctx) over `device`, or over the list `devices` (lsg_init_devices).
     Raises NativeUnavailable without a gfx950 GPU."""
@@ -418,16 +430,50 @@ class Context:
             raise RuntimeError("lsg_submit_jobs: every pipeline slot is busy")
         return self.wait_jobs(t)
 
-    def submit_jobs(self, jobs, seed=0):
+    def submit_jobs(self, jobs, seed=0, groups=None, n_groups=0):
         """Asynchronous verify_jobs: returns a ticket for wait_jobs, or None when every
-        pipeline slot is busy (LSG_ERR_BUSY).  The inputs are copied before returning."""
+        pipeline slot is busy (LSG_ERR_BUSY).  The inputs are copied before returning.
+        groups: one group id per set (job order, then set order; LSG_NO_GROUP: none) below
+        n_groups -- lsg_submit_jobs_grouped, resolved by wait_jobs_grouped."""
         p = jobs if isinstance(jobs, PreparedJobs) else PreparedJobs(jobs)
         t = ctypes.c_uint64()
-        rc = self.lib.lsg_submit_jobs(self.h, p.jobs, p.n_jobs, seed, ctypes.byref(t))
+        if groups is None or n_groups == 0:
+            rc = self.lib.lsg_submit_jobs(self.h, p.jobs, p.n_jobs, seed, ctypes.byref(t))
+            if rc == LSG_ERR_BUSY:
+                return None
+            self._check(rc, "lsg_submit_jobs")
+            return (t.value, p.n_jobs)
+        if len(groups) != p.n_sets:
+            raise ValueError(f"groups: {len(groups)} ids for {p.n_sets} sets")
+        ids = (ctypes.c_uint32 * max(p.n_sets, 1))(*[int(g) for g in groups])
+        rc = self.lib.lsg_submit_jobs_grouped(self.h, p.jobs, p.n_jobs, seed, ids, int(n_groups), ctypes.byref(t))
         if rc == LSG_ERR_BUSY:
             return None
-        self._check(rc, "lsg_submit_jobs")
-        return (t.value, p.n_jobs)
+        self._check(rc, "lsg_submit_jobs_grouped")
+        ticket = GroupedTicket((t.value, p.n_jobs))
+        ticket.n_groups = int(n_groups)
+        return ticket
+
+    def wait_jobs_grouped(self, ticket):
+        """lsg_wait_jobs_grouped -> (per-job (status, err_code), stats, [(bytes96, count)] per group:
+        the compressed sum of the signatures of the sets whose job is LSG_VALID).  A plain ticket
+        gives an empty list."""
+        t, n = ticket
+        ng = getattr(ticket, "n_groups", 0)
+        res = (LsgJobResult * max(n, 1))()
+        st = LsgStats()
+        agg = ctypes.create_string_buffer(96 * max(ng, 1))
+        cnt = (ctypes.c_uint32 * max(ng, 1))()
+        self._check(self.lib.lsg_wait_jobs_grouped(self.h, t, res, ctypes.byref(st), agg, cnt), "lsg_wait_jobs_grouped")
+        out, stats = self._results(res, st, n)
+        return out, stats, [(agg.raw[96 * g:96 * g + 96], int(cnt[g])) for g in range(ng)]
+
+    def verify_jobs_grouped(self, jobs, groups, n_groups, seed=0):
+        """submit_jobs(groups=...) + wait_jobs_grouped"""
+        t = self.submit_jobs(jobs, seed=seed, groups=groups, n_groups=n_groups)
+        if t is None:
+            raise RuntimeError("lsg_submit_jobs_grouped: every pipeline slot is busy")
+        return self.wait_jobs_grouped(t)
 
     @staticmethod
     def _results(res, st, n):

@@ -274,6 +274,16 @@ struct Slot {
   std::vector<uint8_t> sub_done;
   bool resolved = false, resolving = false;
   int resolve_rc = LSG_OK;
+  // per-group sums of the verified signatures (lsg_submit_jobs_grouped):
+  // grp_n groups (0: a plain package), set_grp[i] = staged set i's group.  The plan (gather
+  // list + chunks) has an arena of its own -- the fallback phases rewrite `plan` -- and every
+  // buffer here is allocated by the first grouped package (or lsg_reserve after it).
+  size_t grp_n = 0;
+  std::vector<uint32_t> set_grp;
+  std::vector<int32_t> gplan;
+  SigGroupPlan sgp;
+  HostBuf h_gplan, h_gagg;
+  DevBuf d_gplan, d_gsum, d_gagg, d_gtmp[2];
 };
 
 struct Dev {
@@ -333,6 +343,7 @@ struct lsg_ctx {
   std::vector<PendingPkg> pending;
   size_t pending_sets = 0;
   std::unordered_map<uint64_t, MergeTicket> merged;
+  bool grouped_seen = false;  // a grouped package was submitted: lsg_reserve sizes the group buffers too
   int n_dev = 0;
   Dev* dev[LSG_MAX_DEVICES] = {};
   bool rccl = false;  // several distinct devices: the partials are all-gathered over RCCL
@@ -537,12 +548,13 @@ void slot_destroy(Slot* s) {
                     &s->d_Sb,   &s->d_fgb,    &s->d_Fb,   &s->d_bkt,    &s->d_bits,   &s->d_aux,   &s->d_gath,
                     &s->d_nodeF, &s->d_nodeV, &s->d_plan, &s->d_mid, &s->d_Hm, &s->d_hinfm,
                     &s->d_mmask, &s->d_PmP, &s->d_Pm, &s->d_pinfm, &s->d_errm, &s->d_xport,
-                    &s->d_agga, &s->d_aggi, &s->d_aggpre, &s->d_aggtot, &s->d_aggflag, &s->d_cbits};
+                    &s->d_agga, &s->d_aggi, &s->d_aggpre, &s->d_aggtot, &s->d_aggflag, &s->d_cbits,
+                    &s->d_gplan, &s->d_gsum, &s->d_gagg, &s->d_gtmp[0], &s->d_gtmp[1]};
   for (DevBuf* b : bufs) free_dev(*b);
   for (auto& u : s->seg_tmp)
     for (DevBuf& b : u) free_dev(b);
   HostBuf* hb[] = {&s->h_arena, &s->h_err, &s->h_pinf, &s->h_pkerr, &s->h_verdict, &s->h_blob, &s->h_plan, &s->h_nodeV,
-                   &s->h_xport, &s->h_cbits};
+                   &s->h_xport, &s->h_cbits, &s->h_gplan, &s->h_gagg};
   for (HostBuf* b : hb) free_host(*b);
   for (Timer& t : s->timers) {
     (void)hipEventDestroy(t.a);
@@ -807,6 +819,58 @@ int run_pk_seg(Slot* s, const SegPlan& P, uint32_t* dst) {
       KL(s, "g1_aggregate", lsgk::seg_reduce(S_(s), 0, q.n_chunks, q.ips_log2, PL(s, q.chunk_off), nullptr,
                                              tmp[q.src], dst, tmp[q.tmp_out]));
   }
+  return LSG_OK;
+}
+
+// ---- per-group sums of the verified signatures (lsg_submit_jobs_grouped)
+// buffers for n sets in ng groups: the plan arena (the gather list, at most n words plus n / 8
+// of padding, and three words per chunk: one per group or per SEG_FOLD members in the first
+// pass, fewer in the second), the chunk sums of groups longer than a chunk, the projective sums and the output
+int size_groups(Slot* s, size_t n, size_t ng) {
+  const size_t words = 2 * n + 3 * ng + 64, tmp_items = n / 8 + 64;
+  LSG_RC(ensure_host(s, s->h_gplan, 4 * words));
+  LSG_RC(ensure(s, s->d_gplan, 4 * words));
+  for (DevBuf& b : s->d_gtmp) LSG_RC(ensure(s, b, 4 * W_G2P * tmp_items));
+  LSG_RC(ensure(s, s->d_gsum, 4 * W_G2P * std::max(ng, (size_t)1)));
+  LSG_RC(ensure(s, s->d_gagg, 96 * std::max(ng, (size_t)1)));
+  LSG_RC(ensure_host(s, s->h_gagg, 96 * std::max(ng, (size_t)1)));
+  s->gplan.reserve(words);
+  return LSG_OK;
+}
+
+// Plan, upload and launch the group sums of the slot's package on the current stream: per
+// group the sum of its sets' resident affine signatures (mask: only sets with mask[i] != 0;
+// null: every grouped set), compressed into h_gagg.  No host synchronisation.
+int run_sig_groups(Slot* s, const uint8_t* mask) {
+  const size_t ng = s->grp_n;
+  s->gplan.clear();
+  s->sgp = plan_sig_groups(s->gplan, s->set_grp.data(), s->n_sets, ng, mask,
+                           (int)lsg_ab_long("LSG_SEG_FOLD_WIDE", SEG_FOLD_WIDE));
+  const SegPlan& P = s->sgp.seg;
+  const size_t bytes = 4 * std::max(s->gplan.size(), (size_t)1);
+  LSG_RC(ensure_host(s, s->h_gplan, bytes));
+  LSG_RC(ensure(s, s->d_gplan, bytes));
+  for (DevBuf& b : s->d_gtmp) LSG_RC(ensure(s, b, 4 * W_G2P * std::max(P.tmp_items, (size_t)1)));
+  LSG_RC(ensure(s, s->d_gsum, 4 * W_G2P * ng));
+  LSG_RC(ensure(s, s->d_gagg, 96 * ng));
+  LSG_RC(ensure_host(s, s->h_gagg, 96 * ng));
+  memcpy(s->h_gplan.p, s->gplan.data(), 4 * s->gplan.size());
+  LSG_HIP(s, hipMemcpyAsync(s->d_gplan.p, s->h_gplan.p, 4 * s->gplan.size(), hipMemcpyHostToDevice, S_(s)));
+  const int32_t* A = P_<int32_t>(s->d_gplan);
+  uint32_t* tmp[3] = {nullptr, P_<uint32_t>(s->d_gtmp[0]), P_<uint32_t>(s->d_gtmp[1])};
+  uint32_t* dst = P_<uint32_t>(s->d_gsum);
+  for (size_t k = 0; k < P.passes.size(); k++) {
+    const SegPass& q = P.passes[k];
+    if (k == 0)
+      KL(s, "k_sig_agg_seg", lsgk::sig_agg_seg(S_(s), q.n_chunks, q.ips_log2, A + q.chunk_off, A + s->sgp.gather_off,
+                                               P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
+                                               P_<int32_t>(s->d_seterr), dst, tmp[q.tmp_out]));
+    else
+      KL(s, "sig_agg_reduce", lsgk::seg_reduce(S_(s), 1, q.n_chunks, q.ips_log2, A + q.chunk_off, nullptr, tmp[q.src], dst,
+                                               tmp[q.tmp_out]));
+  }
+  KL(s, "k_g2p_compress", lsgk::g2p_compress(S_(s), (int)ng, dst, P_<uint8_t>(s->d_gagg)));
+  LSG_HIP(s, hipMemcpyAsync(s->h_gagg.p, s->d_gagg.p, 96 * ng, hipMemcpyDeviceToHost, S_(s)));
   return LSG_OK;
 }
 
@@ -1530,7 +1594,8 @@ int launch_sig_prep(Slot* s, bool scale, const std::vector<uint8_t>* mode, uint3
 // staging order (lsg_verify_deposits: the signing roots never leave the GPU); the sets' host
 // msg bytes are placeholders then and are overwritten by a device copy.
 int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint64_t seed, int n_node,
-              const std::vector<size_t>* subs = nullptr, bool lone_ok = true, const uint8_t* dev_msgs = nullptr) {
+              const std::vector<size_t>* subs = nullptr, bool lone_ok = true, const uint8_t* dev_msgs = nullptr,
+              const uint32_t* set_group = nullptr, size_t n_groups = 0) {
   timer_reset(s);
   s->plan.clear();
   memset(&s->stats, 0, sizeof(s->stats));
@@ -1547,6 +1612,16 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   std::vector<const lsg_set*> flat(shape_jobs(s->shape, jobs, ids, subs));
   for (size_t k = 0; k < nj; k++)
     for (uint32_t q = 0; q < jobs[ids[k]].n_sets; q++) flat[s->shape.jobs[k].first + q] = &jobs[ids[k]].sets[q];
+  // a grouped package (single device: ids ascend): the caller's group word of every staged set
+  s->grp_n = set_group ? n_groups : 0;
+  if (s->grp_n) {
+    s->set_grp.assign(flat.size(), LSG_NO_GROUP);
+    size_t j = 0, before = 0;
+    for (size_t k = 0; k < nj; k++) {
+      for (; j < ids[k]; j++) before += jobs[j].n_sets;
+      for (uint32_t q = 0; q < jobs[ids[k]].n_sets; q++) s->set_grp[s->shape.jobs[k].first + q] = set_group[before + q];
+    }
+  }
   if (subs) {  // a coalesced launch: per-sub state
     lsg_stats z;
     memset(&z, 0, sizeof(z));
@@ -1658,12 +1733,21 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
                               hipMemcpyHostToDevice, s->st[0]));
     LSG_HIP(s, hipEventRecord(s->ev_part, s->st[0]));
   }
+  // the group sums over every grouped set, at the end of the side stream's work (beside the
+  // Miller products and final exponentiations on the main stream; launch_readback joins it)
+  const uint64_t th4 = trace_host() ? now_ns() : 0;
+  if (s->grp_n) {
+    s->cur = 1;
+    LSG_RC(run_sig_groups(s, nullptr));
+    s->cur = 0;
+  }
   s->phA_node = node;
   if (trace_host()) {
-    const uint64_t th4 = now_ns();
-    fprintf(stderr, "lsg host: sets %zu jobs %zu subs %d groups %zu | stage %.3f plan %.3f set-launch %.3f group-launch %.3f ms\n",
+    fprintf(stderr, "lsg host: sets %zu jobs %zu subs %d groups %zu | stage %.3f plan %.3f set-launch %.3f group-launch %.3f ms",
             (size_t)s->n_sets, nj, s->shape.n_sub, A.groups.size(), (th1 - th0) * 1e-6, (th2 - th1) * 1e-6, (th3 - th2) * 1e-6,
             (th4 - th3) * 1e-6);
+    if (s->grp_n) fprintf(stderr, " sig-groups %.3f ms", (now_ns() - th4) * 1e-6);
+    fprintf(stderr, "\n");
   }
   return LSG_OK;
 }
@@ -1976,7 +2060,8 @@ int pkg_exchange(lsg_ctx* c, int p) {
 // item 3), and host threads submitting packages to different slots stage them side by side.
 // Errors go to *err (t_err_sink), not to c->err.
 int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t seed, bool lone_ok, bool exch,
-              std::string* err, const uint8_t* dev_msgs = nullptr) {
+              std::string* err, const uint8_t* dev_msgs = nullptr, const uint32_t* set_group = nullptr,
+              size_t n_groups = 0) {
   const int n = c->n_dev;
   std::vector<std::vector<size_t>> ids(n);
   {
@@ -1994,7 +2079,7 @@ int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t se
     // distinct seeds per device for tests; 0 stays 0 (OS CSPRNG on every device)
     const uint64_t sd = seed ? seed + 0x9e3779b97f4a7c15ull * (uint64_t)d : 0;
     rcs[d] = pkg_part1(&c->dev[d]->slots[p], jobs, ids[d], sd, (d == 0 && exch) ? n : 0, nullptr, lone_ok && !exch,
-                       n == 1 ? dev_msgs : nullptr);
+                       n == 1 ? dev_msgs : nullptr, n == 1 ? set_group : nullptr, n_groups);
     t_err_sink = nullptr;
   };
   auto part2 = [&](int d) {
@@ -2083,7 +2168,8 @@ int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t se
 // and on return), staged with the lock released (stage_pkg), and its ticket committed under the
 // lock again.  A reserved slot is SLOT_STAGING: no other call takes, reserves or waits on it.
 int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint64_t seed, lsg_ticket* ticket,
-               bool lone_ok = true, const uint8_t* dev_msgs = nullptr) {
+               bool lone_ok = true, const uint8_t* dev_msgs = nullptr, const uint32_t* set_group = nullptr,
+               size_t n_groups = 0) {
   int p = -1;
   for (int i = 0; i < LSG_SLOTS && p < 0; i++)
     if (c->dev[0]->slots[i].kind == SLOT_FREE) p = i;
@@ -2104,7 +2190,7 @@ int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint
   c->staging++;
   lk.unlock();
   std::string err;
-  const int rc = stage_pkg(c, p, jobs, n_jobs, seed, lone_ok, exch, &err, dev_msgs);
+  const int rc = stage_pkg(c, p, jobs, n_jobs, seed, lone_ok, exch, &err, dev_msgs, set_group, n_groups);
   lk.lock();
   (void)hipSetDevice(c->dev[0]->device);
   c->staging--;
@@ -2129,8 +2215,56 @@ int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint
   return LSG_OK;
 }
 
-// resolve a package: node_valid as pkg_resolve (-2: the ticket's own node check)
-int wait_pkg(lsg_ctx* c, CtxLock* lk, int p, int node_valid, lsg_job_result* results, lsg_stats* stats) {
+// The aggregates of a resolved grouped package (single device): per group the compressed sum of
+// the signatures of the sets whose job resolved to LSG_VALID, and how many they were.  When
+// every grouped set is included (the common case) the sums launched at submit stand; otherwise
+// they are planned again over the included sets and launched once more on the slot's main
+// stream (the per-set values are resident, as for the fallback phases), synchronously.
+int finish_sig_groups(Slot* s, CtxLock* lk, uint8_t* agg96, uint32_t* agg_n) {
+  const size_t ng = s->grp_n;
+  std::vector<uint32_t> cnt(ng, 0);
+  size_t left_out = 0, included = 0;
+  for (size_t k = 0; k < s->shape.jobs.size(); k++) {
+    const JobRec& J = s->shape.jobs[k];
+    const bool valid = s->results[k].status == LSG_VALID;
+    for (size_t i = J.first; i < J.first + J.count; i++) {
+      if (s->set_grp[i] == LSG_NO_GROUP) continue;
+      if (valid) {
+        cnt[s->set_grp[i]]++;
+        included++;
+      } else {
+        left_out++;
+      }
+    }
+  }
+  if (left_out && included) {
+    const std::vector<uint8_t> mask = included_sets(s->shape, s->results.data());
+    s->cur = 0;
+    LSG_RC(run_sig_groups(s, mask.data()));
+    LSG_HIP(s, hipEventRecord(s->ev_done, s->st[0]));
+    const int dev = s->d->device;
+    if (lk) lk->unlock();
+    hipError_t e = event_wait(s->ev_done);
+    if (lk) {
+      lk->lock();
+      (void)hipSetDevice(dev);
+    }
+    if (e != hipSuccess) return fail(s, "hipEventSynchronize", e);
+  }
+  for (size_t g = 0; g < ng; g++) {
+    agg_n[g] = cnt[g];
+    if (cnt[g])
+      memcpy(agg96 + 96 * g, H_<uint8_t>(s->h_gagg) + 96 * g, 96);
+    else
+      memset(agg96 + 96 * g, 0, 96);
+  }
+  return LSG_OK;
+}
+
+// resolve a package: node_valid as pkg_resolve (-2: the ticket's own node check); agg96 /
+// agg_n: the aggregates of a grouped package (null: dropped)
+int wait_pkg(lsg_ctx* c, CtxLock* lk, int p, int node_valid, lsg_job_result* results, lsg_stats* stats,
+             uint8_t* agg96 = nullptr, uint32_t* agg_n = nullptr) {
   const int n = c->n_dev;
   int rc = LSG_OK;
   for (int d = 0; d < n && !rc; d++) {
@@ -2165,6 +2299,7 @@ int wait_pkg(lsg_ctx* c, CtxLock* lk, int p, int node_valid, lsg_job_result* res
     total.batch_sigs_success += s->stats.batch_sigs_success;
     total.n_final_exps += s->stats.n_final_exps;
   }
+  if (!rc && agg96 && agg_n && s0->grp_n) rc = finish_sig_groups(s0, lk, agg96, agg_n);
   if (s0->has_node) total.n_final_exps += 1;
   total.key_error = pkfail;
   total.key_error_job = pkfail ? (uint32_t)pkfail_job : 0;
@@ -2722,6 +2857,12 @@ int lsg_reserve(lsg_ctx* c, size_t max_sets, size_t max_pks, size_t max_msg_byte
         LSG_RC(ensure_host(s, s->h_cbits, 4 * max_pks));
         LSG_RC(ensure(s, s->d_cbits, 4 * max_pks));
       }
+      // the group buffers of lsg_submit_jobs_grouped (max_sets sets in max_sets groups), once the
+      // context has seen a grouped package: the caller reserves again after its first one
+      if (c->grouped_seen) {
+        LSG_RC(size_groups(s, max_sets, max_sets));
+        s->set_grp.reserve(max_sets);
+      }
       LSG_RC(ensure_host(s, s->h_mode, std::max(max_sets, (size_t)1)));
       const size_t plan_words = 16 * max_sets + 4 * max_pks + 64 * 1024;
       LSG_RC(ensure_host(s, s->h_plan, 4 * plan_words));
@@ -2779,7 +2920,48 @@ int lsg_set_coalesce(lsg_ctx* c, uint32_t max_sets, int32_t max_inflight) {
   return LSG_OK;
 }
 
+// A grouped package launches on its own, as the packages of
+// lsg_verify_deposits do: never held by lsg_set_coalesce, and it flushes nothing that holds.
+int lsg_submit_jobs_grouped(lsg_ctx* c, const lsg_job* jobs, size_t n_jobs, uint64_t seed, const uint32_t* set_group,
+                            size_t n_groups, lsg_ticket* ticket) {
+  if (!set_group || n_groups == 0) return lsg_submit_jobs(c, jobs, n_jobs, seed, ticket);
+  if (!c || !ticket || (n_jobs && !jobs) || n_groups > 0x7fffffffull) return LSG_ERR_INVALID_ARG;
+  size_t ns = 0;
+  for (size_t j = 0; j < n_jobs; j++) {
+    if (jobs[j].n_sets && !jobs[j].sets) return LSG_ERR_INVALID_ARG;
+    ns += jobs[j].n_sets;
+  }
+  if (!msg_jobs_ok(jobs, n_jobs)) return LSG_ERR_INVALID_ARG;
+  CtxLock lk(c->mu);
+  for (size_t i = 0; i < ns; i++)
+    if (set_group[i] != LSG_NO_GROUP && set_group[i] >= n_groups) {
+      c->err = "lsg_submit_jobs_grouped: set " + std::to_string(i) + " names group " + std::to_string(set_group[i]) +
+               " of " + std::to_string(n_groups);
+      return LSG_ERR_INVALID_ARG;
+    }
+  if (c->n_dev > 1) {
+    c->err = "lsg_submit_jobs_grouped: groups are single-device (a group can span devices)";
+    return LSG_ERR_INVALID_ARG;
+  }
+  LSG_HIPC(c, hipSetDevice(c->dev[0]->device));
+  c->grouped_seen = true;
+  return submit_pkg(c, lk, jobs, n_jobs, seed, ticket, true, nullptr, set_group, n_groups);
+}
+
+static int wait_jobs_impl(lsg_ctx* c, lsg_ticket ticket, int32_t node_valid, lsg_job_result* results, lsg_stats* stats,
+                          uint8_t* agg96, uint32_t* agg_n);
+
+int lsg_wait_jobs_grouped(lsg_ctx* c, lsg_ticket ticket, lsg_job_result* results, lsg_stats* stats, uint8_t* agg96,
+                          uint32_t* agg_n) {
+  return wait_jobs_impl(c, ticket, -1, results, stats, agg96, agg_n);
+}
+
 int lsg_wait_jobs_node(lsg_ctx* c, lsg_ticket ticket, int32_t node_valid, lsg_job_result* results, lsg_stats* stats) {
+  return wait_jobs_impl(c, ticket, node_valid, results, stats, nullptr, nullptr);
+}
+
+static int wait_jobs_impl(lsg_ctx* c, lsg_ticket ticket, int32_t node_valid, lsg_job_result* results, lsg_stats* stats,
+                          uint8_t* agg96, uint32_t* agg_n) {
   if (!c) return LSG_ERR_INVALID_ARG;
   if (((ticket >> 8) & 255) == SLOT_MERGE) {
     if (node_valid != -1) {
@@ -2800,7 +2982,7 @@ int lsg_wait_jobs_node(lsg_ctx* c, lsg_ticket ticket, int32_t node_valid, lsg_jo
     c->err = "lsg_wait_jobs_node: a multi-device context runs its own node check";
     return LSG_ERR_INVALID_ARG;
   }
-  const int rc = wait_pkg(c, &lk, p, node_valid == -1 ? -2 : (node_valid ? 1 : 0), results, stats);
+  const int rc = wait_pkg(c, &lk, p, node_valid == -1 ? -2 : (node_valid ? 1 : 0), results, stats, agg96, agg_n);
   maybe_flush(c);
   return rc;
 }

@@ -75,6 +75,57 @@ __global__ void LSG_KERNEL_ATTR_W(1) k_sig_scale3(int n, const uint32_t* __restr
   lane_store(out, item, r);
 }
 
+// Signature.aggregate of the verified signatures per caller-named group (lsg_submit_jobs_grouped;
+// SURVEY.md 8f(7)): the G2 twin of k_pk_agg_seg (lsg_k_pk.hip).  One pass of the segmented
+// reduction (lsg_plan.hpp plan_sig_groups) whose elements are the decoded, subgroup-checked
+// affine signatures already resident in sig_aff, reached through the gather list (set slots
+// ordered by group) and folded with complete mixed additions -- no projective copy of every
+// signature written and read back -- then the chunk's lane pairs combined by a butterfly.
+// Chunk = (first list entry, count, output: >= 0 into dst, < 0 into tmp for k_seg_reduce<1>).
+// A set that is not usable (err != 0 or the point at infinity) adds nothing.
+__global__ void LSG_KERNEL_ATTR k_sig_agg_seg(int n_chunks, int ips_log2, const int32_t* __restrict__ chunks,
+                                              const int32_t* __restrict__ gather, const uint32_t* __restrict__ sig_aff,
+                                              const uint8_t* __restrict__ inf, const int32_t* __restrict__ err,
+                                              uint32_t* __restrict__ dst, uint32_t* __restrict__ tmp) {
+  lsg_lane_setup();
+  const size_t item = gtid() / LSG_GROUP;
+  const size_t c = item >> ips_log2;
+  const int ips = 1 << ips_log2, j = (int)(item & (size_t)(ips - 1));
+  const bool active = c < (size_t)n_chunks;
+  g2p_t acc = proj_inf<fp2_t>();
+  int out = 0;
+  if (active) {
+    const int off = chunks[3 * c], len = chunks[3 * c + 1];
+    out = chunks[3 * c + 2];
+    // software-pipelined as k_pk_agg_seg: the next signature's row is in flight while this one
+    // is added (the gathers are scattered over the package's sets)
+    g2a_t a;
+    bool use = false;
+    auto fetch = [&](int k) {
+      const size_t i = (size_t)gather[off + k];
+      a = lane_load<g2a_t>(sig_aff, i);
+      return sig_usable(i, inf, err, nullptr);
+    };
+    if (j < len) use = fetch(j);
+#pragma unroll 1
+    for (int k = j; k < len; k += ips) {
+      const g2a_t cur = a;
+      const bool cur_use = use;
+      if (k + ips < len) use = fetch(k + ips);
+      if (cur_use) acc = proj_is_inf(acc) ? proj_from_aff(cur) : g2_add_mixed(acc, cur);
+    }
+  }
+  // every lane runs the butterfly: a chunk never straddles a wave (ips <= 32 pairs)
+#pragma unroll 1
+  for (int o = ips >> 1; o >= 1; o >>= 1) acc = g2_add(acc, shfl_xor_t(acc, LSG_GROUP * o));
+  if (active && j == 0) {
+    if (out >= 0)
+      lane_store(dst, (size_t)out, acc);
+    else
+      lane_store(tmp, (size_t)(-out - 1), acc);
+  }
+}
+
 __global__ void LSG_KERNEL_ATTR k_g2a_to_bytes(int n, const uint32_t* __restrict__ pts, const uint8_t* __restrict__ inf,
                                                uint8_t* __restrict__ out) {
   LANE_ITEM(n);
@@ -161,6 +212,11 @@ hipError_t sig_prep(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_
 hipError_t sig_scale_only(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err,
                           const uint8_t* pinf, const uint64_t* rnd, const uint8_t* mode, uint32_t* out) {
   LSG_LAUNCH_ITEMS(k_sig_scale3, n, st, n, sig_aff, inf, err, pinf, rnd, mode, out);
+}
+hipError_t sig_agg_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t* chunks, const int32_t* gather,
+                       const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err, uint32_t* dst, uint32_t* tmp) {
+  LSG_LAUNCH_ITEMS(k_sig_agg_seg, (size_t)n_chunks << ips_log2, st, n_chunks, ips_log2, chunks, gather, sig_aff, inf, err,
+                   dst, tmp);
 }
 hipError_t g2a_to_bytes(hipStream_t st, int n, const uint32_t* pts, const uint8_t* inf, uint8_t* out192) {
   LSG_LAUNCH_ITEMS(k_g2a_to_bytes, n, st, n, pts, inf, out192);

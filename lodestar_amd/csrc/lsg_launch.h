@@ -48,6 +48,11 @@ hipError_t sig_prep(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_
 // entries of out are left as they are (fallback phases fill one scaled array in turns)
 hipError_t sig_scale_only(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err,
                           const uint8_t* pinf, const uint64_t* rnd, const uint8_t* mode, uint32_t* out);
+// the first pass of a segmented G2 sum over the resident affine signatures (plan_sig_groups
+// chunks; later passes: seg_reduce op 1 over tmp): element k of the list is set gather[k],
+// folded with mixed additions unless err[set] != 0 or inf[set]
+hipError_t sig_agg_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t* chunks, const int32_t* gather,
+                       const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err, uint32_t* dst, uint32_t* tmp);
 hipError_t g2a_to_bytes(hipStream_t st, int n, const uint32_t* pts, const uint8_t* inf, uint8_t* out192);
 hipError_t g2p_compress(hipStream_t st, int n, const uint32_t* pts, uint8_t* out96);
 hipError_t g2p_to_canon(hipStream_t st, int n, const uint32_t* pts, uint8_t* out288);

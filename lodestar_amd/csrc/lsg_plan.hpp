@@ -1185,4 +1185,60 @@ inline int resolve_package(const PkgShape& sh, const GroupPlan& gp, const SetSta
   return r.run(pkfail);
 }
 
+// ---- per-group sums of the verified signatures (lsg_submit_jobs_grouped)
+// The staged sets whose signature joins its group's aggregate: set i of job k (staging order,
+// verdicts[k] that job's) is included exactly when the job resolved to LSG_VALID -- a multi-set
+// job all or nothing, as its verdict is.
+inline std::vector<uint8_t> included_sets(const PkgShape& sh, const lsg_job_result* verdicts) {
+  size_t n = 0;
+  for (const JobRec& J : sh.jobs) n = std::max(n, J.first + J.count);
+  std::vector<uint8_t> mask(n, 0);
+  for (size_t k = 0; k < sh.jobs.size(); k++)
+    if (verdicts[k].status == LSG_VALID)
+      for (size_t i = sh.jobs[k].first; i < sh.jobs[k].first + sh.jobs[k].count; i++) mask[i] = 1;
+  return mask;
+}
+
+// The plan of k_sig_agg_seg (lsg_k_sig.hip) appended to arena A.  set_group[i] is staged set i's
+// group (below n_groups, or LSG_NO_GROUP); mask (null: every set) leaves out the sets with
+// mask[i] == 0.  gather: n_gather words at A[gather_off ..] holding the n_members set slots
+// ordered by group and within a group by slot; group g's members are gather[off[g] .. off[g] +
+// len[g]).  seg: plan_seg over that list (its first pass is the kernel's, reading sets through
+// the list; a group longer than one chunk of 2^ips_log2 lane pairs x SEG_FOLD members finishes
+// in a second pass of k_seg_reduce<1> over the chunk sums).  An empty group keeps a chunk of
+// length 0: the identity.
+// A group of SIG_GROUP_PAD_MIN members or more is followed by SIG_GROUP_PAD unused words (one
+// cache line): packed back to back, groups of one power-of-two length (64 committees of 512)
+// start at one power-of-two stride, and the write streams of the fill below then evict one
+// another from the same few cache sets (the fill of 32,768 sets took six times as long).
+constexpr int32_t SIG_GROUP_PAD_MIN = 128, SIG_GROUP_PAD = 16;
+struct SigGroupPlan {
+  size_t gather_off = 0, n_gather = 0, n_members = 0;
+  std::vector<int32_t> off, len;  // per group
+  SegPlan seg;
+};
+inline SigGroupPlan plan_sig_groups(std::vector<int32_t>& A, const uint32_t* set_group, size_t n_sets, size_t n_groups,
+                                    const uint8_t* mask, int fold_wide = SEG_FOLD_WIDE) {
+  SigGroupPlan P;
+  P.off.assign(n_groups, 0);
+  P.len.assign(n_groups, 0);
+  auto in = [&](size_t i) { return set_group[i] < n_groups && (!mask || mask[i]); };
+  for (size_t i = 0; i < n_sets; i++)
+    if (in(i)) P.len[set_group[i]]++;
+  int32_t tot = 0;
+  for (size_t g = 0; g < n_groups; g++) {
+    P.off[g] = tot;
+    P.n_members += (size_t)P.len[g];
+    tot += P.len[g] + (P.len[g] >= SIG_GROUP_PAD_MIN ? SIG_GROUP_PAD : 0);
+  }
+  P.gather_off = A.size();
+  P.n_gather = (size_t)tot;
+  A.resize(P.gather_off + P.n_gather);
+  std::vector<int32_t> fill(P.off);
+  for (size_t i = 0; i < n_sets; i++)
+    if (in(i)) A[P.gather_off + (size_t)fill[set_group[i]]++] = (int32_t)i;
+  P.seg = plan_seg(A, 1, P.off, P.len, true, P.gather_off, 0, fold_wide);
+  return P;
+}
+
 }  // namespace lsgp

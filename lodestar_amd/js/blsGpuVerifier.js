@@ -51,6 +51,9 @@
  *   opts.validatePubkeys           PublicKey.fromBytes(pk, affine, true) for the call's keys, on
  *                                  the GPU inside the package (signatureSets/blsToExecutionChange.ts:32)
  *   verifyDeposits                 block/processDeposit.ts:47-66 for a list of DepositData
+ * Op pools (INTEGRATION.md "Op pools", SURVEY.md 8f(7)):
+ *   options.onAggregates           per package and aggregateKey, the sum of the verified sets'
+ *                                  signatures (set.aggregateKey, set.aggregateTag)
  */
 
 const MAX_SIGNATURE_SETS_PER_JOB = 128;
@@ -191,13 +194,20 @@ function EXEC(resolve) {
  * with the verdict and the JS thread keeps running meanwhile.  No retry: one job is one
  * maybeBatch call; an error rejects with its BLST code (e.g. BLST_INVALID_SIZE).
  */
-function verifyDirect(addon, ctx, sets, seed, validate = false) {
+function verifyDirect(addon, ctx, sets, seed, validate = false, onAggregates = null, logger = null) {
   const page = new JobPage(false, true, null, validate);
   const p = page.push(sets);
-  const pkg = packJobs([page, 0, 1], sets.length, undefined, 0);
+  const pkg = packJobs([page, 0, 1], sets.length, undefined, 0, onAggregates !== null);
   if (pkg.nJobs === 1) {
-    addon.verifyPacked(ctx, pkg.arena, pkg.setDesc, pkg.jobDesc, seed, true).then(
-      (r) => settleJobs(pkg.ranges, r.status, r.errCode),
+    const call =
+      pkg.groups === null
+        ? addon.verifyPacked(ctx, pkg.arena, pkg.setDesc, pkg.jobDesc, seed, true)
+        : addon.verifyPacked(ctx, pkg.arena, pkg.setDesc, pkg.jobDesc, seed, true, pkg.groups, pkg.groupKeys.length);
+    call.then(
+      (r) => {
+        if (pkg.groups !== null) deliverAggregates(pkg, r, onAggregates, logger);
+        settleJobs(pkg.ranges, r.status, r.errCode);
+      },
       (e) => page.fail(0, e)
     );
   }
@@ -208,6 +218,7 @@ function verifyDirect(addon, ctx, sets, seed, validate = false) {
 const MAX_COMMITTEE_ID = 1 << 20;
 const MAX_COMMITTEE_LEN = 131072;
 const PK_BITS = 8; // LSG_PK_BITS
+const NO_GROUP = 0xffffffff; // LSG_NO_GROUP
 
 /** A set that names its signers as {committee, bits, bitLen}: committee is an id given to
  * loadCommittees, bits the participation bitfield in SSZ order without a delimiter bit (member k
@@ -473,7 +484,38 @@ const SET_DESC_WORDS = 7; // pkOff, pkLen, nPks, msgOff, msgLen, sigOff, sigLen 
  * and left out.  `into` (optional) is a previous package's buffers, reused when large enough
  * (fresh multi-MB typed arrays per package cost GC time).  Packed jobs drop their sets.
  */
-function packJobs(ranges, nSigs, into, minSigs = 0) {
+function packJobs(ranges, nSigs, into, minSigs = 0, grouped = false) {
+  // grouped (the verifier has an onAggregates handler): a set's aggregateKey becomes its group
+  // id -- one id per distinct key of the package, whichever call the set came from -- and its
+  // aggregateTag is kept for the handler.  A package without a keyed set has groups === null.
+  let groups = null;
+  let groupIds = null; // key -> id
+  let groupKeys = null; // id -> key
+  let groupTags = null; // per set
+  const groupOf = (set, k) => {
+    const key = set.aggregateKey;
+    if (key === undefined) {
+      if (groups !== null) groups[k] = NO_GROUP;
+      return;
+    }
+    if (typeof key !== "string") throw Error("aggregateKey must be a string");
+    if (groups === null) {
+      const len = Math.max(nSigs, minSigs);
+      groups = into && into.groupsBuf && into.groupsBuf.length >= len ? into.groupsBuf : new Uint32Array(len);
+      groups.fill(NO_GROUP);
+      groupIds = new Map();
+      groupKeys = [];
+      groupTags = [];
+    }
+    let id = groupIds.get(key);
+    if (id === undefined) {
+      id = groupKeys.length;
+      groupIds.set(key, id);
+      groupKeys.push(key);
+    }
+    groups[k] = id;
+    groupTags[k] = set.aggregateTag;
+  };
   // 224 bytes per set: one raw key, a 32-byte root, a signature.  Sets that carry more (aggregate
   // keys, signingObject + domain: up to 160 message bytes) grow the arena in put(); the grown
   // buffer comes back as arenaBuf, so a verifier's later packages of that kind reuse it
@@ -525,6 +567,7 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
           const msgWord = dom === null ? root.length : MSG_OBJECT + root.length + 32;
           const sig = set.signature;
           const msgBytes = dom === null ? root.length : root.length + 32;
+          if (grouped) groupOf(set, k);
           if (pk1 instanceof Uint8Array && pk1.length !== PK_BITS && off + pk1.length + msgBytes + sig.length <= cap) {
             // the common shape (one raw key): three copies, no helper calls
             arena.set(pk1, off);
@@ -607,7 +650,53 @@ function packJobs(ranges, nSigs, into, minSigs = 0) {
     setDescBuf,
     jobDescBuf,
     nSigs: k,
+    groups: groups === null ? null : groups.subarray(0, k),
+    groupsBuf: groups !== null ? groups : into && into.groupsBuf ? into.groupsBuf : null,
+    groupKeys,
+    groupTags,
   };
+}
+
+/**
+ * The onAggregates call of one grouped package (SURVEY 8f(7)): per key with at least one verified
+ * signature, {key, signature: the 96-byte compressed sum the device returned, count, tags: the
+ * aggregateTag of every included set in package order}; no call when no key has one.  A set is included exactly when its job
+ * resolved true (the library's rule: a multi-set job all or nothing).  The handler runs before
+ * the package's promises are settled, so a pool that merges here has the aggregate in place when
+ * the caller's `await verifySignatureSets` continues.  A throwing (or rejecting) handler is
+ * logged and never disturbs verdict delivery.
+ */
+function deliverAggregates(pkg, workResult, handler, logger) {
+  try {
+    const n = pkg.groupKeys.length;
+    const tags = new Array(n);
+    const jd = pkg.jobDesc;
+    const groups = pkg.groups;
+    let k = 0;
+    for (let j = 0; j < pkg.nJobs; j++) {
+      const nSets = jd[2 * j];
+      if (workResult.status[j] === LSG_VALID) {
+        for (let i = k; i < k + nSets; i++) {
+          const g = groups[i];
+          if (g === NO_GROUP) continue;
+          if (tags[g] === undefined) tags[g] = [];
+          tags[g].push(pkg.groupTags[i]);
+        }
+      }
+      k += nSets;
+    }
+    const out = [];
+    for (let g = 0; g < n; g++) {
+      const count = workResult.aggCount[g];
+      if (count === 0) continue;
+      out.push({key: pkg.groupKeys[g], signature: workResult.agg.slice(96 * g, 96 * g + 96), count, tags: tags[g] || []});
+    }
+    if (out.length === 0) return;
+    const r = handler(out);
+    if (r && typeof r.then === "function") r.then(undefined, (e) => logger && logger.error("BlsGpuVerifier onAggregates error", {}, e));
+  } catch (e) {
+    if (logger) logger.error("BlsGpuVerifier onAggregates error", {}, e);
+  }
 }
 
 /** GPU package policy defaults (see the class comment) */
@@ -619,7 +708,15 @@ class BlsGpuVerifier {
    * @param {{blsVerifyAllMultiThread?: boolean, device?: number, devices?: number[], seed?: number,
    *          maxSigsPerPackage?: number, eagerPackages?: number, minSigsWhenBusy?: number,
    *          maxPendingSigs?: number, bufferWaitMs?: number, reserveSets?: number,
-   *          reservePubkeys?: number, reserveMsgBytes?: number}} options
+   *          reservePubkeys?: number, reserveMsgBytes?: number,
+   *          onAggregates?: (entries: {key: string, signature: Uint8Array, count: number, tags: any[]}[]) => void}} options
+   *        onAggregates (SURVEY 8f(7)): with a handler, a set may carry `aggregateKey` (a string,
+   *        e.g. the attestation data root) and `aggregateTag` (anything, e.g. the bit index): every
+   *        package then also returns, per key, the compressed sum of the signatures of its sets
+   *        that verified -- sets of different calls that share a key share a group -- and the
+   *        handler gets one call per package, after the verdicts are known and before the
+   *        package's promises are settled (deliverAggregates).  Without a handler the two fields
+   *        are ignored and packages go out exactly as before.
    * @param {{logger?: object, metrics?: object|null, addon?: object}} modules  addon is
    *        injectable (tests drive the queue logic with a mock of the addon's surface)
    *
@@ -644,6 +741,7 @@ class BlsGpuVerifier {
     this.metrics = modules.metrics || null;
     this.blsVerifyAllMultiThread = options.blsVerifyAllMultiThread === true;
     this.seed = options.seed || 0; // 0: randomizers from the OS CSPRNG (production)
+    this.onAggregates = typeof options.onAggregates === "function" ? options.onAggregates : null;
     this.addon = modules.addon || loadAddon();
     // throws loudly without a gfx950 device
     this.ctx = this.addon.open(Array.isArray(options.devices) ? options.devices : options.device || 0);
@@ -744,7 +842,7 @@ class BlsGpuVerifier {
         // verifySignatureSetsMaybeBatch without the queue: no retry, errors reject
         const m = this.metrics && this.metrics.blsThreadPool;
         const timer = m ? m.mainThreadDurationInThreadPool.startTimer() : null;
-        const p = verifyDirect(this.addon, this.ctx, sets, this.seed, opts.validatePubkeys === true);
+        const p = verifyDirect(this.addon, this.ctx, sets, this.seed, opts.validatePubkeys === true, this.onAggregates, this.logger);
         if (timer) p.then(timer, timer);
         return p;
       }
@@ -777,9 +875,16 @@ class BlsGpuVerifier {
     const o = {batchable: true, priority: opts.priority};
     return Promise.all(
       sets.map((s) =>
-        this._queueBlsWork(o, [{type: SignatureSetType.single, pubkey: s.publicKey, signingRoot: message, signature: s.signature}]).catch(
-          () => false
-        )
+        this._queueBlsWork(o, [
+          {
+            type: SignatureSetType.single,
+            pubkey: s.publicKey,
+            signingRoot: message,
+            signature: s.signature,
+            aggregateKey: s.aggregateKey,
+            aggregateTag: s.aggregateTag,
+          },
+        ]).catch(() => false)
       )
     );
   }
@@ -924,10 +1029,13 @@ class BlsGpuVerifier {
       let pkg = null;
       try {
         // buffers sized for a full package, so that every one can be reused
-        pkg = packJobs(ranges, startedSigSets, this.spare.pop(), this.maxSigsPerPackage);
+        pkg = packJobs(ranges, startedSigSets, this.spare.pop(), this.maxSigsPerPackage, this.onAggregates !== null);
         if (pkg.nJobs === 0) return;
         const jobStartNs = process.hrtime.bigint();
-        const workResult = await this.addon.verifyPacked(this.ctx, pkg.arena, pkg.setDesc, pkg.jobDesc, this.seed);
+        const workResult =
+          pkg.groups === null
+            ? await this.addon.verifyPacked(this.ctx, pkg.arena, pkg.setDesc, pkg.jobDesc, this.seed)
+            : await this.addon.verifyPacked(this.ctx, pkg.arena, pkg.setDesc, pkg.jobDesc, this.seed, false, pkg.groups, pkg.groupKeys.length);
         const jobEndNs = process.hrtime.bigint();
         if (m) {
           // index.ts:362-381, with the GPU package in the worker's place
@@ -946,6 +1054,7 @@ class BlsGpuVerifier {
           m.batchRetries.inc(workResult.batchRetries);
           m.batchSigsSuccess.inc(workResult.batchSigsSuccess);
         }
+        if (pkg.groups !== null) deliverAggregates(pkg, workResult, this.onAggregates, this.logger);
         settleJobs(ranges, workResult.status, workResult.errCode);
         if (this.spare.length < this.poolSize) this.spare.push(pkg);
       } catch (e) {

@@ -27,6 +27,11 @@
  *       (process.hrtime.bigint()'s clock); workerId is the pipeline slot that ran the package
  *       (the reference's workerId label).  priority = true (verifyOnMainThread): the package
  *       goes ahead of every queued one, onto the addon's priority thread
+ *       verifyPacked(..., priority, groups: Uint32Array(nSets), nGroups): the grouped form
+ *       (lsg_submit_jobs_grouped + lsg_wait_jobs_grouped) -- one group id per set (0xffffffff: none);
+ *       the result gains agg: Uint8Array(96 * nGroups), the compressed sum of each group's
+ *       verified signatures, and aggCount: Uint32Array(nGroups).  Throws "does not support" when
+ *       the loaded library lacks the entry points
  *   sign(ctx, sks, msgs) / skToPk(ctx, sks)  test and bench input generation
  *   verifySets(ctx, sets, seed) -> {status, errCode}                   lsg_verify_sets
  *   aggregatePubkeys(ctx, pubkeys[]) -> {errCode, bytes: Uint8Array(96)} lsg_aggregate_pubkeys
@@ -67,6 +72,10 @@ extern int lsg_committees_clear(lsg_ctx* ctx, uint32_t first_id, size_t n) __att
 extern int lsg_object_signing_roots(lsg_ctx* ctx, const uint8_t* objs, uint32_t obj_len, size_t n,
                                     const uint8_t* domain32, uint32_t domain_stride, uint8_t* out32)
     __attribute__((weak));
+extern int lsg_submit_jobs_grouped(lsg_ctx* ctx, const lsg_job* jobs, size_t n_jobs, uint64_t seed,
+                                   const uint32_t* set_group, size_t n_groups, lsg_ticket* ticket) __attribute__((weak));
+extern int lsg_wait_jobs_grouped(lsg_ctx* ctx, lsg_ticket ticket, lsg_job_result* results, lsg_stats* stats,
+                                 uint8_t* agg96, uint32_t* agg_n) __attribute__((weak));
 
 #define LSG_NAPI_THREADS 16 /* package threads per context: one outstanding package each */
 
@@ -332,13 +341,18 @@ static napi_value js_device_name(napi_env env, napi_callback_info info) {
 typedef struct pkg_req {
   struct pkg_req* next;
   napi_deferred deferred;
-  napi_ref refs[3]; /* arena, setDesc, jobDesc: kept alive until the promise settles */
+  napi_ref refs[4]; /* arena, setDesc, jobDesc, groups: kept alive until the promise settles */
   const uint8_t* arena;
   size_t arena_len;
   const uint32_t* sdesc;
   const uint32_t* jdesc;
   uint32_t n_sets, n_jobs;
   uint64_t seed;
+  /* the grouped form: one group id per set, n_groups aggregates (groups == NULL: a plain package) */
+  const uint32_t* groups;
+  uint32_t n_groups;
+  uint8_t* agg;
+  uint32_t* agg_n;
   lsg_ticket ticket;
   lsg_job_result* results;
   lsg_stats stats;
@@ -453,7 +467,8 @@ static void* engine_main(void* arg) {
        * packages are outstanding per context (engine_start), so BUSY only means another host
        * thread of this process shares the context: back off */
       for (int tries = 0;; tries++) {
-        r->rc = lsg_submit_jobs(a->c, jobs, r->n_jobs, r->seed, &r->ticket);
+        r->rc = r->groups ? lsg_submit_jobs_grouped(a->c, jobs, r->n_jobs, r->seed, r->groups, r->n_groups, &r->ticket)
+                          : lsg_submit_jobs(a->c, jobs, r->n_jobs, r->seed, &r->ticket);
         if (r->rc != LSG_ERR_BUSY || tries > 100000) break;
         struct timespec ts = {0, 200000};
         nanosleep(&ts, NULL);
@@ -461,7 +476,8 @@ static void* engine_main(void* arg) {
       /* a coalesced ticket still held while every slot is busy waits with LSG_ERR_BUSY until
        * another package's wait frees one (lsg_host.hip wait_merged): back off and wait again */
       for (int tries = 0; r->rc == LSG_OK; tries++) {
-        const int wrc = lsg_wait_jobs(a->c, r->ticket, r->results, &r->stats);
+        const int wrc = r->groups ? lsg_wait_jobs_grouped(a->c, r->ticket, r->results, &r->stats, r->agg, r->agg_n)
+                                  : lsg_wait_jobs(a->c, r->ticket, r->results, &r->stats);
         if (wrc != LSG_ERR_BUSY || tries > 100000) {
           r->rc = wrc;
           break;
@@ -509,12 +525,25 @@ static void engine_deliver(napi_env env, napi_value js_cb, void* context, void* 
       set_int(env, o, "submitUs", r->stats.submit_us);
       set_int(env, o, "keyError", r->stats.key_error);
       set_int(env, o, "workerId", (int64_t)(r->ticket & 0xff));
+      if (r->groups) {
+        napi_value ag, an;
+        napi_create_arraybuffer(env, 96 * (size_t)r->n_groups, &p, &ab);
+        memcpy(p, r->agg, 96 * (size_t)r->n_groups);
+        napi_create_typedarray(env, napi_uint8_array, 96 * (size_t)r->n_groups, ab, 0, &ag);
+        napi_create_arraybuffer(env, 4 * (size_t)r->n_groups, &p, &ab);
+        memcpy(p, r->agg_n, 4 * (size_t)r->n_groups);
+        napi_create_typedarray(env, napi_uint32_array, r->n_groups, ab, 0, &an);
+        napi_set_named_property(env, o, "agg", ag);
+        napi_set_named_property(env, o, "aggCount", an);
+      }
       napi_resolve_deferred(env, r->deferred, o);
     }
-    for (int k = 0; k < 3; k++)
+    for (int k = 0; k < 4; k++)
       if (r->refs[k]) napi_delete_reference(env, r->refs[k]);
     if (a->pending && --a->pending == 0) napi_unref_threadsafe_function(env, a->tsfn);
   }
+  free(r->agg);
+  free(r->agg_n);
   free(r->results);
   free(r);
 }
@@ -571,8 +600,8 @@ static int typed_info(napi_env env, napi_value v, napi_typedarray_type want, voi
 }
 
 static napi_value js_verify_packed(napi_env env, napi_callback_info info) {
-  size_t argc = 6;
-  napi_value argv[6];
+  size_t argc = 8;
+  napi_value argv[8];
   NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
   addon_ctx* a = get_actx(env, argv[0]);
   if (!a) return NULL;
@@ -588,6 +617,24 @@ static napi_value js_verify_packed(napi_env env, napi_callback_info info) {
   if (argc >= 5) napi_get_value_double(env, argv[4], &seedd);
   bool prio = false;
   if (argc >= 6) napi_get_value_bool(env, argv[5], &prio);
+  /* groups?: Uint32Array(nSets), nGroups? (absent, undefined, null or nGroups = 0: a plain package) */
+  void* gp = NULL;
+  double ngd = 0;
+  napi_valuetype gt = napi_undefined;
+  if (argc >= 7) napi_typeof(env, argv[6], &gt);
+  if (argc >= 8) napi_get_value_double(env, argv[7], &ngd);
+  if (gt != napi_undefined && gt != napi_null && ngd > 0) {
+    size_t ng = 0;
+    if (typed_info(env, argv[6], napi_uint32_array, &gp, &ng) || ng != ns / 7 || ngd > 2147483647.0) {
+      napi_throw_type_error(env, NULL, "lsg_napi: verifyPacked(..., groups: Uint32Array(nSets), nGroups)");
+      return NULL;
+    }
+    if (!lsg_submit_jobs_grouped || !lsg_wait_jobs_grouped) {
+      napi_throw_error(env, NULL, "lsg_napi: the loaded library does not support groups (no lsg_submit_jobs_grouped)");
+      return NULL;
+    }
+    if (!gp) gp = sd; /* no sets: any non-NULL pointer, never read */
+  }
   if (engine_start(env, a)) {
     napi_throw_error(env, NULL, "lsg_napi: could not start the package threads");
     return NULL;
@@ -602,6 +649,13 @@ static napi_value js_verify_packed(napi_env env, napi_callback_info info) {
   r->seed = (uint64_t)seedd;
   r->results = (lsg_job_result*)calloc(r->n_jobs ? r->n_jobs : 1, sizeof(lsg_job_result));
   for (int k = 0; k < 3; k++) napi_create_reference(env, argv[1 + k], 1, &r->refs[k]);
+  if (gp) {
+    r->groups = (const uint32_t*)gp;
+    r->n_groups = (uint32_t)ngd;
+    r->agg = (uint8_t*)calloc(r->n_groups, 96);
+    r->agg_n = (uint32_t*)calloc(r->n_groups, sizeof(uint32_t));
+    napi_create_reference(env, argv[6], 1, &r->refs[3]);
+  }
   napi_value promise;
   NAPI_CALL(env, napi_create_promise(env, &r->deferred, &promise));
   if (a->pending++ == 0) napi_ref_threadsafe_function(env, a->tsfn);
