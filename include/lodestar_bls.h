@@ -497,6 +497,48 @@ int lsg_check_fp2_sqr(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out)
  * carries at every operation beside it (lsg_k_reduce.hip k_check_sums lists the slots).  Not
  * on the verification path. */
 int lsg_check_sums(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+/* Parity hooks of the layer between the products and the accept / reject rules (tests only;
+ * none is on the verification path).  Elements travel in the pair layout above: 14 words, limb
+ * L at word 2 (L mod 7) + L / 7.  Each returns LSG_ERR_INVALID_ARG for a null pointer with a
+ * non-zero count or a count whose buffers pass 2^31 bytes.
+ *
+ * lsg_check_canon: n raw lazy elements in (element i at in[14 i ..]), 54 words per element out:
+ *    out[54 i +  0 .. 13]  pair_canon(a): the representative in [0, p) of any lazy value
+ *    out[54 i + 14 .. 27]  fp_canonical(a): the same for a value in (-p, 2p)
+ *    out[54 i + 28 .. 39]  the 48 bytes fp_to_be48(fp_canonical(a)) writes, in memory order
+ *    out[54 i + 40]        bit 0 fp_is_zero(a), bit 1 fp_canon_lt_p(a), bit 2 fp_canon_gt_half(a),
+ *                          bit 3 fp_canon_parity(a)
+ *    out[54 i + 41]        0
+ *    out[54 i + 42 .. 53]  the 48 bytes fp_to_be48(a) writes for the raw value (a in [0, 2^384):
+ *                          the form that carries the flag bits 381..383)
+ * and, for nb big-endian 48-byte strings at bytes48, fp_from_be_bytes(b, 12) as 14 words per
+ * string in out_limbs.  Either count may be 0 (its pointers are then not read).
+ *
+ * lsg_check_fp2_roots: n Fp2 elements (a0, a1) in Montgomery form, lazy limbs allowed
+ * (in[28 i ..] = a0, in[28 i + 14 ..] = a1), 58 words per item out, field values raw:
+ *    out[58 i +  0 .. 27]  the root fp2_sqrt leaves, (c0, c1) (a square root when bit 0 is set)
+ *    out[58 i + 28 .. 41]  fp_inv(a0), the fixed-exponent power
+ *    out[58 i + 42 .. 55]  pair_mont_mul(pair_inv_gcd(pair_canon(a0)), R^3): the divstep
+ *                          inversion as the batched inversions' roots run it
+ *    out[58 i + 56]        bit 0 fp2_sqrt's result, bit 1 fp2_sgn0(a), bit 2 fp2_lexi_largest(a),
+ *                          bit 3 fp2_is_zero(a)
+ *    out[58 i + 57]        0
+ * Both inverses x of a0 satisfy x a0 = 2^812 (mod p) as integers, and x = 0 (mod p) for a0 = 0.
+ *
+ * lsg_check_batch_inv: n raw elements in (14 words each), the n outputs of the host's batched
+ * inversion of them (the call the hash and key stages make) out, raw, same congruence; zeros
+ * in any representation come out as zero.
+ *
+ * lsg_check_map_uniform: lsg_hash_to_g2 from the expanded messages on: n x 256 caller-chosen
+ * "uniform bytes" (four 64-byte big-endian integers per item: u0.c0, u0.c1, u1.c0, u1.c1) take
+ * the place of expand_message_xmd's output; out192 receives the 192-byte uncompressed points
+ * (the infinity encoding where the sum of the two mapped points is the identity). */
+int lsg_check_canon(lsg_ctx* ctx, const uint32_t* in, size_t n, const uint8_t* bytes48, size_t nb, uint32_t* out,
+                    uint32_t* out_limbs);
+int lsg_check_fp2_roots(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+int lsg_check_batch_inv(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+int lsg_check_map_uniform(lsg_ctx* ctx, const uint8_t* ub256, size_t n, uint8_t* out192);
+
 /* Integer-VALU roofline probe: runs a throughput kernel of dependent-free 381-bit
  * Montgomery multiplications; reports Fp-mul/s and v_mad_u64_u32/s (x300 per mul). */
 int lsg_probe_fp_mul_rate(lsg_ctx* ctx, double* fp_mul_per_s, double* mad_per_s);

@@ -172,6 +172,7 @@ EXPORTS = [
     "lsg_signing_roots", "lsg_attestation_signing_roots", "lsg_jobs_partial_device", "lsg_final_submit_device",
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
     "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums",
+    "lsg_check_canon", "lsg_check_fp2_roots", "lsg_check_batch_inv", "lsg_check_map_uniform",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
     "lsg_object_signing_roots",
@@ -248,6 +249,10 @@ def load_library(path=LIB_PATH):
         lib.lsg_check_fp_sqr.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_fp2_sqr.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_sums.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_canon.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_char_p, ctypes.c_char_p]
+        lib.lsg_check_fp2_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_batch_inv.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_map_uniform.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_probe_mad_peak.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         for name in EXPORTS:
             if name != "lsg_last_error":
@@ -823,6 +828,42 @@ class Context:
         src = struct.pack(f"<{len(words)}I", *words)
         self._check(self.lib.lsg_check_sums(self.h, src, n, out), "lsg_check_sums")
         return list(struct.unpack(f"<{42 * 14 * n}I", out.raw))
+
+    def check_canon(self, words, strings=()):
+        """lsg_check_canon: `words` = 14 u32 per raw element, `strings` = 48-byte strings.  Returns
+        (54 u32 per element, 14 u32 per string); the word offsets are in lodestar_bls.h."""
+        n, nb = len(words) // 14, len(strings)
+        assert len(words) == 14 * n and all(len(b) == 48 for b in strings)
+        out = ctypes.create_string_buffer(4 * 54 * max(n, 1))
+        limbs = ctypes.create_string_buffer(4 * 14 * max(nb, 1))
+        src = struct.pack(f"<{len(words)}I", *words)
+        self._check(self.lib.lsg_check_canon(self.h, src, n, b"".join(strings), nb, out, limbs), "lsg_check_canon")
+        return (list(struct.unpack(f"<{54 * n}I", out.raw[:4 * 54 * n])),
+                list(struct.unpack(f"<{14 * nb}I", limbs.raw[:4 * 14 * nb])))
+
+    def check_fp2_roots(self, words):
+        """lsg_check_fp2_roots: `words` = 28 u32 per item (a0, a1); returns 58 u32 per item."""
+        n = len(words) // 28
+        assert len(words) == 28 * n
+        out = ctypes.create_string_buffer(4 * 58 * n)
+        src = struct.pack(f"<{len(words)}I", *words)
+        self._check(self.lib.lsg_check_fp2_roots(self.h, src, n, out), "lsg_check_fp2_roots")
+        return list(struct.unpack(f"<{58 * n}I", out.raw))
+
+    def check_batch_inv(self, words):
+        """lsg_check_batch_inv: `words` = 14 u32 per raw element; returns 14 u32 per element (raw)."""
+        return self._check_sqr("lsg_check_batch_inv", words, 14)
+
+    def check_map_uniform(self, items):
+        """lsg_check_map_uniform: `items` = 256-byte strings; returns the 192-byte points."""
+        n = len(items)
+        assert all(len(b) == 256 for b in items)
+        if not n:
+            return []
+        out = ctypes.create_string_buffer(192 * n)
+        self._check(self.lib.lsg_check_map_uniform(self.h, b"".join(items), n, out), "lsg_check_map_uniform")
+        raw = out.raw
+        return [raw[192 * i:192 * i + 192] for i in range(n)]
 
     def probe_fp_mul_rate(self):
         a, b = ctypes.c_double(), ctypes.c_double()

@@ -3891,6 +3891,87 @@ int lsg_check_sums(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
   return LSG_OK;
 }
 
+// the field-edge hooks (k_check_canon, k_check_from_bytes, k_check_fp2_roots, batch_inv, launch_hash)
+int lsg_check_canon(lsg_ctx* c, const uint32_t* in, size_t n, const uint8_t* bytes48, size_t nb, uint32_t* out,
+                    uint32_t* out_limbs) {
+  constexpr size_t WOUT = lsgk::CHECK_CANON_OUT;
+  if (!c || (n && (!in || !out)) || (nb && (!bytes48 || !out_limbs)) || n > 0x7fffffffull / (4 * WOUT) ||
+      nb > 0x7fffffffull / (4 * W_FP))
+    return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  Slot* s = &c->dev[0]->util;
+  timer_reset(s);
+  if (n) {
+    LSG_RC(ensure(s, s->d_aux, 4 * W_FP * n));
+    LSG_RC(ensure(s, s->d_Fb, 4 * WOUT * n));
+    LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, in, 4 * W_FP * n, hipMemcpyHostToDevice, s->st[0]));
+    KL(s, "k_check_canon", lsgk::check_canon(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+    LSG_HIP(s, hipMemcpyAsync(out, s->d_Fb.p, 4 * WOUT * n, hipMemcpyDeviceToHost, s->st[0]));
+    LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  }
+  if (nb) {
+    LSG_RC(ensure(s, s->d_aux, 48 * nb));
+    LSG_RC(ensure(s, s->d_Fb, 4 * W_FP * nb));
+    LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, bytes48, 48 * nb, hipMemcpyHostToDevice, s->st[0]));
+    KL(s, "k_check_from_bytes", lsgk::check_from_bytes(S_(s), (int)nb, P_<uint8_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+    LSG_HIP(s, hipMemcpyAsync(out_limbs, s->d_Fb.p, 4 * W_FP * nb, hipMemcpyDeviceToHost, s->st[0]));
+    LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  }
+  return LSG_OK;
+}
+
+int lsg_check_fp2_roots(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
+  constexpr size_t WOUT = lsgk::CHECK_ROOTS_OUT;
+  if (!c || (n && (!in || !out)) || n > 0x7fffffffull / (4 * WOUT)) return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  if (n == 0) return LSG_OK;
+  Slot* s = &c->dev[0]->util;
+  timer_reset(s);
+  LSG_RC(ensure(s, s->d_aux, 4 * 2 * W_FP * n));
+  LSG_RC(ensure(s, s->d_Fb, 4 * WOUT * n));
+  LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, in, 4 * 2 * W_FP * n, hipMemcpyHostToDevice, s->st[0]));
+  KL(s, "k_check_fp2_roots", lsgk::check_fp2_roots(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  LSG_HIP(s, hipMemcpyAsync(out, s->d_Fb.p, 4 * WOUT * n, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  return LSG_OK;
+}
+
+int lsg_check_batch_inv(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
+  if (!c || (n && (!in || !out)) || n > 0x7fffffffull / (4 * W_FP)) return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  if (n == 0) return LSG_OK;
+  Slot* s = &c->dev[0]->util;
+  timer_reset(s);
+  LSG_RC(ensure(s, s->d_aux, 4 * W_FP * n));
+  LSG_RC(ensure(s, s->d_Fb, 4 * W_FP * n));
+  LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, in, 4 * W_FP * n, hipMemcpyHostToDevice, s->st[0]));
+  LSG_RC(batch_inv(s, 0, "binv_check", P_<uint32_t>(s->d_aux), n, P_<uint32_t>(s->d_Fb)));
+  LSG_HIP(s, hipMemcpyAsync(out, s->d_Fb.p, 4 * W_FP * n, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  keep_times(s);
+  return LSG_OK;
+}
+
+// lsg_hash_to_g2 from the expanded messages on: the caller's 256 "uniform bytes" per item
+int lsg_check_map_uniform(lsg_ctx* c, const uint8_t* ub256, size_t n, uint8_t* out192) {
+  if (!c || (n && (!ub256 || !out192)) || n > 0x7fffffffull / 256) return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  if (n == 0) return LSG_OK;
+  Slot* s = &c->dev[0]->util;
+  timer_reset(s);
+  LSG_RC(size_state(s, n, 0, 1, 0));
+  LSG_RC(ensure(s, s->d_aux, 192 * n));
+  LSG_HIP(s, hipMemcpyAsync(s->d_ub.p, ub256, 256 * n, hipMemcpyHostToDevice, s->st[0]));
+  const int nn = (int)n;
+  LSG_RC(launch_hash(s, nn, P_<uint32_t>(s->d_H), P_<uint8_t>(s->d_hinf)));
+  KL(s, "k_g2a_to_bytes",
+     lsgk::g2a_to_bytes(S_(s), nn, P_<uint32_t>(s->d_H), P_<uint8_t>(s->d_hinf), P_<uint8_t>(s->d_aux)));
+  LSG_HIP(s, hipMemcpyAsync(out192, s->d_aux.p, 192 * n, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  keep_times(s);
+  return LSG_OK;
+}
+
 int lsg_probe_fp_mul_rate(lsg_ctx* c, double* fp_mul_per_s, double* mad_per_s) {
   if (!c || !fp_mul_per_s || !mad_per_s) return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);

@@ -326,6 +326,55 @@ __global__ void LSG_KERNEL_ATTR k_check_sums(int n, const uint32_t* __restrict__
   put2(fp2_sub(fp2_sub(t2c, t0c), fp2_mul_xi(fp2_add(el2(7), el2(9)))));
 }
 
+// parity hooks of the layer between the products and the accept / reject rules: canonical
+// forms, the predicates on them, the byte conversions, the Fp2 root and the two inversions,
+// on caller-chosen raw limbs.  Every output comes from the function the kernels call.
+// k_check_canon: one raw element per item in, LSG_CHECK_CANON_OUT words per item out:
+//    0..13  pair_canon(a)      14..27  fp_canonical(a)     28..39  fp_to_be48(fp_canonical(a))
+//   40      bit 0 fp_is_zero(a), 1 fp_canon_lt_p(a), 2 fp_canon_gt_half(a), 3 fp_canon_parity(a)
+//   41      0           42..53  fp_to_be48(a): the raw value's bytes (a in [0, 2^384), flag bits kept)
+constexpr int LSG_CHECK_CANON_OUT = lsgk::CHECK_CANON_OUT;
+__global__ void LSG_KERNEL_ATTR k_check_canon(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  const fp_t a = lane_load<fp_t>(in, item);
+  uint32_t* o = out + (size_t)LSG_CHECK_CANON_OUT * item;
+  const fp_t c = fp_canonical(a);
+  lane_store(o, 0, pair_canon(a));
+  lane_store(o + 14, 0, c);
+  fp_to_be48((uint8_t*)(o + 28), c);
+  fp_to_be48((uint8_t*)(o + 42), a);
+  const uint32_t f = (fp_is_zero(a) ? 1u : 0u) | (fp_canon_lt_p(a) ? 2u : 0u) | (fp_canon_gt_half(a) ? 4u : 0u) |
+                     (fp_canon_parity(a) ? 8u : 0u);
+  o[40 + (lead ? 0 : 1)] = lead ? f : 0u;
+}
+// k_check_from_bytes: 48 big-endian bytes per item in, fp_from_be_bytes(b, 12) out (14 words)
+__global__ void LSG_KERNEL_ATTR k_check_from_bytes(int n, const uint8_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  (void)lead;
+  lane_store(out, item, fp_from_be_bytes(in + 48 * item, 12));
+}
+// k_check_fp2_roots: (a0, a1) in Montgomery form (lazy limbs allowed) per item in,
+// LSG_CHECK_ROOTS_OUT words per item out:
+//    0..27  the root fp2_sqrt leaves (c0, c1), raw      28..41  fp_inv(a0), raw
+//   42..55  pair_mont_mul(pair_inv_gcd(pair_canon(a0)), FP_RCUBE), raw (k_binv_root, block_inv)
+//   56      bit 0 fp2_sqrt's result, 1 fp2_sgn0(a), 2 fp2_lexi_largest(a), 3 fp2_is_zero(a)
+//   57      0
+constexpr int LSG_CHECK_ROOTS_OUT = lsgk::CHECK_ROOTS_OUT;
+__global__ void LSG_KERNEL_ATTR k_check_fp2_roots(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  const fp2_t a(lane_load<fp_t>(in, 2 * item), lane_load<fp_t>(in, 2 * item + 1));
+  uint32_t* o = out + (size_t)LSG_CHECK_ROOTS_OUT * item;
+  fp2_t r;
+  const bool ok = fp2_sqrt(r, a);
+  lane_store(o, 0, r.c0);
+  lane_store(o + 14, 0, r.c1);
+  lane_store(o + 28, 0, fp_inv(a.c0));
+  lane_store(o + 42, 0, pair_mont_mul(pair_inv_gcd(pair_canon(a.c0)), fp_t(FP_RCUBE)));
+  const uint32_t f = (ok ? 1u : 0u) | (fp2_sgn0(a) ? 2u : 0u) | (fp2_lexi_largest(a) ? 4u : 0u) |
+                     (fp2_is_zero(a) ? 8u : 0u);
+  o[56 + (lead ? 0 : 1)] = lead ? f : 0u;
+}
+
 // roofline probe: 4 independent limb-parallel Montgomery chains per pair
 __global__ void LSG_KERNEL_ATTR k_probe_fp_mul(int n, int iters, uint32_t* __restrict__ io) {
   LANE_ITEM(n);
@@ -405,6 +454,15 @@ hipError_t check_fp2_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* ou
 }
 hipError_t check_sums(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
   LSG_LAUNCH_ITEMS(k_check_sums, n, st, n, in, out);
+}
+hipError_t check_canon(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_canon, n, st, n, in, out);
+}
+hipError_t check_from_bytes(hipStream_t st, int n, const uint8_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_from_bytes, n, st, n, in, out);
+}
+hipError_t check_fp2_roots(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_fp2_roots, n, st, n, in, out);
 }
 hipError_t probe_fp_mul(hipStream_t st, int items, int iters, uint32_t* io) {
   LSG_LAUNCH_ITEMS(k_probe_fp_mul, items, st, items, iters, io);

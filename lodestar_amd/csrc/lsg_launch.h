@@ -162,5 +162,10 @@ hipError_t check_fp2_mul(hipStream_t st, int n, const uint32_t* in, uint32_t* ou
 hipError_t check_fp_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t check_fp2_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t check_sums(hipStream_t st, int n, const uint32_t* in, uint32_t* out);  // 12 elements in, 42 out per item
+// the field-edge hooks (lodestar_bls.h lsg_check_canon, lsg_check_fp2_roots)
+constexpr int CHECK_CANON_OUT = 54, CHECK_ROOTS_OUT = 58;  // words per item out
+hipError_t check_canon(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
+hipError_t check_from_bytes(hipStream_t st, int n, const uint8_t* in48, uint32_t* out);
+hipError_t check_fp2_roots(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t probe_mad(hipStream_t st, int blocks, int iters, uint32_t seed, uint64_t* io);
 }  // namespace lsgk

@@ -644,10 +644,12 @@ static void g1p_to_aff(fp* x, fp* y, const g1p* p) {
 /* ------------------------------------------------------------------ (de)serialisation (ZCash) */
 enum { E_OK = 0, E_BAD_ENCODING = 1, E_NOT_ON_CURVE = 2, E_NOT_IN_GROUP = 3, E_PK_INF = 6, E_INVALID_SIZE = 10 };
 
-static int read_fp48(fp* r, const uint8_t* b) {
+/* flags: the first coordinate of an encoding, whose top 3 bits are the ZCash flags (blst masks
+ * only these; every other coordinate is compared with p as all 384 bits) */
+static int read_fp48(fp* r, const uint8_t* b, int flags) {
   uint64_t v[6];
   be_to_limbs(v, b, 48);
-  v[5] &= (1ull << 61) - 1; /* the 3 flag bits */
+  if (flags) v[5] &= (1ull << 61) - 1;
   if (!lt_p(v)) return E_BAD_ENCODING;
   fp_from_canon(r, v);
   return E_OK;
@@ -667,7 +669,7 @@ static int g2_decode_sig(fp2* x, fp2* y, int* inf, const uint8_t* b, size_t len)
     return E_OK;
   }
   int e;
-  if ((e = read_fp48(&x->c1, b)) || (e = read_fp48(&x->c0, b + 48))) return e;
+  if ((e = read_fp48(&x->c1, b, 1)) || (e = read_fp48(&x->c0, b + 48, 0))) return e;
   fp2 rhs, t, b2;
   f2_sqr(&t, x);
   f2_mul(&rhs, &t, x);
@@ -697,7 +699,7 @@ static int g1_decode_pk(fp* x, fp* y, int* inf, const uint8_t* b) {
   }
   if (in0 & 0x20) return E_BAD_ENCODING;
   int e;
-  if ((e = read_fp48(x, b)) || (e = read_fp48(y, b + 48))) return e;
+  if ((e = read_fp48(x, b, 1)) || (e = read_fp48(y, b + 48, 0))) return e;
   fp l, r, t, four = C_ONE;
   fp_add(&four, &four, &four);
   fp_add(&four, &four, &four);

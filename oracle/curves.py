@@ -219,9 +219,13 @@ def g2_serialize(Pt):
     return _fp_to_be(x[1]) + _fp_to_be(x[0]) + _fp_to_be(y[1]) + _fp_to_be(y[0])
 
 
-def _be_fp(b):
-    """Parse 48 big-endian bytes with the top 3 bits cleared; return int or raise BAD_ENCODING if >= p."""
-    v = int.from_bytes(b, "big") & ((1 << 381) - 1)
+def _be_fp(b, flags=False):
+    """Parse 48 big-endian bytes; return int or raise BAD_ENCODING if >= p.  flags: the first
+    coordinate of an encoding, whose top 3 bits are the ZCash flags and are cleared (blst masks
+    only these: every other coordinate is compared with p as all 384 bits)."""
+    v = int.from_bytes(b, "big")
+    if flags:
+        v &= (1 << 381) - 1
     if v >= P:
         raise BlstError(BLST_BAD_ENCODING)
     return v
@@ -236,7 +240,7 @@ def g1_uncompress(b):
         if (in0 & 0x3F) == 0 and not any(b[1:48]):
             return None
         raise BlstError(BLST_BAD_ENCODING)
-    x = _be_fp(b[:48])
+    x = _be_fp(b[:48], flags=True)
     y = fp_sqrt(x * x * x + B1)
     if y is None:
         raise BlstError(BLST_POINT_NOT_ON_CURVE)
@@ -262,7 +266,7 @@ def g1_deserialize(b):
         raise BlstError(BLST_BAD_ENCODING)
     if in0 & 0x20:
         raise BlstError(BLST_BAD_ENCODING)
-    x = _be_fp(b[:48])
+    x = _be_fp(b[:48], flags=True)
     y = _be_fp(b[48:96])
     Pt = (x, y)
     if not E1.on_curve(Pt):
@@ -281,7 +285,7 @@ def g2_uncompress(b):
         if (in0 & 0x3F) == 0 and not any(b[1:96]):
             return None
         raise BlstError(BLST_BAD_ENCODING)
-    x1 = _be_fp(b[:48])
+    x1 = _be_fp(b[:48], flags=True)
     x0 = _be_fp(b[48:96])
     x = (x0, x1)
     rhs = f2_add(f2_mul(f2_sqr(x), x), B2)
@@ -310,7 +314,7 @@ def g2_deserialize(b):
         raise BlstError(BLST_BAD_ENCODING)
     if in0 & 0x20:
         raise BlstError(BLST_BAD_ENCODING)
-    x = (_be_fp(b[48:96]), _be_fp(b[0:48]))
+    x = (_be_fp(b[48:96]), _be_fp(b[0:48], flags=True))
     y = (_be_fp(b[144:192]), _be_fp(b[96:144]))
     Pt = (x, y)
     if not E2.on_curve(Pt):

@@ -439,3 +439,106 @@ void hc_pair_fp2_mul_raw(const int32_t* a, const int32_t* b, int32_t* out) {
 }
 }
 #endif
+
+#ifdef LSG_HOSTCHECK_PAIR
+// ---- the field-edge tables (tests/field_edges.py) on raw limbs: the one-lane form of what the
+// device hooks lsg_check_canon / lsg_check_fp2_roots / lsg_check_batch_inv /
+// lsg_check_map_uniform run (14 signed limbs per element, limb k at word k)
+#include <algorithm>
+#include <vector>
+#include "lsg_layout.h"  // LSG_BINV_T
+static fp_t hc_raw(const int32_t* w) {
+  fp_t a;
+  for (int k = 0; k < 14; k++) a.l[k] = (uint32_t)w[k];
+  return a;
+}
+static void hc_raw_out(int32_t* w, const fp_t& a) {
+  for (int k = 0; k < 14; k++) w[k] = (int32_t)a.l[k];
+}
+static fp_t hc_binv_root(const fp_t& x) {  // k_binv_root, block_inv
+  return pair_mont_mul(pair_inv_gcd(pair_canon(x)), fp_t(FP_RCUBE));
+}
+// The recurrences of k_binv_fold / k_binv_unfold (lsg_k_reduce.hip) restated: chunks of T
+// values fold into prefix products, the chunk products are the next level's values, one root
+// inversion, and the unfold back down.  zero_to_one holds at level 0 only, as in batch_inv.
+static std::vector<fp_t> hc_binv(const std::vector<fp_t>& v, size_t T, bool zero_to_one) {
+  const size_t n = v.size();
+  if (n == 1) return {hc_binv_root(v[0])};
+  const size_t chunks = (n + T - 1) / T;
+  const fp_t one = fp_one();
+  std::vector<fp_t> pre(n), tot(chunks), out(n);
+  for (size_t c = 0; c < chunks; c++) {
+    const size_t first = c * T, last = std::min(n, first + T);
+    fp_t acc = one;
+    for (size_t k = first; k < last; k++) {
+      fp_t x = v[k];
+      if (zero_to_one) x = fp_select(fp_is_zero(x), one, x);
+      acc = k == first ? x : fp_mul(acc, x);
+      pre[k] = acc;
+    }
+    tot[c] = acc;
+  }
+  const std::vector<fp_t> tinv = hc_binv(tot, T, false);
+  for (size_t c = 0; c < chunks; c++) {
+    const size_t first = c * T, last = std::min(n, first + T);
+    fp_t acc = tinv[c];
+    for (size_t k = last; k-- > first;) {
+      const fp_t x = v[k];
+      const bool z = zero_to_one && fp_is_zero(x);
+      const fp_t r = k > first ? fp_mul(acc, pre[k - 1]) : acc;
+      out[k] = z ? fp_zero() : r;
+      if (k > first && !z) acc = fp_mul(acc, x);
+    }
+  }
+  return out;
+}
+extern "C" {
+// out: pair_canon, fp_canonical (14 words each), be48 of the latter, be48 of a itself; returns the flag word of
+// lsg_check_canon
+uint32_t hc_canon(const int32_t* a14, int32_t* canon14, int32_t* canonical14, uint8_t* be48, uint8_t* raw48) {
+  const fp_t a = hc_raw(a14), c = fp_canonical(a);
+  hc_raw_out(canon14, pair_canon(a));
+  hc_raw_out(canonical14, c);
+  fp_to_be48(be48, c);
+  fp_to_be48(raw48, a);
+  return (fp_is_zero(a) ? 1u : 0u) | (fp_canon_lt_p(a) ? 2u : 0u) | (fp_canon_gt_half(a) ? 4u : 0u) |
+         (fp_canon_parity(a) ? 8u : 0u);
+}
+void hc_from_be48(const uint8_t* b48, int32_t* out14) { hc_raw_out(out14, fp_from_be_bytes(b48, 12)); }
+// out56: root (c0, c1), fp_inv(a0), the divstep form; returns the flag word of lsg_check_fp2_roots
+uint32_t hc_fp2_roots(const int32_t* a28, int32_t* out56) {
+  const fp2_t a(hc_raw(a28), hc_raw(a28 + 14));
+  fp2_t r;
+  const bool ok = fp2_sqrt(r, a);
+  hc_raw_out(out56, r.c0);
+  hc_raw_out(out56 + 14, r.c1);
+  hc_raw_out(out56 + 28, fp_inv(a.c0));
+  hc_raw_out(out56 + 42, hc_binv_root(a.c0));
+  return (ok ? 1u : 0u) | (fp2_sgn0(a) ? 2u : 0u) | (fp2_lexi_largest(a) ? 4u : 0u) | (fp2_is_zero(a) ? 8u : 0u);
+}
+int hc_batch_inv(const int32_t* in, int n, int T, int32_t* out) {
+  if (n < 1 || T < 2) return -1;  // (a level has to shrink)
+  std::vector<fp_t> v((size_t)n);
+  for (int i = 0; i < n; i++) v[(size_t)i] = hc_raw(in + 14 * i);
+  const std::vector<fp_t> r = hc_binv(v, (size_t)T, true);
+  for (int i = 0; i < n; i++) hc_raw_out(out + 14 * i, r[(size_t)i]);
+  return 0;
+}
+// the device stages from the uniform bytes on (k_h2c_prep, the batched inversion of the two
+// norms, k_h2c_map, the clearing, the inversion of N(Z), k_h2c_affine, k_g2a_to_bytes)
+void hc_map_uniform(const uint8_t* ub, uint8_t* out192) {
+  const fp2_t u0 = fp2_make(fp_from_be64_mod(ub), fp_from_be64_mod(ub + 64));
+  const fp2_t u1 = fp2_make(fp_from_be64_mod(ub + 128), fp_from_be64_mod(ub + 192));
+  const std::vector<fp_t> ni = hc_binv({fp2_norm(sswu_tv1(u0)), fp2_norm(sswu_tv1(u1))}, LSG_BINV_T, true);
+  const g2p_t q = clear_cofactor_g2(g2_add(iso_map3(map_to_curve_sswu_ni(u0, ni[0])), iso_map3(map_to_curve_sswu_ni(u1, ni[1]))));
+  const bool inf = proj_is_inf(q);
+  g2a_t a = {fp2_zero(), fp2_zero()};
+  if (!inf) {
+    const fp2_t zi = fp2_inv_with_norm_inv(q.Z, hc_binv({fp2_norm(q.Z)}, LSG_BINV_T, true)[0]);
+    a.x = fp2_mul(q.X, zi);
+    a.y = fp2_mul(q.Y, zi);
+  }
+  g2_serialize(out192, a, inf);
+}
+}
+#endif

@@ -620,6 +620,107 @@ def test_pubkey_validate_matches_oracle(ctx):
                 assert out == g1_serialize(pt)
 
 
+# ---- decode boundaries through the public entry points: x at 0, at p and at the top of the
+# field's 381 bits with both sign flags, and uncompressed y at p - y and y + p; expectations live
+# from oracle/verifier.py
+def _edge_x():
+    from oracle.fields import P
+    return [0, 1, 2, 3, P - 1, P, P + 1, (1 << 381) - 1]
+
+
+def _oracle_code(fn, b):
+    try:
+        return 0, fn(b)
+    except BlstError as e:
+        return e.code, None
+
+
+def _flagged(body, sign):
+    b = bytearray(body)
+    b[0] |= 0x80 | (0x20 if sign else 0)
+    return bytes(b)
+
+
+def test_pubkey_validate_compressed_x_boundaries(ctx):
+    pks = [_flagged(x.to_bytes(48, "big"), s) for x in _edge_x() for s in (0, 1)]
+    exp = [_oracle_code(ov.public_key_validate, pk) for pk in pks]
+    assert {c for c, _ in exp} >= {1, 2, 3}
+    for pk, (out, err), (code, pt) in zip(pks, ctx.pubkey_validate(pks), exp):
+        assert err == code, (pk.hex(), err, code)
+        if code == 0:
+            assert out == g1_serialize(pt)
+
+
+def test_sig_decode_compressed_x_boundaries(ctx):
+    zero = bytes(48)
+    sigs = [_flagged(c1 + c0, s) for x in _edge_x() for s in (0, 1)
+            for c1, c0 in ((zero, x.to_bytes(48, "big")), (x.to_bytes(48, "big"), zero))]
+    exp = [_oracle_code(ov.signature_from_bytes, sg) for sg in sigs]
+    assert {c for c, _ in exp} >= {1, 2, 3}
+    for sg, (out, err), (code, pt) in zip(sigs, ctx.sig_decode(sigs), exp):
+        assert err == code, (sg.hex(), err, code)
+        if code == 0:
+            assert out == g2_serialize(pt)
+
+
+def _multiples(curve, gen, n):
+    out, pt = [], gen
+    for _ in range(n):
+        out.append(pt)
+        pt = curve.add(pt, gen)
+    return out
+
+
+def test_uncompressed_y_boundaries(ctx):
+    """(x, p - y) decodes, as -P; a coordinate plus p is BLST_BAD_ENCODING.  Only the first
+    coordinate of an encoding carries flag bits: in every other one bit 381 is part of the
+    number (blst compares all 384 bits with p), so y + p is rejected whether or not the sum
+    reaches 2^381.  The first eight multiples of each generator give sums on both sides."""
+    from oracle.curves import E2, G1_GEN, G2_GEN
+    from oracle.fields import P
+    be = lambda v: int(v).to_bytes(48, "big")  # noqa: E731
+    # G1, 96 bytes, through KeyValidate
+    pts = _multiples(E1, G1_GEN, 8)
+    assert {(y + P) >> 381 for _, y in pts} == {0, 1}
+    pks = [b for x, y in pts for b in (be(x) + be(P - y), be(x) + be(y + P))]
+    got = ctx.pubkey_validate(pks)
+    exp = [_oracle_code(ov.public_key_validate, pk) for pk in pks]
+    assert [c for c, _ in exp] == [0, 1] * 8 and [e for _, e in got] == [0, 1] * 8, (got, exp)
+    for k, (x, y) in enumerate(pts):
+        assert got[2 * k][0] == g1_serialize((x, P - y)) == g1_serialize(exp[2 * k][1])
+    # G2, 192 bytes (x.c1, x.c0, y.c1, y.c0), through Signature.fromBytes
+    pts = _multiples(E2, G2_GEN, 8)
+    assert {(c + P) >> 381 for _, y in pts for c in y} == {0, 1} == {(x[0] + P) >> 381 for x, _ in pts}
+    sigs = []
+    for x, y in pts:
+        xb = be(x[1]) + be(x[0])
+        sigs += [xb + be(P - y[1]) + be(P - y[0]), xb + be(y[1]) + be(y[0] + P), xb + be(y[1] + P) + be(y[0]),
+                 be(x[1]) + be(x[0] + P) + be(y[1]) + be(y[0])]
+    got = ctx.sig_decode(sigs)
+    exp = [_oracle_code(ov.signature_from_bytes, sg) for sg in sigs]
+    assert [c for c, _ in exp] == [0, 1, 1, 1] * 8 and [e for _, e in got] == [0, 1, 1, 1] * 8, (got, exp)
+    for k, (x, y) in enumerate(pts):
+        assert got[4 * k][0] == g2_serialize((x, (P - y[0], P - y[1]))) == g2_serialize(exp[4 * k][1])
+
+
+def test_compressed_x_c0_plus_p_is_bad_encoding(ctx):
+    """x.c0 of a compressed signature is the encoding's second coordinate: x.c0 + p is
+    BLST_BAD_ENCODING with and without bit 381 in the sum"""
+    from oracle.curves import E2, G2_GEN, g2_compress
+    from oracle.fields import P
+    pts = _multiples(E2, G2_GEN, 8)
+    assert {(x[0] + P) >> 381 for x, _ in pts} == {0, 1}
+    sigs = []
+    for pt in pts:
+        c = g2_compress(pt)
+        sigs += [c, c[:48] + (pt[0][0] + P).to_bytes(48, "big")]
+    got = ctx.sig_decode(sigs)
+    exp = [_oracle_code(ov.signature_from_bytes, sg) for sg in sigs]
+    assert [c for c, _ in exp] == [0, 1] * 8 and [e for _, e in got] == [0, 1] * 8, (got, exp)
+    for k, pt in enumerate(pts):
+        assert got[2 * k][0] == g2_serialize(pt)
+
+
 def test_aggregate_signatures_matches_golden(ctx):
     """Op-pool Signature.aggregate: every golden case of one encoding in one
     batched call, plus an empty group, against the oracle's fixture."""

@@ -19,26 +19,7 @@ from oracle.curves import (
 from oracle import hash_to_curve as h2c
 from oracle.pairing import miller_loop_fast, final_exp_fast
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-SRC = os.path.join(HERE, "native", "hostcheck.hip")
-# host builds of the generic math over two Fp backends: "elem" (12 x 32-bit limbs, fully
-# reduced, lsg_fp_elem.hpp) and "pair" (the pair backend's lazy signed 14 x 29-bit limbs,
-# lsg_fp_pair.hpp with all limbs in one lane)
-LIBS = {"elem": (os.path.join(HERE, "native", "libhostcheck.so"), []),
-        "pair": (os.path.join(HERE, "native", "libhostcheck_pair.so"), ["-DLSG_HOSTCHECK_PAIR"])}
-
-
-def _build(backend):
-    lib, defs = LIBS[backend]
-    hdrs = [os.path.join(ROOT, "lodestar_amd", "csrc", f) for f in os.listdir(os.path.join(ROOT, "lodestar_amd", "csrc"))]
-    newest = max(os.path.getmtime(p) for p in hdrs + [SRC])
-    if os.path.exists(lib) and os.path.getmtime(lib) >= newest:
-        return lib
-    from lodestar_amd.build import hipcc  # (as build(): PATH, else the ROCm install's own)
-    subprocess.check_call([hipcc(), "-x", "hip", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-shared"] + defs +
-                          ["-I", os.path.join(ROOT, "lodestar_amd", "csrc"), SRC, "-o", lib])
-    return lib
+from tests.hostcheck_lib import HERE, build as _build  # the host builds of the two Fp backends
 
 
 @pytest.fixture(scope="module", params=["elem", "pair"])
