@@ -497,6 +497,26 @@ int lsg_check_fp2_sqr(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out)
  * carries at every operation beside it (lsg_k_reduce.hip k_check_sums lists the slots).  Not
  * on the verification path. */
 int lsg_check_sums(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+/* Parity hooks of the Fp2 layout with one component per lane (the [x] chains of k_sig_subgroup
+ * and k_h2c_clear; tests only, not on the verification path).  Elements travel in the pair
+ * layout above, raw in and raw out; Fp2 value X_j of an item is its elements (2 j, 2 j + 1).
+ *
+ * lsg_check_fp2_lanes: 12 elements per item in (A, B, C, D, E, F = X_0 .. X_5), 24 per item out.
+ * Y_j = out elements (24 i + 2 j, 24 i + 2 j + 1), converted back to the pair layout:
+ *    Y_0  A through the conversion in and out (the same words)
+ *    Y_1  A B / 2^406          Y_2  A^2 / 2^406         (mod p, the leaves' normalised limbs)
+ *    Y_3  (A + B + C - D - E - F) carried once
+ *    Y_4 .. Y_8  2A, 3A, 4A, 8A, 12A (carry_mul)
+ *    Y_9  12 (1 + u) A         Y_10  -A
+ * and out words (24 i + 22) * 14 .. + 27: A as the lanes hold it, word k of lane h (0: even, 1:
+ * odd lane of the item's pair) at 2 k + h -- limb k of c0 on lane 0, of c1 on lane 1.
+ *
+ * lsg_check_g2_lanes: 12 elements per item in: a Jacobian point J = (X_0, X_1, X_2) and a
+ * homogeneous point Q = (X_3, X_4, X_5); 24 per item out: jac_dbl(J) computed in the lane
+ * layout (Y_0 .. Y_2), in the pair layout (Y_3 .. Y_5), jac_add_proj(J, Q) in the lane layout
+ * (Y_6 .. Y_8), in the pair layout (Y_9 .. Y_11). */
+int lsg_check_fp2_lanes(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+int lsg_check_g2_lanes(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
 /* Parity hooks of the layer between the products and the accept / reject rules (tests only;
  * none is on the verification path).  Elements travel in the pair layout above: 14 words, limb
  * L at word 2 (L mod 7) + L / 7.  Each returns LSG_ERR_INVALID_ARG for a null pointer with a

@@ -171,7 +171,7 @@ EXPORTS = [
     "lsg_final_submit_groups", "lsg_final_wait_groups", "lsg_aggregate_signatures",
     "lsg_signing_roots", "lsg_attestation_signing_roots", "lsg_jobs_partial_device", "lsg_final_submit_device",
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
-    "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums",
+    "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums", "lsg_check_fp2_lanes", "lsg_check_g2_lanes",
     "lsg_check_canon", "lsg_check_fp2_roots", "lsg_check_batch_inv", "lsg_check_map_uniform",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
@@ -249,6 +249,8 @@ def load_library(path=LIB_PATH):
         lib.lsg_check_fp_sqr.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_fp2_sqr.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_sums.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_fp2_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_g2_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_canon.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_char_p, ctypes.c_char_p]
         lib.lsg_check_fp2_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_batch_inv.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
@@ -828,6 +830,23 @@ class Context:
         src = struct.pack(f"<{len(words)}I", *words)
         self._check(self.lib.lsg_check_sums(self.h, src, n, out), "lsg_check_sums")
         return list(struct.unpack(f"<{42 * 14 * n}I", out.raw))
+
+    def _check_lanes(self, fn, words):
+        n = len(words) // (12 * 14)
+        assert len(words) == 12 * 14 * n
+        out = ctypes.create_string_buffer(4 * 24 * 14 * n)
+        src = struct.pack(f"<{len(words)}I", *words)
+        self._check(getattr(self.lib, fn)(self.h, src, n, out), fn)
+        return list(struct.unpack(f"<{24 * 14 * n}I", out.raw))
+
+    def check_fp2_lanes(self, words):
+        """lsg_check_fp2_lanes: `words` = 12 x 14 u32 per item; returns 24 x 14 u32 per item (raw;
+        the slots are in lodestar_bls.h)."""
+        return self._check_lanes("lsg_check_fp2_lanes", words)
+
+    def check_g2_lanes(self, words):
+        """lsg_check_g2_lanes: `words` = 12 x 14 u32 per item; returns 24 x 14 u32 per item (raw)."""
+        return self._check_lanes("lsg_check_g2_lanes", words)
 
     def check_canon(self, words, strings=()):
         """lsg_check_canon: `words` = 14 u32 per raw element, `strings` = 48-byte strings.  Returns

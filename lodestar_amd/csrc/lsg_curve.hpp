@@ -43,6 +43,14 @@ template <> LSG_INL fp2_t fzero<fp2_t>() { return fp2_zero(); }
 template <class F> LSG_INL F fone();
 template <> LSG_INL fp_t fone<fp_t>() { return FP_ONE; }
 template <> LSG_INL fp2_t fone<fp2_t>() { return fp2_one(); }
+#ifdef LSG_PAIR_MODE
+// Fp2 with one component per lane (fp2v_t) behind the same names: the G2 [x] chains
+#include "lsg_fp2_lanes.hpp"
+#endif
+#ifdef LSG_FP2_LANES
+template <> LSG_INL fp2v_t fzero<fp2v_t>() { return fp2v_from_const(fpc_t{}, fpc_t{}); }
+template <> LSG_INL fp2v_t fone<fp2v_t>() { return fp2v_from_const(FP_ONE, fpc_t{}); }
+#endif
 
 template <class F>
 struct aff_t {
@@ -258,6 +266,38 @@ LSG_INL g1p_t gadd(const g1p_t& p, const g1p_t& q) { return g1_add(p, q); }
 LSG_INL g2p_t gadd(const g2p_t& p, const g2p_t& q) { return g2_add(p, q); }
 LSG_INL g1p_t gdbl(const g1p_t& p) { return g1_dbl(p); }
 LSG_INL g2p_t gdbl(const g2p_t& p) { return g2_dbl(p); }
+#ifdef LSG_FP2_LANES
+// G2 points with their coordinates in the component-per-lane layout: the same formulas
+typedef aff_t<fp2v_t> g2va_t;
+typedef proj_t<fp2v_t> g2vp_t;
+LSG_BIGFN g2vp_t g2v_add(g2vp_t p, g2vp_t q) { return proj_add(p, q); }
+LSG_INL g2vp_t gadd(const g2vp_t& p, const g2vp_t& q) { return g2v_add(p, q); }
+LSG_INL g2va_t g2v_from_pair(const g2a_t& a) { return g2va_t{fp2v_from_pair(a.x), fp2v_from_pair(a.y)}; }
+LSG_INL g2vp_t g2v_from_pair(const g2p_t& p) {
+  return g2vp_t{fp2v_from_pair(p.X), fp2v_from_pair(p.Y), fp2v_from_pair(p.Z)};
+}
+LSG_INL g2p_t g2_to_pair(const g2vp_t& p) {
+  g2p_t r;
+  r.X = fp2v_to_pair(p.X);
+  r.Y = fp2v_to_pair(p.Y);
+  r.Z = fp2v_to_pair(p.Z);
+  return r;
+}
+#endif
+LSG_INL const g2p_t& g2_to_pair(const g2p_t& p) { return p; }
+// an affine G2 point read in the pair form (the global layout), in the layout F of a chain
+template <class F> struct g2_layout;
+template <> struct g2_layout<fp2_t> {
+  static LSG_INL g2a_t in(const g2a_t& a) { return a; }
+};
+#ifdef LSG_FP2_LANES
+template <> struct g2_layout<fp2v_t> {
+  static LSG_INL g2va_t in(const g2a_t& a) { return g2v_from_pair(a); }
+};
+typedef fp2v_t chain_fp2_t;  // the layout of k_sig_subgroup's [x] chain
+#else
+typedef fp2_t chain_fp2_t;
+#endif
 
 // ---- Jacobian doubling chains.  A doubling in Jacobian coordinates (x = X/Z^2, y = Y/Z^3;
 // dbl-2009-l, a = 0: 1M + 5S) costs 13 Fp multiplications over Fp2 against 22 for the
@@ -312,6 +352,9 @@ LSG_INL jac_t<F> jac_dbl_t(const jac_t<F>& p) {
 }
 LSG_BIGFN jac_t<fp_t> jac_dbl(jac_t<fp_t> p) { return jac_dbl_t(p); }
 LSG_BIGFN jac_t<fp2_t> jac_dbl(jac_t<fp2_t> p) { return jac_dbl_t(p); }
+#ifdef LSG_FP2_LANES
+LSG_BIGFN jac_t<fp2v_t> jac_dbl(jac_t<fp2v_t> p) { return jac_dbl_t(p); }
+#endif
 
 // acc (Jacobian) + q (homogeneous) through the complete RCB addition
 template <class F>
@@ -405,6 +448,34 @@ LSG_INL proj_t<F> proj_mul_xabs_get(const G& get) {
   }
   return jac_to_proj(acc);
 }
+#ifdef LSG_FP2_LANES
+// The same chain over Fp2 with only its 63 doublings in the component-per-lane layout
+// (lsg_fp2_lanes.hpp): the accumulator crosses to the pair form for each of the 5 complete
+// additions and back.  For k_h2c_clear, which has no register to spare at its additions (two
+// points live): with them in the lane layout it needed scratch.  get() and the result are in the
+// pair form.
+LSG_INL jac_t<fp2v_t> jac_from_pair(const jac_t<fp2_t>& p) {
+  return jac_t<fp2v_t>{fp2v_from_pair(p.X), fp2v_from_pair(p.Y), fp2v_from_pair(p.Z)};
+}
+LSG_INL jac_t<fp2_t> jac_to_pair(const jac_t<fp2v_t>& p) {
+  jac_t<fp2_t> r;
+  r.X = fp2v_to_pair(p.X);
+  r.Y = fp2v_to_pair(p.Y);
+  r.Z = fp2v_to_pair(p.Z);
+  return r;
+}
+template <class G>
+LSG_INL g2p_t g2_mul_xabs_get_dbl_lanes(const G& get) {
+  const uint64_t xa = ((uint64_t)LSG_X_ABS_HI << 32) | LSG_X_ABS_LO;
+  jac_t<fp2v_t> acc = jac_from_pair(jac_from_proj(get()));
+#pragma unroll 1
+  for (int b = 62; b >= 0; b--) {
+    acc = jac_dbl(acc);
+    if ((xa >> b) & 1u) acc = jac_from_pair(jac_add_proj(jac_to_pair(acc), get()));
+  }
+  return jac_to_proj(jac_to_pair(acc));
+}
+#endif
 template <class F>
 LSG_INL proj_t<F> proj_mul_xabs(const proj_t<F>& p) {
   return proj_mul_xabs_get<F>([&]() { return p; });
@@ -443,11 +514,12 @@ LSG_INL g2p_t g2_psi2(const g2p_t& p) {
 }
 
 // Scott's G2 membership test: psi(P) == [x]P (x < 0)
-template <class G>
+// (F: the layout the chain runs in, get()'s coordinates; the comparison is in the pair form)
+template <class F = fp2_t, class G>
 LSG_INL bool g2_in_group_get(const G& get) {
   if (proj_is_inf(get())) return true;
-  g2p_t xp = proj_neg(proj_mul_xabs_get<fp2_t>(get));
-  return proj_eq(g2_psi(get()), xp);
+  const proj_t<F> xp = proj_neg(proj_mul_xabs_get<F>(get));
+  return proj_eq(g2_psi(g2_to_pair(get())), g2_to_pair(xp));
 }
 LSG_BIGFN bool g2_in_group(g2p_t p) {
   return g2_in_group_get([&]() { return p; });

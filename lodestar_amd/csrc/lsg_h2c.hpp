@@ -177,9 +177,18 @@ LSG_BIGFN g2p_t clear_cofactor_g2(g2p_t p) {
 // holding P on entry) and one point parked in the caller's global slot (cput/cget): the [x]
 // chains run with their base in LDS and only the accumulator in registers, and no step in
 // between holds more than two points.
-template <class G, class P, class CP, class CG>
+// LANES: the two [x] chains run their doublings with one Fp2 component per lane
+// (g2_mul_xabs_get_dbl_lanes, lsg_curve.hpp); the additions, the sums between the chains, psi
+// and psi^2 are in the pair form either way.
+template <bool LANES = false, class G, class P, class CP, class CG>
 LSG_INL g2p_t clear_cofactor_g2_parked(const G& get, const P& put, const CP& cput, const CG& cget) {
-  cput(proj_neg(proj_mul_xabs_get<fp2_t>(get)));  // t1 = [x]P
+  auto xabs = [&]() {
+#ifdef LSG_FP2_LANES
+    if (LANES) return g2_mul_xabs_get_dbl_lanes(get);
+#endif
+    return proj_mul_xabs_get<fp2_t>(get);
+  };
+  cput(proj_neg(xabs()));  // t1 = [x]P
   g2p_t c;
   {
     const g2p_t p = get();
@@ -190,6 +199,6 @@ LSG_INL g2p_t clear_cofactor_g2_parked(const G& get, const P& put, const CP& cpu
   const g2p_t t1 = cget();
   cput(g2_add(c, proj_neg(t1)));  // c = psi^2(2P) - P - psi(P) - [x]P
   put(g2_add(t1, get()));         // [x]P + psi(P)
-  const g2p_t t2 = proj_neg(proj_mul_xabs_get<fp2_t>(get));  // [x]([x]P + psi(P))
+  const g2p_t t2 = proj_neg(xabs());  // [x]([x]P + psi(P))
   return g2_add(cget(), t2);
 }

@@ -877,6 +877,19 @@ int run_sig_groups(Slot* s, const uint8_t* mask) {
 // batched inversions in one launch per call (k_binv_block); LSG_BINV_BLOCK=0 (A/B build): the
 // multi-level fold / root / unfold launches
 static bool binv_block_on() { return lsg_ab_long("LSG_BINV_BLOCK", 1) != 0; }
+// the G2 [x] chains of k_sig_subgroup and k_h2c_clear with one Fp2 component per lane
+// (lsg_fp2_lanes.hpp); LSG_FP2_LANES=0 (A/B build): the kernels' pair-form twins
+static bool fp2_lanes_on() { return lsg_ab_long("LSG_FP2_LANES", 1) != 0; }
+// G2 membership of the slot's n decoded signatures (d_sigaff, d_siginf) into d_seterr
+int launch_sig_subgroup(Slot* s, int n) {
+  if (fp2_lanes_on())
+    KL(s, "k_sig_subgroup", lsgk::sig_subgroup(S_(s), n, P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
+                                               P_<int32_t>(s->d_seterr)));
+  else
+    KL(s, "k_sig_subgroup_pair", lsgk::sig_subgroup(S_(s), n, P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
+                                                    P_<int32_t>(s->d_seterr), true));
+  return LSG_OK;
+}
 
 // Words (per Fp of W_FP) of the two scratch arrays a batched inversion of n values needs:
 // lv = every level's prefix products plus levels >= 1's values, iv = levels >= 1's inverses
@@ -955,7 +968,10 @@ int launch_hash(Slot* s, int n, uint32_t* H, uint8_t* hinf) {
     KL(s, "k_slp_h2c", lsg_slp_h2c_clear(S_(s), n, P_<uint32_t>(s->d_Hp), H, hinf));
     return LSG_OK;
   }
-  KL(s, "k_h2c_clear", lsgk::h2c_clear(S_(s), n, P_<uint32_t>(s->d_Hp), P_<uint32_t>(s->d_zN), hinf));
+  if (fp2_lanes_on())
+    KL(s, "k_h2c_clear", lsgk::h2c_clear(S_(s), n, P_<uint32_t>(s->d_Hp), P_<uint32_t>(s->d_zN), hinf));
+  else
+    KL(s, "k_h2c_clear_pair", lsgk::h2c_clear(S_(s), n, P_<uint32_t>(s->d_Hp), P_<uint32_t>(s->d_zN), hinf, true));
   LSG_RC(batch_inv(s, 0, "binv_hash", P_<uint32_t>(s->d_zN), (size_t)n, P_<uint32_t>(s->d_zNi)));
   KL(s, "k_h2c_affine", lsgk::h2c_affine(S_(s), n, P_<uint32_t>(s->d_Hp), P_<uint32_t>(s->d_zNi), hinf, H));
   return LSG_OK;
@@ -1340,8 +1356,7 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
     KL(s, "k_slp_subgroup", lsg_slp_g2_subgroup(S_(s), n, P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
                                                 P_<int32_t>(s->d_seterr)));
   else
-    KL(s, "k_sig_subgroup", lsgk::sig_subgroup(S_(s), n, P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
-                                               P_<int32_t>(s->d_seterr)));
+    LSG_RC(launch_sig_subgroup(s, n));
   if (s->n_kv)  // a key error beats a signature error (the reference validates the key first)
     KL(s, "k_pk_keyvalidate_apply", lsgk::pk_keyvalidate_apply(S_(s), (int)s->n_kv, PL(s, s->kv_off + s->n_kv),
                                                                P_<int32_t>(s->d_pkp), P_<int32_t>(s->d_seterr)));
@@ -3573,9 +3588,7 @@ static int sig_decode_impl(lsg_ctx* c, const uint8_t* sigs, uint32_t sig_len, si
   const int nn = (int)n;
   KL(s, "k_sig_decode", lsgk::sig_decode(S_(s), nn, P_<uint8_t>(s->d_sig), P_<uint32_t>(s->d_siglen),
                                          P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf), P_<int32_t>(s->d_seterr)));
-  if (validate)
-    KL(s, "k_sig_subgroup", lsgk::sig_subgroup(S_(s), nn, P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
-                                               P_<int32_t>(s->d_seterr)));
+  if (validate) LSG_RC(launch_sig_subgroup(s, nn));
   return LSG_OK;
 }
 
@@ -3890,6 +3903,28 @@ int lsg_check_sums(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
   LSG_HIP(s, hipStreamSynchronize(s->st[0]));
   return LSG_OK;
 }
+
+// the component-per-lane Fp2 hooks (k_check_fp2_lanes, k_check_g2_lanes): EIN elements per item in, EOUT out
+static int check_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out, bool g2) {
+  const size_t EIN = g2 ? lsgk::CHECK_G2L_IN : lsgk::CHECK_LANES_IN, EOUT = g2 ? lsgk::CHECK_G2L_OUT : lsgk::CHECK_LANES_OUT;
+  if (!c || (n && (!in || !out)) || n > 0x7fffffffull / (4 * W_FP * EOUT)) return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  if (n == 0) return LSG_OK;
+  Slot* s = &c->dev[0]->util;
+  timer_reset(s);
+  LSG_RC(ensure(s, s->d_aux, 4 * EIN * W_FP * n));
+  LSG_RC(ensure(s, s->d_Fb, 4 * EOUT * W_FP * n));
+  LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, in, 4 * EIN * W_FP * n, hipMemcpyHostToDevice, s->st[0]));
+  if (g2)
+    KL(s, "k_check_g2_lanes", lsgk::check_g2_lanes(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  else
+    KL(s, "k_check_fp2_lanes", lsgk::check_fp2_lanes(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  LSG_HIP(s, hipMemcpyAsync(out, s->d_Fb.p, 4 * EOUT * W_FP * n, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  return LSG_OK;
+}
+int lsg_check_fp2_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_lanes(c, in, n, out, false); }
+int lsg_check_g2_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_lanes(c, in, n, out, true); }
 
 // the field-edge hooks (k_check_canon, k_check_from_bytes, k_check_fp2_roots, batch_inv, launch_hash)
 int lsg_check_canon(lsg_ctx* c, const uint32_t* in, size_t n, const uint8_t* bytes48, size_t nb, uint32_t* out,

@@ -175,20 +175,36 @@ __global__ void LSG_KERNEL_ATTR_W(LSG_H2C_WAVES) k_h2c_map(int n2, const uint32_
 // stage 2b: clear_cofactor in place; zN_i = N(Z) (0 at infinity) for the batched inversion.
 // The [x] chains take their base point from an LDS slot per lane and the partial sum waits in
 // the item's own slot of Hp, so the chains hold only their accumulator.
-__global__ void LSG_KERNEL_ATTR_W(LSG_H2C_WAVES) k_h2c_clear(int n, uint32_t* __restrict__ Hp, uint32_t* __restrict__ zN,
-                                            uint8_t* __restrict__ hinf) {
-  __shared__ uint32_t park[sizeof(g2p_t) / 4 * LSG_TPB];
+// LANES: the doublings of the two chains in the component-per-lane Fp2 layout (lsg_fp2_lanes.hpp).
+// The additions stay in the pair form: with them in the lane layout as well, as k_sig_subgroup
+// runs them, this kernel needed 32 to 64 bytes of scratch per lane at 2 waves per SIMD.
+template <bool LANES>
+LSG_DEVI void h2c_clear_item(uint32_t* park, int n, uint32_t* __restrict__ Hp, uint32_t* __restrict__ zN,
+                             uint8_t* __restrict__ hinf) {
   LANE_ITEM(n);
   lds_park(park, lane_load<g2p_t>(Hp, item));
-  g2p_t q = clear_cofactor_g2_parked([&]() { return lds_unpark<g2p_t>(park); },
-                                     [&](const g2p_t& v) { lds_park(park, v); },
-                                     [&](const g2p_t& v) { lane_store(Hp, item, v); },
-                                     [&]() { return lane_load<g2p_t>(Hp, item); });
+  g2p_t q = clear_cofactor_g2_parked<LANES>([&]() { return lds_unpark<g2p_t>(park); },
+                                            [&](const g2p_t& v) { lds_park(park, v); },
+                                            [&](const g2p_t& v) { lane_store(Hp, item, v); },
+                                            [&]() { return lane_load<g2p_t>(Hp, item); });
   bool is_inf = proj_is_inf(q);
   lane_store(Hp, item, q);
   lane_store(zN, item, is_inf ? fp_zero() : fp2_norm(q.Z));
   if (lead) hinf[item] = is_inf ? 1 : 0;
 }
+__global__ void LSG_KERNEL_ATTR_W(LSG_H2C_WAVES) k_h2c_clear(int n, uint32_t* __restrict__ Hp, uint32_t* __restrict__ zN,
+                                            uint8_t* __restrict__ hinf) {
+  __shared__ uint32_t park[sizeof(g2p_t) / 4 * LSG_TPB];
+  h2c_clear_item<true>(park, n, Hp, zN, hinf);
+}
+#ifdef LSG_FP2_LANES
+// the same kernel on the pair form: the A/B library's LSG_FP2_LANES=0 and the device tests
+__global__ void LSG_KERNEL_ATTR_W(LSG_H2C_WAVES) k_h2c_clear_pair(int n, uint32_t* __restrict__ Hp,
+                                                                  uint32_t* __restrict__ zN, uint8_t* __restrict__ hinf) {
+  __shared__ uint32_t park[sizeof(g2p_t) / 4 * LSG_TPB];
+  h2c_clear_item<false>(park, n, Hp, zN, hinf);
+}
+#endif
 
 // each set's hashed point from its message's (packages whose sets share messages hash every
 // distinct message once)
@@ -311,7 +327,11 @@ hipError_t h2c_prep(hipStream_t st, int n, const uint8_t* ub, uint32_t* U, uint3
 hipError_t h2c_map(hipStream_t st, int n, const uint32_t* U, const uint32_t* ninv, uint32_t* Hp) {
   LSG_LAUNCH_ITEMS(k_h2c_map, 2 * n, st, 2 * n, U, ninv, Hp);
 }
-hipError_t h2c_clear(hipStream_t st, int n, uint32_t* Hp, uint32_t* zN, uint8_t* hinf) {
+hipError_t h2c_clear(hipStream_t st, int n, uint32_t* Hp, uint32_t* zN, uint8_t* hinf, bool pair_form) {
+#ifdef LSG_FP2_LANES
+  if (pair_form) LSG_LAUNCH_ITEMS(k_h2c_clear_pair, n, st, n, Hp, zN, hinf);
+#endif
+  (void)pair_form;
   LSG_LAUNCH_ITEMS(k_h2c_clear, n, st, n, Hp, zN, hinf);
 }
 hipError_t h2c_gather(hipStream_t st, int n, const uint32_t* mid, const uint32_t* Hm, const uint8_t* hinfm, uint32_t* H,

@@ -326,6 +326,73 @@ __global__ void LSG_KERNEL_ATTR k_check_sums(int n, const uint32_t* __restrict__
   put2(fp2_sub(fp2_sub(t2c, t0c), fp2_mul_xi(fp2_add(el2(7), el2(9)))));
 }
 
+// parity hooks of the component-per-lane Fp2 layout (lsg_fp2_lanes.hpp) on caller-chosen limbs.
+// k_check_fp2_lanes: 12 raw pair-layout elements per item in = the Fp2 values A..F
+// (X = (el 2j, el 2j + 1)); 12 Fp2 values per item out, raw, every one but the last converted
+// back to the pair layout:
+//    0  A through the conversion in and out      1  A B      2  A^2
+//    3  (A + B + C - D - E - F).carry()          4..8  2A, 3A, 4A, 8A, 12A (carry_mul)
+//    9  fmul_b3(A)                               10  -A
+//   11  A in the lane layout as the lanes hold it: word k of lane h at 2 k + h (pins which
+//       lane holds which component)
+// k_check_g2_lanes: 12 elements in = a Jacobian point J = (A, B, C) and a homogeneous point
+// Q = (D, E, F); out: jac_dbl(J) in the lane layout, in the pair layout, jac_add_proj(J, Q) in the
+// lane layout, in the pair layout (3 Fp2 values each).
+#ifdef LSG_FP2_LANES
+__global__ void LSG_KERNEL_ATTR k_check_fp2_lanes(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  (void)lead;
+  auto el2 = [&](int j) {
+    return fp2_t(lane_load<fp_t>(in, (size_t)lsgk::CHECK_LANES_IN * item + 2 * j),
+                 lane_load<fp_t>(in, (size_t)lsgk::CHECK_LANES_IN * item + 2 * j + 1));
+  };
+  int o = 0;
+  auto put = [&](const fp2v_t& v) {
+    const fp2_t w = fp2v_to_pair(v);
+    lane_store(out, (size_t)lsgk::CHECK_LANES_OUT * item + (size_t)o, w.c0);
+    lane_store(out, (size_t)lsgk::CHECK_LANES_OUT * item + (size_t)o + 1, w.c1);
+    o += 2;
+  };
+  const fp2v_t A = fp2v_from_pair(el2(0)), B = fp2v_from_pair(el2(1)), C = fp2v_from_pair(el2(2));
+  const fp2v_t D = fp2v_from_pair(el2(3)), E = fp2v_from_pair(el2(4)), F = fp2v_from_pair(el2(5));
+  put(A);
+  put(fmul(A, B));
+  put(fsqr(A));
+  put((fsum(A) + B + C - D - E - F).carry());
+  put(fmulk<2>(A));
+  put(fmulk<3>(A));
+  put(fmulk<4>(A));
+  put(fmulk<8>(A));
+  put(fmulk<12>(A));
+  put(fmul_b3(A));
+  put(fneg(A));
+  lane_store(out + (size_t)lsgk::CHECK_LANES_OUT * lsgl::W_FP * item + (size_t)o * lsgl::W_FP, 0, A);
+}
+__global__ void LSG_KERNEL_ATTR k_check_g2_lanes(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  (void)lead;
+  auto el2 = [&](int j) {
+    return fp2_t(lane_load<fp_t>(in, (size_t)lsgk::CHECK_G2L_IN * item + 2 * j),
+                 lane_load<fp_t>(in, (size_t)lsgk::CHECK_G2L_IN * item + 2 * j + 1));
+  };
+  int o = 0;
+  auto put2 = [&](const fp2_t& w) {
+    lane_store(out, (size_t)lsgk::CHECK_G2L_OUT * item + (size_t)o, w.c0);
+    lane_store(out, (size_t)lsgk::CHECK_G2L_OUT * item + (size_t)o + 1, w.c1);
+    o += 2;
+  };
+  auto putv = [&](const jac_t<fp2v_t>& r) { put2(fp2v_to_pair(r.X)), put2(fp2v_to_pair(r.Y)), put2(fp2v_to_pair(r.Z)); };
+  auto putp = [&](const jac_t<fp2_t>& r) { put2(r.X), put2(r.Y), put2(r.Z); };
+  const jac_t<fp2_t> J = {el2(0), el2(1), el2(2)};
+  const g2p_t Q = {el2(3), el2(4), el2(5)};
+  const jac_t<fp2v_t> Jv = {fp2v_from_pair(J.X), fp2v_from_pair(J.Y), fp2v_from_pair(J.Z)};
+  putv(jac_dbl(Jv));
+  putp(jac_dbl(J));
+  putv(jac_add_proj(Jv, g2v_from_pair(Q)));
+  putp(jac_add_proj(J, Q));
+}
+#endif
+
 // parity hooks of the layer between the products and the accept / reject rules: canonical
 // forms, the predicates on them, the byte conversions, the Fp2 root and the two inversions,
 // on caller-chosen raw limbs.  Every output comes from the function the kernels call.
@@ -455,6 +522,17 @@ hipError_t check_fp2_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* ou
 hipError_t check_sums(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
   LSG_LAUNCH_ITEMS(k_check_sums, n, st, n, in, out);
 }
+#ifdef LSG_FP2_LANES
+hipError_t check_fp2_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_fp2_lanes, n, st, n, in, out);
+}
+hipError_t check_g2_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_g2_lanes, n, st, n, in, out);
+}
+#else  // -DLSG_NO_FP2_LANES: the layout is not built
+hipError_t check_fp2_lanes(hipStream_t, int, const uint32_t*, uint32_t*) { return hipErrorNotSupported; }
+hipError_t check_g2_lanes(hipStream_t, int, const uint32_t*, uint32_t*) { return hipErrorNotSupported; }
+#endif
 hipError_t check_canon(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
   LSG_LAUNCH_ITEMS(k_check_canon, n, st, n, in, out);
 }

@@ -29,15 +29,30 @@ __global__ void LSG_KERNEL_ATTR k_sig_decode(int n, const uint8_t* __restrict__ 
 
 // psi(P) == [x]P (Jacobian doubling chain, complete additions); the chain's base point waits
 // in an LDS slot per lane, re-read at the five additions, instead of in spilled registers
+// F: the layout the chain runs in and the point is parked in (chain_fp2_t: one Fp2 component
+// per lane, lsg_fp2_lanes.hpp); sig_aff is read in the pair form and converted at the load
+template <class F>
+LSG_DEVI void sig_subgroup_item(uint32_t* park, int n, const uint32_t* __restrict__ sig_aff,
+                                const uint8_t* __restrict__ inf, int32_t* __restrict__ err) {
+  LANE_ITEM(n);
+  if (err[item] != 0 || inf[item]) return;
+  lds_park(park, g2_layout<F>::in(lane_load<g2a_t>(sig_aff, item)));
+  bool ok = g2_in_group_get<F>([&]() { return proj_from_aff(lds_unpark<aff_t<F>>(park)); });
+  if (lead && !ok) err[item] = LSG_BLST_POINT_NOT_IN_GROUP;
+}
 __global__ void LSG_KERNEL_ATTR k_sig_subgroup(int n, const uint32_t* __restrict__ sig_aff,
                                                const uint8_t* __restrict__ inf, int32_t* __restrict__ err) {
   __shared__ uint32_t park[sizeof(g2a_t) / 4 * LSG_TPB];
-  LANE_ITEM(n);
-  if (err[item] != 0 || inf[item]) return;
-  lds_park(park, lane_load<g2a_t>(sig_aff, item));
-  bool ok = g2_in_group_get([&]() { return proj_from_aff(lds_unpark<g2a_t>(park)); });
-  if (lead && !ok) err[item] = LSG_BLST_POINT_NOT_IN_GROUP;
+  sig_subgroup_item<chain_fp2_t>(park, n, sig_aff, inf, err);
 }
+#ifdef LSG_FP2_LANES
+// the same kernel on the pair form: the A/B library's LSG_FP2_LANES=0 and the device tests
+__global__ void LSG_KERNEL_ATTR k_sig_subgroup_pair(int n, const uint32_t* __restrict__ sig_aff,
+                                                    const uint8_t* __restrict__ inf, int32_t* __restrict__ err) {
+  __shared__ uint32_t park[sizeof(g2a_t) / 4 * LSG_TPB];
+  sig_subgroup_item<fp2_t>(park, n, sig_aff, inf, err);
+}
+#endif
 
 // The point set i adds to its group's signature sum S_g = sum r_i sig_i: the identity for a
 // set that cannot contribute (undecodable or infinite signature, infinite aggregated key: the
@@ -196,7 +211,11 @@ hipError_t sig_decode(hipStream_t st, int n, const uint8_t* sig, const uint32_t*
                       uint8_t* inf, int32_t* err) {
   LSG_LAUNCH_ITEMS(k_sig_decode, n, st, n, sig, sig_len, sig_aff, inf, err);
 }
-hipError_t sig_subgroup(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, int32_t* err) {
+hipError_t sig_subgroup(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, int32_t* err, bool pair_form) {
+#ifdef LSG_FP2_LANES
+  if (pair_form) LSG_LAUNCH_ITEMS(k_sig_subgroup_pair, n, st, n, sig_aff, inf, err);
+#endif
+  (void)pair_form;
   LSG_LAUNCH_ITEMS(k_sig_subgroup, n, st, n, sig_aff, inf, err);
 }
 hipError_t sig_prep(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err,

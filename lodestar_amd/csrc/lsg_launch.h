@@ -15,7 +15,8 @@ hipError_t expand_msg(hipStream_t st, int n, const uint8_t* msg, const uint32_t*
                       const uint8_t* dst, uint32_t dst_len, uint8_t* ub);
 hipError_t h2c_prep(hipStream_t st, int n, const uint8_t* ub, uint32_t* U, uint32_t* norms);
 hipError_t h2c_map(hipStream_t st, int n, const uint32_t* U, const uint32_t* ninv, uint32_t* Hp);
-hipError_t h2c_clear(hipStream_t st, int n, uint32_t* Hp, uint32_t* zN, uint8_t* hinf);
+// pair_form: the kernel with its [x] chains in the pair layout (A/B; lsg_fp2_lanes.hpp)
+hipError_t h2c_clear(hipStream_t st, int n, uint32_t* Hp, uint32_t* zN, uint8_t* hinf, bool pair_form = false);
 hipError_t h2c_gather(hipStream_t st, int n, const uint32_t* mid, const uint32_t* Hm, const uint8_t* hinfm, uint32_t* H,
                       uint8_t* hinf);
 hipError_t h2c_affine(hipStream_t st, int n, const uint32_t* Hp, const uint32_t* ninv, const uint8_t* hinf,
@@ -37,7 +38,8 @@ hipError_t msg_roots(hipStream_t st, int n, uint8_t* msg, const uint32_t* off, u
 // ---- signatures (lsg_k_sig.hip)                                       SURVEY 8a M2, M4
 hipError_t sig_decode(hipStream_t st, int n, const uint8_t* sig, const uint32_t* sig_len, uint32_t* sig_aff,
                       uint8_t* inf, int32_t* err);
-hipError_t sig_subgroup(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, int32_t* err);
+hipError_t sig_subgroup(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, int32_t* err,
+                        bool pair_form = false);
 // out[i] = the projective point set i adds to its group's RLC signature sum: the identity
 // when the signature did not decode (err), is the point at infinity (inf) or the set's
 // aggregated key is infinity (pinf, may be null); else [r_i] sig_i when rnd is given and
@@ -162,6 +164,10 @@ hipError_t check_fp2_mul(hipStream_t st, int n, const uint32_t* in, uint32_t* ou
 hipError_t check_fp_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t check_fp2_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t check_sums(hipStream_t st, int n, const uint32_t* in, uint32_t* out);  // 12 elements in, 42 out per item
+// the component-per-lane Fp2 hooks (lodestar_bls.h lsg_check_fp2_lanes, lsg_check_g2_lanes)
+constexpr int CHECK_LANES_IN = 12, CHECK_LANES_OUT = 24, CHECK_G2L_IN = 12, CHECK_G2L_OUT = 24;  // elements per item
+hipError_t check_fp2_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
+hipError_t check_g2_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 // the field-edge hooks (lodestar_bls.h lsg_check_canon, lsg_check_fp2_roots)
 constexpr int CHECK_CANON_OUT = 54, CHECK_ROOTS_OUT = 58;  // words per item out
 hipError_t check_canon(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
