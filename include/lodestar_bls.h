@@ -558,6 +558,18 @@ int lsg_check_canon(lsg_ctx* ctx, const uint32_t* in, size_t n, const uint8_t* b
 int lsg_check_fp2_roots(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
 int lsg_check_batch_inv(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
 int lsg_check_map_uniform(lsg_ctx* ctx, const uint8_t* ub256, size_t n, uint8_t* out192);
+/* Parity hook of the random linear combination (tests only): lsg_batch_partial in every respect
+ * -- one batchable job, every set scaled, the same slot, plan, kernels and launches, per-set
+ * error codes, single-device contexts -- except that set i takes the randomizer rnd[i] where
+ * lsg_batch_partial takes the i-th draw of its seed, so that a test can put edge scalars, equal
+ * scalars and skewed bucket occupancies through the scaling kernels and the bucket sums.  The
+ * pointer travels with the call (no context state: concurrent submitters are unaffected).
+ * LSG_ERR_INVALID_ARG, before anything is staged, for a null pointer (set_err may be null), a zero
+ * randomizer or a multi-device context; the context stays usable.  It adds no power to the
+ * library: a nonzero seed already fixes every randomizer. */
+int lsg_check_batch_partial_rnd(lsg_ctx* ctx, const lsg_set* sets, size_t n_sets,
+                                const uint64_t* rnd /* [n_sets], each nonzero */, uint8_t* out576,
+                                int32_t* set_err, int32_t* any_error);
 
 /* Integer-VALU roofline probe: runs a throughput kernel of dependent-free 381-bit
  * Montgomery multiplications; reports Fp-mul/s and v_mad_u64_u32/s (x300 per mul). */

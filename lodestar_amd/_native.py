@@ -173,6 +173,7 @@ EXPORTS = [
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
     "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums", "lsg_check_fp2_lanes", "lsg_check_g2_lanes",
     "lsg_check_canon", "lsg_check_fp2_roots", "lsg_check_batch_inv", "lsg_check_map_uniform",
+    "lsg_check_batch_partial_rnd",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
     "lsg_object_signing_roots",
@@ -255,6 +256,8 @@ def load_library(path=LIB_PATH):
         lib.lsg_check_fp2_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_batch_inv.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_map_uniform.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_batch_partial_rnd.argtypes = [vp, ctypes.POINTER(LsgSet), sz, ctypes.POINTER(u64),
+                                                    ctypes.c_char_p, pi32, pi32]
         lib.lsg_probe_mad_peak.argtypes = [vp, ctypes.POINTER(ctypes.c_double)]
         for name in EXPORTS:
             if name != "lsg_last_error":
@@ -883,6 +886,19 @@ class Context:
         self._check(self.lib.lsg_check_map_uniform(self.h, b"".join(items), n, out), "lsg_check_map_uniform")
         raw = out.raw
         return [raw[192 * i:192 * i + 192] for i in range(n)]
+
+    def batch_partial_rnd(self, sets, rnd):
+        """lsg_check_batch_partial_rnd: batch_partial with set i scaled by rnd[i] (nonzero 64-bit
+        integers); returns (576-byte partial, per-set error codes, any_error)."""
+        b = SetBuffer(sets)
+        assert len(rnd) == b.n
+        r = (ctypes.c_uint64 * max(b.n, 1))(*[int(x) for x in rnd])
+        out = ctypes.create_string_buffer(576)
+        errs = (ctypes.c_int32 * max(b.n, 1))()
+        anyerr = ctypes.c_int32()
+        self._check(self.lib.lsg_check_batch_partial_rnd(self.h, b.arr, b.n, r, out, errs, ctypes.byref(anyerr)),
+                    "lsg_check_batch_partial_rnd")
+        return out.raw, [errs[i] for i in range(b.n)], bool(anyerr.value)
 
     def probe_fp_mul_rate(self):
         a, b = ctypes.c_double(), ctypes.c_double()

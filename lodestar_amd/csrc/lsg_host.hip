@@ -1001,8 +1001,11 @@ static uint64_t msg_key(const uint8_t* m, uint32_t msg_len) {
 // unknown key length.  Such a set stages its id and bits only -- no key slots, no per-key
 // error entries -- and its set-level errors are resolved here: an unknown or unset committee
 // or a length mismatch (LSG_ERR_BAD_COMMITTEE, shape.bits_kerr), no participant (shape.bits_p 0).
+// rnd_in: the caller's randomizers, one per staged set, in place of the draws
+// (lsg_check_batch_partial_rnd; each nonzero, checked at the entry point).
 int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, bool scale,
-               const std::vector<uint8_t>* noscale = nullptr, bool dedup = false, bool bits_ok = false) {
+               const std::vector<uint8_t>* noscale = nullptr, bool dedup = false, bool bits_ok = false,
+               const uint64_t* rnd_in = nullptr) {
   size_t npk = 0, msg_total = 0, n_bits_sets = 0, bit_words = 0;
   bool any_obj = false;   // a message is an SSZ object + domain (LSG_MSG_OBJECT): k_msg_roots runs
   bool all_index = true;  // every key names a table row: 4-byte key slots (a block body's
@@ -1169,7 +1172,9 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   s->msg_dedup = nm < n;
   if (s->msg_dedup) s->msg_id.assign(mid, mid + n);
   if (scale && n) {
-    if (seed == 0) {
+    if (rnd_in) {
+      memcpy(rnd, rnd_in, 8 * n);
+    } else if (seed == 0) {
       if (!os_random(rnd, 8 * n)) {
         set_err(s->d->c, "no entropy for the RLC randomizers (getrandom failed)");
         return LSG_ERR_ENTROPY;
@@ -1610,7 +1615,7 @@ int launch_sig_prep(Slot* s, bool scale, const std::vector<uint8_t>* mode, uint3
 // msg bytes are placeholders then and are overwritten by a device copy.
 int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint64_t seed, int n_node,
               const std::vector<size_t>* subs = nullptr, bool lone_ok = true, const uint8_t* dev_msgs = nullptr,
-              const uint32_t* set_group = nullptr, size_t n_groups = 0) {
+              const uint32_t* set_group = nullptr, size_t n_groups = 0, const uint64_t* rnd_in = nullptr) {
   timer_reset(s);
   s->plan.clear();
   memset(&s->stats, 0, sizeof(s->stats));
@@ -1650,7 +1655,7 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   s->sw = read_switches();
   s->gp = plan_groups(s->shape, s->sw, lone_ok);
   const uint64_t th0 = trace_host() ? now_ns() : 0;
-  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &s->gp.noscale, dev_msgs == nullptr, true));
+  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &s->gp.noscale, dev_msgs == nullptr, true, rnd_in));
   if (dev_msgs && !flat.empty())  // (placeholders are never merged: message i is set i's)
     LSG_HIP(s, hipMemcpyAsync(s->d_msg.p, dev_msgs, 32 * flat.size(), hipMemcpyDeviceToDevice, s->st[0]));
   // the byte keys of LSG_JOB_VALIDATE_KEYS jobs, compacted (table rows were validated when the
@@ -2076,7 +2081,7 @@ int pkg_exchange(lsg_ctx* c, int p) {
 // Errors go to *err (t_err_sink), not to c->err.
 int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t seed, bool lone_ok, bool exch,
               std::string* err, const uint8_t* dev_msgs = nullptr, const uint32_t* set_group = nullptr,
-              size_t n_groups = 0) {
+              size_t n_groups = 0, const uint64_t* rnd_in = nullptr) {
   const int n = c->n_dev;
   std::vector<std::vector<size_t>> ids(n);
   {
@@ -2094,7 +2099,7 @@ int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t se
     // distinct seeds per device for tests; 0 stays 0 (OS CSPRNG on every device)
     const uint64_t sd = seed ? seed + 0x9e3779b97f4a7c15ull * (uint64_t)d : 0;
     rcs[d] = pkg_part1(&c->dev[d]->slots[p], jobs, ids[d], sd, (d == 0 && exch) ? n : 0, nullptr, lone_ok && !exch,
-                       n == 1 ? dev_msgs : nullptr, n == 1 ? set_group : nullptr, n_groups);
+                       n == 1 ? dev_msgs : nullptr, n == 1 ? set_group : nullptr, n_groups, n == 1 ? rnd_in : nullptr);
     t_err_sink = nullptr;
   };
   auto part2 = [&](int d) {
@@ -2184,7 +2189,7 @@ int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t se
 // lock again.  A reserved slot is SLOT_STAGING: no other call takes, reserves or waits on it.
 int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint64_t seed, lsg_ticket* ticket,
                bool lone_ok = true, const uint8_t* dev_msgs = nullptr, const uint32_t* set_group = nullptr,
-               size_t n_groups = 0) {
+               size_t n_groups = 0, const uint64_t* rnd_in = nullptr) {
   int p = -1;
   for (int i = 0; i < LSG_SLOTS && p < 0; i++)
     if (c->dev[0]->slots[i].kind == SLOT_FREE) p = i;
@@ -2205,7 +2210,7 @@ int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint
   c->staging++;
   lk.unlock();
   std::string err;
-  const int rc = stage_pkg(c, p, jobs, n_jobs, seed, lone_ok, exch, &err, dev_msgs, set_group, n_groups);
+  const int rc = stage_pkg(c, p, jobs, n_jobs, seed, lone_ok, exch, &err, dev_msgs, set_group, n_groups, rnd_in);
   lk.lock();
   (void)hipSetDevice(c->dev[0]->device);
   c->staging--;
@@ -3139,9 +3144,10 @@ int lsg_poll(lsg_ctx* c, lsg_ticket ticket, int32_t* done) {
   return LSG_OK;
 }
 
-// one shard's partial (sync): all sets as one batchable job
-int lsg_batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_t seed, uint8_t* out576,
-                      int32_t* set_err, int32_t* any_error) {
+// one shard's partial (sync): all sets as one batchable job.  rnd_in: the
+// randomizers of lsg_check_batch_partial_rnd in place of the seed's draws
+static int batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_t seed, const uint64_t* rnd_in,
+                         uint8_t* out576, int32_t* set_err, int32_t* any_error) {
   if (!c || !out576 || !any_error || (n_sets && !sets)) return LSG_ERR_INVALID_ARG;
   if (c->n_dev > 1) {
     c->err = "lsg_batch_partial: single-device contexts only";
@@ -3156,7 +3162,8 @@ int lsg_batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_t s
     job.sets = sets;
     job.n_sets = (uint32_t)n_sets;
     job.flags = LSG_JOB_BATCHABLE;
-    int rc = submit_pkg(c, lk, &job, 1, seed, &t, false);  // the partial leaves: every r_i random
+    // the partial leaves: every r_i random
+    int rc = submit_pkg(c, lk, &job, 1, seed, &t, false, nullptr, nullptr, 0, rnd_in);
     if (rc) return rc;
   }
   const int prc = presync_pkg(c, t, false);
@@ -3186,6 +3193,21 @@ int lsg_batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_t s
   s->kind = SLOT_FREE;
   keep_times(s);
   return LSG_OK;
+}
+
+int lsg_batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_t seed, uint8_t* out576,
+                      int32_t* set_err, int32_t* any_error) {
+  return batch_partial(c, sets, n_sets, seed, nullptr, out576, set_err, any_error);
+}
+
+// parity hook (tests): lsg_batch_partial with the caller's randomizers; every argument error is
+// reported before anything is staged
+int lsg_check_batch_partial_rnd(lsg_ctx* c, const lsg_set* sets, size_t n_sets, const uint64_t* rnd, uint8_t* out576,
+                                int32_t* set_err, int32_t* any_error) {
+  if (!c || !out576 || !any_error || (n_sets && (!sets || !rnd))) return LSG_ERR_INVALID_ARG;
+  for (size_t i = 0; i < n_sets; i++)
+    if (rnd[i] == 0) return LSG_ERR_INVALID_ARG;
+  return batch_partial(c, sets, n_sets, 1, rnd, out576, set_err, any_error);
 }
 
 int lsg_final_submit_groups(lsg_ctx* c, const uint8_t* partials576, size_t n_groups, size_t per_group,

@@ -13,6 +13,11 @@
 //        sub-package) ..  C check_calls"
 //   2 op fold_wide has_idx n_specs (len count)[n_specs]      segments for plan_seg
 //     -> "seg ok passes P"
+//   3 K msm_min package_group sub_groups nb_merge b0_min b0_run lone_ok rnd_mode seed ...
+//     case 1 with chosen randomizers for the scaled sets (case 1 is rnd_mode 0: splitmix64 | 1):
+//     1 all 0x0101010101010101 (eight buckets hold every set), 2 all 2^63 (one bit sum is not
+//     empty), 3 all 2^64 - 1, 4 (1 + i mod 255) << 24 (every bucket of one window, no other)
+//     -> the line of case 1 followed by " P passes" (of phase A's bucket plan; 0: no MSM group)
 // Any broken invariant prints a message and exits nonzero.
 #include <stdio.h>
 #include <stdlib.h>
@@ -217,8 +222,20 @@ void check_phase(const std::vector<int32_t>& A, const PhasePlan& Ph, const std::
   }
 }
 
-// ---- case 1: one package through plan_groups, plan_phase and resolve_package
-void verdict_case(Input& in, FILE* out) {
+// the randomizer of scaled set i under rnd_mode (the header lists the modes)
+uint64_t chosen_rnd(int mode, size_t i, uint64_t& sd) {
+  switch (mode) {
+    case 0: return splitmix64(sd) | 1;
+    case 1: return 0x0101010101010101ull;
+    case 2: return 1ull << 63;
+    case 3: return ~0ull;
+    case 4: return (uint64_t)(1 + i % 255) << 24;
+  }
+  die("unknown rnd_mode");
+}
+
+// ---- cases 1 and 3: one package through plan_groups, plan_phase and resolve_package
+void verdict_case(Input& in, FILE* out, bool with_mode) {
   const int K = (int)in.next();
   Switches sw;
   sw.msm_min_group = (size_t)in.next();
@@ -228,6 +245,7 @@ void verdict_case(Input& in, FILE* out) {
   sw.b0_min = (size_t)in.next();
   sw.b0_run = (size_t)in.next();
   const bool lone_ok = in.next() != 0;
+  const int rnd_mode = with_mode ? (int)in.next() : 0;
   uint64_t sd = (uint64_t)in.next();
   const size_t nj = (size_t)in.next();
   std::vector<size_t> subs((size_t)in.next());
@@ -297,7 +315,7 @@ void verdict_case(Input& in, FILE* out) {
   GroupPlan gp = plan_groups(sh, sw, lone_ok);
   REQUIRE(gp.noscale.size() == n, "noscale size");
   std::vector<uint64_t> rnd(n);
-  for (size_t i = 0; i < n; i++) rnd[i] = gp.noscale[i] ? 0 : (splitmix64(sd) | 1);
+  for (size_t i = 0; i < n; i++) rnd[i] = gp.noscale[i] ? 0 : chosen_rnd(rnd_mode, i, sd);
   // phase-A groups: disjoint, MSM groups first, every set with a job in exactly one group;
   // an unscaled set is alone in its group
   std::vector<int> set_group(n, -1);
@@ -372,7 +390,9 @@ void verdict_case(Input& in, FILE* out) {
     fprintf(out, "U %u %u %d %u ", sub_stats[k].batch_retries, sub_stats[k].batch_sigs_success, sub_stats[k].key_error,
             sub_stats[k].key_error_job);
   }
-  fprintf(out, "C %zu\n", calls);
+  fprintf(out, "C %zu", calls);
+  if (with_mode) fprintf(out, " P %zu", A.n_msm ? A.buckets.passes.size() : (size_t)0);
+  fprintf(out, "\n");
 }
 
 }  // namespace
@@ -389,8 +409,8 @@ int main(int argc, char** argv) {
   REQUIRE(out != nullptr, "cannot write the output file");
   for (long long k = in.next(); k > 0; k--) {
     const long long kind = in.next();
-    if (kind == 1)
-      verdict_case(in, out);
+    if (kind == 1 || kind == 3)
+      verdict_case(in, out, kind == 3);
     else if (kind == 2)
       seg_case(in, out);
     else

@@ -167,8 +167,10 @@ def expected_line(jobs, subs):
 
 
 def case_ints(jobs, subs, sw, seed):
-    v = [1, sw["K"], sw["msm_min"], sw["package_group"], sw["sub_groups"], sw["nb_merge"], sw["b0_min"], sw["b0_run"],
-         sw["lone_ok"], seed, len(jobs), len(subs or [])] + list(subs or [])
+    # rnd_mode (chosen phase-A randomizers, plancheck.cpp case kind 3) only where a case names one
+    head = [3, sw["rnd_mode"]] if sw.get("rnd_mode") else [1]
+    v = [head[0], sw["K"], sw["msm_min"], sw["package_group"], sw["sub_groups"], sw["nb_merge"], sw["b0_min"], sw["b0_run"],
+         sw["lone_ok"]] + head[1:] + [seed, len(jobs), len(subs or [])] + list(subs or [])
     for job in jobs:
         v += [(BATCHABLE if job["batchable"] else 0) | (VALIDATE_KEYS if job["validate"] else 0), len(job["sets"])]
         for s in job["sets"]:
@@ -186,8 +188,17 @@ def check(driver, cases):
     for (name, jobs, subs, sw), line in zip(cases, lines):
         verdicts, _, n_calls = line.rpartition(" C ")
         assert verdicts.strip() == expected_line(jobs, subs), f"{name} {sw}"
-        calls.append(int(n_calls))
+        calls.append(int(n_calls.partition(" P ")[0]))
     return calls
+
+
+def bucket_passes(driver, cases):
+    """check(), and the number of passes of phase A's bucket plan per case (rnd_mode cases)"""
+    ints = []
+    for k, (_, jobs, subs, sw) in enumerate(cases):
+        ints += case_ints(jobs, subs, dict(SWITCHES, **sw), 1000 + k)
+    check(driver, cases)
+    return [int(line.rpartition(" P ")[2]) for line in driver(ints, len(cases))]
 
 
 def variants(name, jobs, subs=None, **fixed):
@@ -354,6 +365,30 @@ def test_phase_b0_lowered_threshold(driver):
             jobs = mixed(16 * n_chunks, bad={0, 31 * n_chunks}, thrown={17})
             cases += variants(f"{n_chunks} chunks of mixed jobs run {run}", jobs, b0_min=2, b0_run=run)
     check(driver, cases)
+
+
+RND_MODES = {"all equal": 1, "single bit": 2, "all ones": 3, "one window": 4}
+
+
+def test_skewed_randomizers(driver):
+    """Chosen phase-A randomizers (tests/test_gpu_rlc_edges.py runs the same patterns on the
+    device) at 256, 513 and 600 single-set jobs: buckets that hold every set -- past 512 members
+    (32 lane pairs x 16 folds) the bucket plan takes a second pass -- and bit sums over empty
+    buckets only, executed on integers; valid packages and ones whose fallback phases run"""
+    cases = []
+    for n in (256, 513, 600):
+        for mode in RND_MODES.values():
+            for K in (1, 4):
+                for msm_min in (1, 256):
+                    sw = dict(K=K, msm_min=msm_min, rnd_mode=mode)
+                    cases.append((f"{n} valid", singles(n), None, sw))
+                    cases.append((f"{n} two bad", singles(n, bad={3, n - 1}), None, sw))
+            cases.append((f"{n} mixed", mixed(n // 2, bad={n // 3}, thrown={7}), None, dict(msm_min=1, rnd_mode=mode)))
+    passes = bucket_passes(driver, cases)
+    for (name, jobs, _, sw), p in zip(cases, passes):
+        n_sets = sum(len(j["sets"]) for j in jobs)
+        full = sw["rnd_mode"] != RND_MODES["one window"]  # a bucket holds every set of the group
+        assert p == (2 if full and n_sets > 512 else 1), f"{name} {sw}: {p} passes"
 
 
 def random_package(rng):
