@@ -410,6 +410,40 @@ int lsg_committees_set(lsg_ctx* ctx, uint32_t first_id, const uint32_t* indices,
 int lsg_committees_clear(lsg_ctx* ctx, uint32_t first_id, size_t n);
 int lsg_committee_count(lsg_ctx* ctx, size_t* n);
 
+/* The message cache: an opt-in, per-device cache of the affine G2 points H(m)
+ * under the POP DST, kept across packages.  A slot's 64 AttestationData are signed by tens of
+ * thousands of attesters whose sets arrive spread over hundreds of gossip-sized packages; with
+ * the cache on, a message the device hashed for an earlier package is not staged, not copied
+ * to the device and not hashed again (nor is its signing root computed, when it is an
+ * LSG_MSG_OBJECT message).
+ *   lsg_msg_cache_set(capacity)  allocates `capacity` rows per device (0: off, everything freed)
+ *                                and the host key store; waits for the work in flight and
+ *                                drops every entry, as does lsg_msg_cache_clear.  Call
+ *                                lsg_reserve after it (or again): it sizes the per-slot
+ *                                buffers of cached packages, which then allocate nothing.
+ *   lsg_msg_cache_get_stats      counters summed over the devices.
+ * The key is the message as it is staged -- payload bytes plus the LSG_MSG_OBJECT marker of
+ * its length -- compared on every byte; empty messages and messages of more than 192 bytes
+ * are never cached (`bypassed`).  The package that first sees a message hashes it and writes
+ * the point into a row; the entry becomes visible once the host has observed that launch's
+ * completion (lsg_wait_jobs*, lsg_poll).  Until then other packages naming the message hash it
+ * themselves (`pending`).  Rows a launch reads or writes are pinned until then; with every row
+ * pinned a new message is hashed and not inserted (`full`).  Replacement is CLOCK with a
+ * second chance for rows that were hit.  lookups == hits + pending + inserts + full.
+ * The cache serves the packages of lsg_submit_jobs* / lsg_verify_jobs / lsg_verify_sets on
+ * every device of the context (each device keeps its own); lsg_hash_to_g2 (caller's DST),
+ * lsg_verify_deposits on one device (its messages stay on the device) and lsg_batch_partial do
+ * not use it.  Verdicts, error codes, counters, aggregates and exported partials are those of
+ * a context without the cache: a stored point is the computed point copied word for word.
+ * A context that never calls lsg_msg_cache_set stages, allocates and launches as before. */
+typedef struct {
+  uint64_t lookups, hits, pending, inserts, evictions, bypassed, full;
+  uint32_t entries, capacity;
+} lsg_msg_cache_stats;
+int lsg_msg_cache_set(lsg_ctx* ctx, size_t capacity);
+int lsg_msg_cache_clear(lsg_ctx* ctx);
+int lsg_msg_cache_get_stats(lsg_ctx* ctx, lsg_msg_cache_stats* out);
+
 /* Batched KeyValidate: PublicKey.fromBytes(pk, affine, validate=true) of
  * processDeposit.ts:57-65 for n keys of pk_len (48/96) bytes -- decode, not the point at
  * infinity (BLST_PK_IS_INFINITY), in the r-torsion subgroup (BLST_POINT_NOT_IN_GROUP).

@@ -157,6 +157,11 @@ class LsgStats(ctypes.Structure):
     ]
 
 
+class LsgMsgCacheStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("lookups", "hits", "pending", "inserts", "evictions", "bypassed",
+                                                "full")] + [("entries", ctypes.c_uint32), ("capacity", ctypes.c_uint32)]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -178,6 +183,7 @@ EXPORTS = [
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
     "lsg_object_signing_roots",
     "lsg_submit_jobs_grouped", "lsg_wait_jobs_grouped",
+    "lsg_msg_cache_set", "lsg_msg_cache_clear", "lsg_msg_cache_get_stats",
 ]
 
 
@@ -232,6 +238,9 @@ def load_library(path=LIB_PATH):
         lib.lsg_committees_set.argtypes = [vp, u32, ctypes.POINTER(u32), ctypes.POINTER(u32), sz, pi32]
         lib.lsg_committees_clear.argtypes = [vp, u32, sz]
         lib.lsg_committee_count.argtypes = [vp, ctypes.POINTER(sz)]
+        lib.lsg_msg_cache_set.argtypes = [vp, sz]
+        lib.lsg_msg_cache_clear.argtypes = [vp]
+        lib.lsg_msg_cache_get_stats.argtypes = [vp, ctypes.POINTER(LsgMsgCacheStats)]
         lib.lsg_final_submit_groups.argtypes = [vp, ctypes.c_char_p, sz, sz, pu64]
         lib.lsg_final_wait_groups.argtypes = [vp, u64, pi32]
         lib.lsg_pubkey_validate.argtypes = [vp, ctypes.c_char_p, u32, sz, ctypes.c_char_p, pi32]
@@ -612,6 +621,20 @@ class Context:
         n = ctypes.c_size_t()
         self._check(self.lib.lsg_committee_count(self.h, ctypes.byref(n)), "lsg_committee_count")
         return n.value
+
+    def msg_cache_set(self, capacity):
+        """lsg_msg_cache_set: keep up to `capacity` hashed messages H(m) per device across packages
+        (0: off and freed).  Call reserve() after it for allocation-free submissions."""
+        self._check(self.lib.lsg_msg_cache_set(self.h, int(capacity)), "lsg_msg_cache_set")
+
+    def msg_cache_clear(self):
+        self._check(self.lib.lsg_msg_cache_clear(self.h), "lsg_msg_cache_clear")
+
+    def msg_cache_stats(self):
+        """lsg_msg_cache_get_stats as a dict (summed over the context's devices)"""
+        st = LsgMsgCacheStats()
+        self._check(self.lib.lsg_msg_cache_get_stats(self.h, ctypes.byref(st)), "lsg_msg_cache_get_stats")
+        return {k: int(getattr(st, k)) for k, _ in LsgMsgCacheStats._fields_}
 
     def pubkey_validate(self, pks):
         """Batched KeyValidate: [(uncompressed 96 B, BLST code)] per key."""

@@ -53,6 +53,7 @@
 #include "lsg_layout.h"
 #include "lsg_serial.h"
 #include "lsg_ab.h"
+#include "lsg_msg_cache.hpp"
 #include "lsg_plan.hpp"
 
 using namespace lsgl;
@@ -203,6 +204,18 @@ struct Slot {
   std::vector<uint32_t> mtab, mfirst;
   std::vector<uint64_t> mkey;
   std::vector<uint32_t> msg_id;  // host copy of the set -> message map (msg_dedup)
+  // the message cache (lsg_msg_cache_set).  mc_ok: this package may use it (set by
+  // the submitter); mc_on: it was staged through it -- n_miss of the n_msgs distinct messages
+  // are staged and hashed, mc_hits come from arena rows (mc_pins: pinned until the launch's
+  // completion is observed), mc_pend rows are written by k_h2c_cache_store and published then.
+  // Plan arena: one source word per distinct message at mc_src_off, the (miss, row) pairs of
+  // the store at mc_st_off.
+  bool mc_ok = false, mc_on = false;
+  uint64_t mc_epoch = 0;
+  size_t n_miss = 0, mc_hits = 0, mc_src_off = 0, mc_st_off = 0;
+  std::vector<uint32_t> mc_pins, mc_pend;
+  std::vector<int32_t> mc_store;
+  DevBuf d_Hx, d_hinfx;  // the misses' points when some message hit
   SegPlan msum;                  // msg_agg: per message, the masked scaled keys of the package group
   DevBuf d_mmask, d_PmP, d_Pm, d_pinfm, d_errm;
   bool single_keys = false;  // every set has exactly one key (key i is set i's)
@@ -309,6 +322,10 @@ struct Dev {
   DevBuf d_cm_idx, d_cm_off, d_cm_sum;
   // lsg_verify_deposits: the call's DepositData and their signing roots (the packages' messages)
   DevBuf d_dep_in, d_dep_roots;
+  // the message cache (lsg_msg_cache_set): the policy, the arena of affine H(m) rows in the lane
+  // layout and one infinity flag per row
+  MsgCache mc;
+  DevBuf d_mc_rows, d_mc_inf;
   // kernel times of the last package / call completed on this device (lsg_last_kernel_times),
   // read from the slot's timing events when it completed, before the slot can be reused
   std::vector<std::pair<const char*, float>> last_times;
@@ -549,7 +566,7 @@ void slot_destroy(Slot* s) {
                     &s->d_nodeF, &s->d_nodeV, &s->d_plan, &s->d_mid, &s->d_Hm, &s->d_hinfm,
                     &s->d_mmask, &s->d_PmP, &s->d_Pm, &s->d_pinfm, &s->d_errm, &s->d_xport,
                     &s->d_agga, &s->d_aggi, &s->d_aggpre, &s->d_aggtot, &s->d_aggflag, &s->d_cbits,
-                    &s->d_gplan, &s->d_gsum, &s->d_gagg, &s->d_gtmp[0], &s->d_gtmp[1]};
+                    &s->d_gplan, &s->d_gsum, &s->d_gagg, &s->d_gtmp[0], &s->d_gtmp[1], &s->d_Hx, &s->d_hinfx};
   for (DevBuf* b : bufs) free_dev(*b);
   for (auto& u : s->seg_tmp)
     for (DevBuf& b : u) free_dev(b);
@@ -1085,7 +1102,22 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
     }
     return false;
   };
-  if (dedup && dedup_on && n > 1 && sample_repeats()) {
+  // the message cache (package staging only: s->mc_ok): every distinct message is looked up, so
+  // the table is always built -- the sample would hide messages that repeat across packages
+  MsgCache* mc = dedup && dedup_on && s->mc_ok && s->d->mc.capacity() ? &s->d->mc : nullptr;
+  s->mc_on = mc != nullptr;
+  s->n_miss = s->mc_hits = 0;
+  s->mc_pins.clear();
+  s->mc_pend.clear();
+  bool miss_obj = false;
+  if (mc) {
+    s->mc_epoch = mc->epoch();
+    s->mc_src_off = s->plan.size();
+    s->plan.resize(s->mc_src_off + n);
+  }
+  std::vector<int32_t>& mc_store = s->mc_store;  // (miss, row) pairs, appended to the plan below
+  mc_store.clear();
+  if (dedup && dedup_on && n > 0 && (mc || (n > 1 && sample_repeats()))) {
     cap = 16;
     while (cap < 2 * n) cap <<= 1;
     s->mtab.assign(cap, UINT32_MAX);
@@ -1101,8 +1133,9 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
     else
       memset(sg, 0, 96);
     uint32_t id = (uint32_t)nm;
+    uint64_t key = 0;
     if (cap) {
-      const uint64_t key = msg_key(q->msg, q->msg_len);
+      key = msg_key(q->msg, q->msg_len);
       for (size_t h = (size_t)key & (cap - 1);; h = (h + 1) & (cap - 1)) {
         const uint32_t e = s->mtab[h];
         if (e == UINT32_MAX) {
@@ -1120,7 +1153,37 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
       }
     }
     mid[i] = id;
-    if (id == nm) {  // a new message: staged once
+    if (id == nm && mc) {  // a new message: from its cache row, or staged (and hashed) as a miss
+      const uint32_t mb = msg_bytes(q->msg_len);
+      uint32_t row = 0;
+      bool hit = false, store = false;
+      if (!MsgCache::cacheable(mb) || !q->msg) {
+        mc->note_bypass();
+      } else {
+        const MsgCache::Result r = mc->lookup(key, q->msg, q->msg_len, mb, &row);
+        hit = r == MsgCache::HIT;
+        store = r == MsgCache::MISS && mc->allot(key, q->msg, q->msg_len, mb, &row);
+      }
+      if (hit) {
+        s->mc_pins.push_back(row);
+        s->mc_hits++;
+        s->plan[s->mc_src_off + nm] = (int32_t)(LSG_MC_ROW | row);
+      } else {
+        const size_t k = s->n_miss++;
+        if (store) {
+          s->mc_pend.push_back(row);
+          mc_store.push_back((int32_t)k);
+          mc_store.push_back((int32_t)row);
+        }
+        s->plan[s->mc_src_off + nm] = (int32_t)k;
+        msgoff[k] = (uint32_t)mo;
+        msglen[k] = q->msg_len;
+        miss_obj = miss_obj || msg_marked(q->msg_len);
+        if (mb) memcpy(A + o_msg + mo, q->msg, mb);
+        mo += mb;
+      }
+      nm++;
+    } else if (id == nm) {  // a new message: staged once
       msgoff[nm] = (uint32_t)mo;
       msglen[nm] = q->msg_len;  // (with its marker: k_msg_roots turns the payload into a 32-byte message)
       const uint32_t mb = msg_bytes(q->msg_len);
@@ -1168,7 +1231,12 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   }
   s->single_keys = single && n > 0;
   s->n_msgs = nm;
-  s->msg_objs = any_obj;
+  s->msg_objs = mc ? miss_obj : any_obj;
+  if (mc) {  // the source words of the nm distinct messages stay; the store's pairs follow them
+    s->plan.resize(s->mc_src_off + nm);
+    s->mc_st_off = s->plan.size();
+    s->plan.insert(s->plan.end(), mc_store.begin(), mc_store.end());
+  }
   s->msg_dedup = nm < n;
   if (s->msg_dedup) s->msg_id.assign(mid, mid + n);
   if (scale && n) {
@@ -1207,7 +1275,7 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   struct {
     DevBuf* d;
     size_t off, len;
-  } cp[] = {{&s->d_sig, o_sig, 192 * nn},      {&s->d_siglen, o_siglen, 4 * nn}, {&s->d_msg, o_msg, std::max(msg_total, (size_t)1)},
+  } cp[] = {{&s->d_sig, o_sig, 192 * nn},      {&s->d_siglen, o_siglen, 4 * nn}, {&s->d_msg, o_msg, std::max(mc ? mo : msg_total, (size_t)1)},
             {&s->d_msgoff, o_msgoff, 4 * nn}, {&s->d_msglen, o_msglen, 4 * nn}, {&s->d_pk, o_pk, ks * np},
             {&s->d_pklen, o_pklen, 4 * np},   {&s->d_rnd, o_rnd, 8 * nn}};
   for (auto& x : cp) LSG_HIP(s, hipMemcpyAsync(x.d->p, A + x.off, x.len, hipMemcpyHostToDevice, S));
@@ -1384,20 +1452,65 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
   s->cur = 0;
   // hash_to_G2 once per distinct message, then each set's point gathered from its message's
   const int nm = (int)s->n_msgs;
-  if (s->msg_objs)  // LSG_MSG_OBJECT messages: object + domain -> the 32-byte signing root, in place
-    KL(s, "k_msg_roots", lsgk::msg_roots(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
-                                         P_<uint32_t>(s->d_msglen)));
-  KL(s, "k_expand_msg", lsgk::expand_msg(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
-                                         P_<uint32_t>(s->d_msglen), P_<uint8_t>(s->d_dst), DST_POP_LEN,
-                                         P_<uint8_t>(s->d_ub)));
-  if (s->msg_dedup) {
-    LSG_RC(ensure(s, s->d_Hm, 4 * W_G2A * (size_t)nm));
-    LSG_RC(ensure(s, s->d_hinfm, (size_t)nm));
-    LSG_RC(launch_hash(s, nm, P_<uint32_t>(s->d_Hm), P_<uint8_t>(s->d_hinfm)));
-    KL(s, "k_h2c_gather", lsgk::h2c_gather(S_(s), n, P_<uint32_t>(s->d_mid), P_<uint32_t>(s->d_Hm),
-                                           P_<uint8_t>(s->d_hinfm), P_<uint32_t>(s->d_H), P_<uint8_t>(s->d_hinf)));
+  if (s->mc_on && (s->mc_hits || !s->mc_pend.empty())) {
+    // the message cache: only the nx misses are staged and hashed (none: no hash-stage kernel
+    // runs); with a hit among the messages they go to d_Hx and k_h2c_cache_merge fills the
+    // per-message (or, every set its own message, per-set) points from rows and misses
+    const int nx = (int)s->n_miss;
+    const bool merge = s->mc_hits > 0;
+    uint32_t* Hd = P_<uint32_t>(s->d_H);
+    uint8_t* hd = P_<uint8_t>(s->d_hinf);
+    if (s->msg_dedup) {
+      LSG_RC(ensure(s, s->d_Hm, 4 * W_G2A * (size_t)nm));
+      LSG_RC(ensure(s, s->d_hinfm, (size_t)nm));
+      Hd = P_<uint32_t>(s->d_Hm);
+      hd = P_<uint8_t>(s->d_hinfm);
+    }
+    uint32_t* Hx = Hd;
+    uint8_t* hx = hd;
+    if (merge) {
+      LSG_RC(ensure(s, s->d_Hx, 4 * W_G2A * (size_t)std::max(nx, 1)));
+      LSG_RC(ensure(s, s->d_hinfx, (size_t)std::max(nx, 1)));
+      Hx = P_<uint32_t>(s->d_Hx);
+      hx = P_<uint8_t>(s->d_hinfx);
+    }
+    if (nx > 0) {
+      if (s->msg_objs)
+        KL(s, "k_msg_roots", lsgk::msg_roots(S_(s), nx, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
+                                             P_<uint32_t>(s->d_msglen)));
+      KL(s, "k_expand_msg", lsgk::expand_msg(S_(s), nx, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
+                                             P_<uint32_t>(s->d_msglen), P_<uint8_t>(s->d_dst), DST_POP_LEN,
+                                             P_<uint8_t>(s->d_ub)));
+      LSG_RC(launch_hash(s, nx, Hx, hx));
+    }
+    const uint32_t n_rows = d->mc.capacity();
+    if (merge)
+      KL(s, "k_h2c_cache_merge",
+         lsgk::h2c_cache_merge(S_(s), nm, (const uint32_t*)PL(s, s->mc_src_off), n_rows, P_<uint32_t>(d->d_mc_rows),
+                               P_<uint8_t>(d->d_mc_inf), (uint32_t)nx, Hx, hx, Hd, hd));
+    if (!s->mc_pend.empty())
+      KL(s, "k_h2c_cache_store",
+         lsgk::h2c_cache_store(S_(s), (int)s->mc_pend.size(), (const uint32_t*)PL(s, s->mc_st_off), (uint32_t)nx, Hx, hx,
+                               n_rows, P_<uint32_t>(d->d_mc_rows), P_<uint8_t>(d->d_mc_inf)));
+    if (s->msg_dedup)
+      KL(s, "k_h2c_gather", lsgk::h2c_gather(S_(s), n, P_<uint32_t>(s->d_mid), P_<uint32_t>(s->d_Hm),
+                                             P_<uint8_t>(s->d_hinfm), P_<uint32_t>(s->d_H), P_<uint8_t>(s->d_hinf)));
   } else {
-    LSG_RC(launch_hash(s, n, P_<uint32_t>(s->d_H), P_<uint8_t>(s->d_hinf)));
+    if (s->msg_objs)  // LSG_MSG_OBJECT messages: object + domain -> the 32-byte signing root, in place
+      KL(s, "k_msg_roots", lsgk::msg_roots(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
+                                           P_<uint32_t>(s->d_msglen)));
+    KL(s, "k_expand_msg", lsgk::expand_msg(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
+                                           P_<uint32_t>(s->d_msglen), P_<uint8_t>(s->d_dst), DST_POP_LEN,
+                                           P_<uint8_t>(s->d_ub)));
+    if (s->msg_dedup) {
+      LSG_RC(ensure(s, s->d_Hm, 4 * W_G2A * (size_t)nm));
+      LSG_RC(ensure(s, s->d_hinfm, (size_t)nm));
+      LSG_RC(launch_hash(s, nm, P_<uint32_t>(s->d_Hm), P_<uint8_t>(s->d_hinfm)));
+      KL(s, "k_h2c_gather", lsgk::h2c_gather(S_(s), n, P_<uint32_t>(s->d_mid), P_<uint32_t>(s->d_Hm),
+                                             P_<uint8_t>(s->d_hinfm), P_<uint32_t>(s->d_H), P_<uint8_t>(s->d_hinf)));
+    } else {
+      LSG_RC(launch_hash(s, n, P_<uint32_t>(s->d_H), P_<uint8_t>(s->d_hinf)));
+    }
   }
   if (!miller_fused())
     KL(s, "k_miller_lines", lsgk::miller_lines(S_(s), n, P_<uint32_t>(s->d_H), P_<uint32_t>(s->d_lines)));
@@ -1615,7 +1728,8 @@ int launch_sig_prep(Slot* s, bool scale, const std::vector<uint8_t>* mode, uint3
 // msg bytes are placeholders then and are overwritten by a device copy.
 int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint64_t seed, int n_node,
               const std::vector<size_t>* subs = nullptr, bool lone_ok = true, const uint8_t* dev_msgs = nullptr,
-              const uint32_t* set_group = nullptr, size_t n_groups = 0, const uint64_t* rnd_in = nullptr) {
+              const uint32_t* set_group = nullptr, size_t n_groups = 0, const uint64_t* rnd_in = nullptr,
+              bool msg_cache = true) {
   timer_reset(s);
   s->plan.clear();
   memset(&s->stats, 0, sizeof(s->stats));
@@ -1655,7 +1769,10 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   s->sw = read_switches();
   s->gp = plan_groups(s->shape, s->sw, lone_ok);
   const uint64_t th0 = trace_host() ? now_ns() : 0;
-  LSG_RC(stage_sets(s, flat.data(), flat.size(), seed, true, &s->gp.noscale, dev_msgs == nullptr, true, rnd_in));
+  s->mc_ok = msg_cache;  // (only here: every other caller of stage_sets stays outside the message cache)
+  const int src = stage_sets(s, flat.data(), flat.size(), seed, true, &s->gp.noscale, dev_msgs == nullptr, true, rnd_in);
+  s->mc_ok = false;
+  LSG_RC(src);
   if (dev_msgs && !flat.empty())  // (placeholders are never merged: message i is set i's)
     LSG_HIP(s, hipMemcpyAsync(s->d_msg.p, dev_msgs, 32 * flat.size(), hipMemcpyDeviceToDevice, s->st[0]));
   // the byte keys of LSG_JOB_VALIDATE_KEYS jobs, compacted (table rows were validated when the
@@ -2032,6 +2149,22 @@ Slot* ticket_final(lsg_ctx* c, uint64_t t) {
   return s;
 }
 
+// The slot's launch is over for the message cache: its pinned rows are unpinned and the rows it
+// wrote become visible (ok: the host has observed the launch's completion) or free (a failed
+// submit, after sync_slot).  Idempotent: the first of wait and poll to observe it settles.
+void mc_settle(Slot* s, bool ok) {
+  if (!s->mc_on) return;
+  MsgCache& mc = s->d->mc;
+  mc.unpin(s->mc_epoch, s->mc_pins.data(), s->mc_pins.size());
+  if (ok)
+    mc.publish(s->mc_epoch, s->mc_pend.data(), s->mc_pend.size());
+  else
+    mc.drop(s->mc_epoch, s->mc_pend.data(), s->mc_pend.size());
+  s->mc_pins.clear();
+  s->mc_pend.clear();
+  s->mc_on = false;
+}
+
 void sync_slot(Slot* s) {
   for (int k = 0; k < 2; k++)
     if (s->st[k]) (void)hipStreamSynchronize(s->st[k]);
@@ -2081,7 +2214,7 @@ int pkg_exchange(lsg_ctx* c, int p) {
 // Errors go to *err (t_err_sink), not to c->err.
 int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t seed, bool lone_ok, bool exch,
               std::string* err, const uint8_t* dev_msgs = nullptr, const uint32_t* set_group = nullptr,
-              size_t n_groups = 0, const uint64_t* rnd_in = nullptr) {
+              size_t n_groups = 0, const uint64_t* rnd_in = nullptr, bool msg_cache = true) {
   const int n = c->n_dev;
   std::vector<std::vector<size_t>> ids(n);
   {
@@ -2099,7 +2232,8 @@ int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t se
     // distinct seeds per device for tests; 0 stays 0 (OS CSPRNG on every device)
     const uint64_t sd = seed ? seed + 0x9e3779b97f4a7c15ull * (uint64_t)d : 0;
     rcs[d] = pkg_part1(&c->dev[d]->slots[p], jobs, ids[d], sd, (d == 0 && exch) ? n : 0, nullptr, lone_ok && !exch,
-                       n == 1 ? dev_msgs : nullptr, n == 1 ? set_group : nullptr, n_groups, n == 1 ? rnd_in : nullptr);
+                       n == 1 ? dev_msgs : nullptr, n == 1 ? set_group : nullptr, n_groups, n == 1 ? rnd_in : nullptr,
+                       msg_cache);
     t_err_sink = nullptr;
   };
   auto part2 = [&](int d) {
@@ -2189,7 +2323,7 @@ int stage_pkg(lsg_ctx* c, int p, const lsg_job* jobs, size_t n_jobs, uint64_t se
 // lock again.  A reserved slot is SLOT_STAGING: no other call takes, reserves or waits on it.
 int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint64_t seed, lsg_ticket* ticket,
                bool lone_ok = true, const uint8_t* dev_msgs = nullptr, const uint32_t* set_group = nullptr,
-               size_t n_groups = 0, const uint64_t* rnd_in = nullptr) {
+               size_t n_groups = 0, const uint64_t* rnd_in = nullptr, bool msg_cache = true) {
   int p = -1;
   for (int i = 0; i < LSG_SLOTS && p < 0; i++)
     if (c->dev[0]->slots[i].kind == SLOT_FREE) p = i;
@@ -2210,7 +2344,7 @@ int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint
   c->staging++;
   lk.unlock();
   std::string err;
-  const int rc = stage_pkg(c, p, jobs, n_jobs, seed, lone_ok, exch, &err, dev_msgs, set_group, n_groups, rnd_in);
+  const int rc = stage_pkg(c, p, jobs, n_jobs, seed, lone_ok, exch, &err, dev_msgs, set_group, n_groups, rnd_in, msg_cache);
   lk.lock();
   (void)hipSetDevice(c->dev[0]->device);
   c->staging--;
@@ -2218,6 +2352,7 @@ int submit_pkg(lsg_ctx* c, CtxLock& lk, const lsg_job* jobs, size_t n_jobs, uint
   if (rc) {
     for (int d = 0; d < n; d++) {
       sync_slot(&c->dev[d]->slots[p]);
+      mc_settle(&c->dev[d]->slots[p], false);
       c->dev[d]->slots[p].kind = SLOT_FREE;
     }
     c->err = err;
@@ -2292,6 +2427,7 @@ int wait_pkg(lsg_ctx* c, CtxLock* lk, int p, int node_valid, lsg_job_result* res
     (void)hipSetDevice(c->dev[d]->device);
     if (event_wait(s->ev_done) != hipSuccess) rc = fail(s, "hipEventSynchronize", hipGetLastError());
   }
+  for (int d = 0; d < n; d++) mc_settle(&c->dev[d]->slots[p], rc == LSG_OK);
   Slot* s0 = &c->dev[0]->slots[p];
   // the ticket's own node check (lsg_init_devices) decides the package groups: 2 = passed
   if (!rc && node_valid == -2) node_valid = s0->has_node ? (H_<int32_t>(s0->h_nodeV)[0] ? 2 : 0) : -1;
@@ -2417,6 +2553,7 @@ int flush_pending(lsg_ctx* c) {
   if (!rc) rc = pkg_part2(s);
   if (rc) {
     sync_slot(s);
+    mc_settle(s, false);
     // every held package's wait (or poll) reports this failure -- its code and message --
     // instead of an unknown ticket; the entry goes when its ticket is waited on
     for (auto& pk : c->pending) {
@@ -2517,6 +2654,7 @@ int wait_merged(lsg_ctx* c, lsg_ticket t, lsg_job_result* results, lsg_stats* st
   LSG_HIPC(c, hipSetDevice(c->dev[0]->device));
   Slot* s = &c->dev[0]->slots[p];
   c->cv.wait(lk, [&] { return !s->resolving; });
+  mc_settle(s, true);
   if (!s->resolved) {  // the first waiter resolves every sub-package (fallback phases included)
     s->resolving = true;
     s->resolve_rc = pkg_resolve(s, &lk, -1, 0);
@@ -2679,6 +2817,8 @@ void dev_destroy(Dev* d) {
   free_dev(d->d_cm_sum);
   free_dev(d->d_dep_in);
   free_dev(d->d_dep_roots);
+  free_dev(d->d_mc_rows);
+  free_dev(d->d_mc_inf);
   if (d->s_util) (void)hipStreamDestroy(d->s_util);
   for (hipStream_t st : d->s_fe)
     if (st) (void)hipStreamDestroy(st);
@@ -2882,6 +3022,24 @@ int lsg_reserve(lsg_ctx* c, size_t max_sets, size_t max_pks, size_t max_msg_byte
       if (c->grouped_seen) {
         LSG_RC(size_groups(s, max_sets, max_sets));
         s->set_grp.reserve(max_sets);
+      }
+      // the message cache's per-slot buffers, once the context has one (lsg_msg_cache_set; as the
+      // bit arena above): the misses' points beside the per-message ones, which such a package
+      // always has -- its message table is always built -- with the per-message key sums
+      if (c->dev[d]->mc.capacity()) {
+        const size_t nn = std::max(max_sets, (size_t)1);
+        LSG_RC(ensure(s, s->d_Hx, 4 * W_G2A * nn));
+        LSG_RC(ensure(s, s->d_hinfx, nn));
+        LSG_RC(ensure(s, s->d_Hm, 4 * W_G2A * nn));
+        LSG_RC(ensure(s, s->d_hinfm, nn));
+        LSG_RC(ensure(s, s->d_mmask, 4 * W_G1P * nn));
+        LSG_RC(ensure(s, s->d_PmP, 4 * W_G1P * nn));
+        LSG_RC(ensure(s, s->d_Pm, 4 * W_G1A * nn));
+        LSG_RC(ensure(s, s->d_pinfm, nn));
+        LSG_RC(ensure(s, s->d_errm, 4 * nn));
+        s->mc_pins.reserve(max_sets);
+        s->mc_pend.reserve(max_sets);
+        s->mc_store.reserve(2 * max_sets);
       }
       LSG_RC(ensure_host(s, s->h_mode, std::max(max_sets, (size_t)1)));
       const size_t plan_words = 16 * max_sets + 4 * max_pks + 64 * 1024;
@@ -3108,6 +3266,7 @@ int lsg_poll(lsg_ctx* c, lsg_ticket ticket, int32_t* done) {
   if (!c || !done) return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);
   std::vector<hipEvent_t> evs;
+  std::vector<Slot*> mcs;
   if (Slot* f = ticket_final(c, ticket)) {
     evs.push_back(f->ev_done);
   } else if (((ticket >> 8) & 255) == SLOT_MERGE) {
@@ -3127,10 +3286,14 @@ int lsg_poll(lsg_ctx* c, lsg_ticket ticket, int32_t* done) {
       }
     }
     evs.push_back(c->dev[0]->slots[it->second.slot].ev_done);
+    mcs.push_back(&c->dev[0]->slots[it->second.slot]);
   } else {
     const int p = ticket_pkg(c, ticket);
     if (p < 0) return LSG_ERR_INVALID_ARG;
-    for (int d = 0; d < c->n_dev; d++) evs.push_back(c->dev[d]->slots[p].ev_done);
+    for (int d = 0; d < c->n_dev; d++) {
+      evs.push_back(c->dev[d]->slots[p].ev_done);
+      mcs.push_back(&c->dev[d]->slots[p]);
+    }
   }
   *done = 1;
   for (hipEvent_t e : evs) {
@@ -3141,6 +3304,7 @@ int lsg_poll(lsg_ctx* c, lsg_ticket ticket, int32_t* done) {
     }
     if (r != hipSuccess) return fail_c(c, "hipEventQuery", r);
   }
+  for (Slot* s : mcs) mc_settle(s, true);  // completion observed: the launch's cache rows become visible
   return LSG_OK;
 }
 
@@ -3163,7 +3327,8 @@ static int batch_partial(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint64_
     job.n_sets = (uint32_t)n_sets;
     job.flags = LSG_JOB_BATCHABLE;
     // the partial leaves: every r_i random
-    int rc = submit_pkg(c, lk, &job, 1, seed, &t, false, nullptr, nullptr, 0, rnd_in);
+    // (outside the message cache: this call frees its slot itself)
+    int rc = submit_pkg(c, lk, &job, 1, seed, &t, false, nullptr, nullptr, 0, rnd_in, false);
     if (rc) return rc;
   }
   const int prc = presync_pkg(c, t, false);
@@ -3405,6 +3570,83 @@ int lsg_pubkey_table_set(lsg_ctx* c, size_t first, const uint8_t* pks, uint32_t 
   (void)hipSetDevice(c->dev[0]->device);
   if (err)
     for (size_t k = 0; k < n; k++) err[k] = pkerr[k];
+  return LSG_OK;
+}
+
+// The message cache: per device an arena of `capacity` affine H(m) rows in the
+// lane layout with one infinity flag each, and the host policy's key store (lsg_msg_cache.hpp).
+// Like a pubkey-table rewrite it takes the staging lock exclusively and drains the devices;
+// what launches still unwaited pinned or wrote belongs to the epoch that ends here.
+static int msg_cache_reset(lsg_ctx* c, size_t capacity, bool realloc) {
+  std::unique_lock<std::shared_mutex> tab(c->tab_mu);  // no package is being staged
+  LSG_ENTER(c);
+  int rc = LSG_OK;
+  for (int i = 0; i < c->n_dev && !rc; i++) {
+    Dev* d = c->dev[i];
+    LSG_HIPC(c, hipSetDevice(d->device));
+    LSG_HIPC(c, hipDeviceSynchronize());
+    if (!realloc) {
+      d->mc.clear();
+      continue;
+    }
+    d->mc.resize(0);
+    free_dev(d->d_mc_rows);
+    free_dev(d->d_mc_inf);
+    if (!capacity) continue;
+    hipError_t e = hipMalloc(&d->d_mc_rows.p, 4 * W_G2A * capacity);
+    if (e == hipSuccess) {
+      g_allocs++;
+      d->d_mc_rows.cap = 4 * W_G2A * capacity;
+      e = hipMalloc(&d->d_mc_inf.p, capacity);
+    }
+    if (e == hipSuccess) {
+      g_allocs++;
+      d->d_mc_inf.cap = capacity;
+      e = hipMemset(d->d_mc_inf.p, 0, capacity);
+    }
+    if (e != hipSuccess) {
+      rc = fail_c(c, "hipMalloc", e);
+      break;
+    }
+    d->mc.resize(capacity);
+  }
+  if (rc)  // no half-enabled context: the cache is off on every device
+    for (int i = 0; i < c->n_dev; i++) {
+      (void)hipSetDevice(c->dev[i]->device);
+      c->dev[i]->mc.resize(0);
+      free_dev(c->dev[i]->d_mc_rows);
+      free_dev(c->dev[i]->d_mc_inf);
+    }
+  (void)hipSetDevice(c->dev[0]->device);
+  return rc;
+}
+
+int lsg_msg_cache_set(lsg_ctx* c, size_t capacity) {
+  if (!c || capacity >= LSG_MC_ROW) return LSG_ERR_INVALID_ARG;
+  return msg_cache_reset(c, capacity, true);
+}
+
+int lsg_msg_cache_clear(lsg_ctx* c) {
+  if (!c) return LSG_ERR_INVALID_ARG;
+  return msg_cache_reset(c, 0, false);
+}
+
+int lsg_msg_cache_get_stats(lsg_ctx* c, lsg_msg_cache_stats* out) {
+  if (!c || !out) return LSG_ERR_INVALID_ARG;
+  std::lock_guard<std::mutex> lk(c->mu);
+  memset(out, 0, sizeof(*out));
+  for (int i = 0; i < c->n_dev; i++) {
+    const MsgCacheStats t = c->dev[i]->mc.stats();
+    out->lookups += t.lookups;
+    out->hits += t.hits;
+    out->pending += t.pending;
+    out->inserts += t.inserts;
+    out->evictions += t.evictions;
+    out->bypassed += t.bypassed;
+    out->full += t.full;
+    out->entries += t.entries;
+    out->capacity += t.capacity;
+  }
   return LSG_OK;
 }
 

@@ -8,6 +8,7 @@
 //   k_h2c_map      SSWU (shared-norm square root) -> 3-isogeny, one per field element; Q0 + Q1
 //   k_h2c_clear    clear_cofactor (psi form); N(Z) for the second batched inversion
 //   k_h2c_affine   (X, Y) * conj(Z) / N(Z)
+//   k_h2c_cache_merge / k_h2c_cache_store   points read from / copied into the message cache
 #include "lsg_kcommon.hpp"
 
 // waves per SIMD for the SSWU map and the cofactor clearing: 2 (256 registers, some scratch)
@@ -217,6 +218,34 @@ __global__ void LSG_KERNEL_ATTR k_h2c_gather(int n, const uint32_t* __restrict__
   if (lead) hinf[item] = hinfm[m];
 }
 
+// The message cache (lsg_msg_cache_set; lsg_msg_cache.hpp).  src[m] names where
+// distinct message m's point is: row r of the device's arena (LSG_MC_ROW | r: a hit) or hashed
+// message k of this package (k: a miss, hashed into Hx).  Words out of range copy nothing.
+__global__ void LSG_KERNEL_ATTR k_h2c_cache_merge(int nm, const uint32_t* __restrict__ src, uint32_t n_rows,
+                                                  const uint32_t* __restrict__ rows, const uint8_t* __restrict__ rinf,
+                                                  uint32_t n_miss, const uint32_t* __restrict__ Hx,
+                                                  const uint8_t* __restrict__ hinfx, uint32_t* __restrict__ Hm,
+                                                  uint8_t* __restrict__ hinfm) {
+  LANE_ITEM(nm);
+  const uint32_t w = src[item], k = w & ~LSG_MC_ROW;
+  const bool hit = (w & LSG_MC_ROW) != 0;
+  if (k >= (hit ? n_rows : n_miss)) return;
+  lane_store(Hm, item, lane_load<g2a_t>(hit ? rows : Hx, k));
+  if (lead) hinfm[item] = hit ? rinf[k] : hinfx[k];
+}
+
+// the misses the host allotted a row to: item j copies hashed message list[2j] into row list[2j + 1]
+__global__ void LSG_KERNEL_ATTR k_h2c_cache_store(int n, const uint32_t* __restrict__ list, uint32_t n_miss,
+                                                  const uint32_t* __restrict__ Hx, const uint8_t* __restrict__ hinfx,
+                                                  uint32_t n_rows, uint32_t* __restrict__ rows,
+                                                  uint8_t* __restrict__ rinf) {
+  LANE_ITEM(n);
+  const uint32_t k = list[2 * item], r = list[2 * item + 1];
+  if (k >= n_miss || r >= n_rows) return;
+  lane_store(rows, r, lane_load<g2a_t>(Hx, k));
+  if (lead) rinf[r] = hinfx[k];
+}
+
 // stage 3: H affine = (X, Y) * conj(Z) / N(Z)   (= proj_to_aff, 1/Z = conj(Z) / N(Z))
 __global__ void LSG_KERNEL_ATTR k_h2c_affine(int n, const uint32_t* __restrict__ Hp, const uint32_t* __restrict__ ninv,
                                              const uint8_t* __restrict__ hinf, uint32_t* __restrict__ H) {
@@ -337,6 +366,15 @@ hipError_t h2c_clear(hipStream_t st, int n, uint32_t* Hp, uint32_t* zN, uint8_t*
 hipError_t h2c_gather(hipStream_t st, int n, const uint32_t* mid, const uint32_t* Hm, const uint8_t* hinfm, uint32_t* H,
                       uint8_t* hinf) {
   LSG_LAUNCH_ITEMS(k_h2c_gather, n, st, n, mid, Hm, hinfm, H, hinf);
+}
+hipError_t h2c_cache_merge(hipStream_t st, int nm, const uint32_t* src, uint32_t n_rows, const uint32_t* rows,
+                           const uint8_t* rinf, uint32_t n_miss, const uint32_t* Hx, const uint8_t* hinfx, uint32_t* Hm,
+                           uint8_t* hinfm) {
+  LSG_LAUNCH_ITEMS(k_h2c_cache_merge, nm, st, nm, src, n_rows, rows, rinf, n_miss, Hx, hinfx, Hm, hinfm);
+}
+hipError_t h2c_cache_store(hipStream_t st, int n, const uint32_t* list, uint32_t n_miss, const uint32_t* Hx,
+                           const uint8_t* hinfx, uint32_t n_rows, uint32_t* rows, uint8_t* rinf) {
+  LSG_LAUNCH_ITEMS(k_h2c_cache_store, n, st, n, list, n_miss, Hx, hinfx, n_rows, rows, rinf);
 }
 hipError_t h2c_affine(hipStream_t st, int n, const uint32_t* Hp, const uint32_t* ninv, const uint8_t* hinf,
                       uint32_t* H) {

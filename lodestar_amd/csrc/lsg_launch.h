@@ -9,6 +9,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+constexpr uint32_t LSG_MC_ROW = 0x80000000u;  // a message-cache source word that names an arena row
+
 namespace lsgk {
 // ---- hash_to_G2 (lsg_k_hash.hip)                                      SURVEY 8a M3
 hipError_t expand_msg(hipStream_t st, int n, const uint8_t* msg, const uint32_t* off, const uint32_t* len,
@@ -21,6 +23,15 @@ hipError_t h2c_gather(hipStream_t st, int n, const uint32_t* mid, const uint32_t
                       uint8_t* hinf);
 hipError_t h2c_affine(hipStream_t st, int n, const uint32_t* Hp, const uint32_t* ninv, const uint8_t* hinf,
                       uint32_t* H);
+// The message cache (lsg_msg_cache.hpp): a device arena of n_rows affine points `rows` with
+// their infinity flags `rinf`.  merge: Hm[m], hinfm[m] for the package's nm distinct messages
+// from src[m] = LSG_MC_ROW | row (a hit) or k (its k-th hashed message, in Hx / hinfx, n_miss of
+// them).  store: hashed message list[2j] into row list[2j + 1], n pairs.
+hipError_t h2c_cache_merge(hipStream_t st, int nm, const uint32_t* src, uint32_t n_rows, const uint32_t* rows,
+                           const uint8_t* rinf, uint32_t n_miss, const uint32_t* Hx, const uint8_t* hinfx, uint32_t* Hm,
+                           uint8_t* hinfm);
+hipError_t h2c_cache_store(hipStream_t st, int n, const uint32_t* list, uint32_t n_miss, const uint32_t* Hx,
+                           const uint8_t* hinfx, uint32_t n_rows, uint32_t* rows, uint8_t* rinf);
 hipError_t signing_root(hipStream_t st, int n, const uint8_t* roots, const uint8_t* domains, uint32_t dstride,
                         uint8_t* out32);
 hipError_t attestation_signing_root(hipStream_t st, int n, const uint8_t* data, const uint8_t* domains,

@@ -275,6 +275,25 @@ function loadCommitteesSync(addon, ctx, firstId, committees) {
   return Array.from(addon.committeesSet(ctx, firstId, indices, offsets));
 }
 
+/** options.msgCacheEntries rows of hashed messages H(m) per device, kept across packages
+ * (lsg_msg_cache_set; INTEGRATION.md "Message cache"), set once when the context opens; 0 or
+ * absent: the library is not called at all.  Returns the rows in effect. */
+function msgCacheOpen(addon, ctx, entries) {
+  const rows = entries === undefined || entries === null ? 0 : Number(entries);
+  if (!Number.isInteger(rows) || rows < 0) throw Error("msgCacheEntries must be a non-negative integer");
+  if (rows === 0) return 0;
+  if (typeof addon.msgCacheSet !== "function") throw Error("the addon does not support msgCacheEntries");
+  addon.msgCacheSet(ctx, rows);
+  return rows;
+}
+
+const MSG_CACHE_COUNTERS = ["lookups", "hits", "pending", "inserts", "evictions", "bypassed", "full", "entries", "capacity"];
+
+function msgCacheStatsSync(addon, ctx) {
+  if (typeof addon.msgCacheStats === "function") return addon.msgCacheStats(ctx);
+  return Object.fromEntries(MSG_CACHE_COUNTERS.map((k) => [k, 0]));
+}
+
 /** utils.ts:19-26 */
 function getAggregatedPubkeysCount(sets) {
   let n = 0;
@@ -708,7 +727,7 @@ class BlsGpuVerifier {
    * @param {{blsVerifyAllMultiThread?: boolean, device?: number, devices?: number[], seed?: number,
    *          maxSigsPerPackage?: number, eagerPackages?: number, minSigsWhenBusy?: number,
    *          maxPendingSigs?: number, bufferWaitMs?: number, reserveSets?: number,
-   *          reservePubkeys?: number, reserveMsgBytes?: number,
+   *          reservePubkeys?: number, reserveMsgBytes?: number, msgCacheEntries?: number,
    *          onAggregates?: (entries: {key: string, signature: Uint8Array, count: number, tags: any[]}[]) => void}} options
    *        onAggregates (SURVEY 8f(7)): with a handler, a set may carry `aggregateKey` (a string,
    *        e.g. the attestation data root) and `aggregateTag` (anything, e.g. the bit index): every
@@ -717,6 +736,9 @@ class BlsGpuVerifier {
    *        handler gets one call per package, after the verdicts are known and before the
    *        package's promises are settled (deliverAggregates).  Without a handler the two fields
    *        are ignored and packages go out exactly as before.
+   *        msgCacheEntries (default 0: off): rows of the per-device cache of hashed messages
+   *        H(m) kept across packages -- a slot's AttestationData are hashed once, not once per
+   *        package; 4096 holds three slots' worth with room for the singletons between them.
    * @param {{logger?: object, metrics?: object|null, addon?: object}} modules  addon is
    *        injectable (tests drive the queue logic with a mock of the addon's surface)
    *
@@ -751,6 +773,8 @@ class BlsGpuVerifier {
     this.minSigsWhenBusy = options.minSigsWhenBusy || Math.max(1, Math.floor(this.maxSigsPerPackage / 4));
     this.maxPendingSigs = options.maxPendingSigs || 4 * this.maxSigsPerPackage;
     this.bufferWaitMs = options.bufferWaitMs === undefined ? MAX_BUFFER_WAIT_MS : options.bufferWaitMs;
+    // the message cache (lsg_msg_cache_set), before the reservation, which sizes its buffers too
+    this.msgCacheEntries = msgCacheOpen(this.addon, this.ctx, options.msgCacheEntries);
     if (options.reserveSets && this.addon.reserve) {
       // preallocate every pipeline slot for packages of up to reserveSets sets (lsg_reserve)
       const pks = options.reservePubkeys || options.reserveSets;
@@ -792,6 +816,14 @@ class BlsGpuVerifier {
    * `pubkeyIndices` instead of PublicKeys.  Returns per-key BLST codes (0 = loaded). */
   loadPubkeys(firstIndex, pubkeys) {
     return this.addon.pubkeyTableSet(this.ctx, firstIndex, pubkeys.map(pubkeyBytes));
+  }
+
+  /** The message cache's counters summed over the devices (lsg_msg_cache_get_stats): lookups,
+   * hits, pending, inserts, evictions, bypassed, full, entries, capacity -- all 0 with
+   * msgCacheEntries 0. */
+  getMsgCacheStats() {
+    if (this.closed) throw new QueueError({code: QueueErrorCode.QUEUE_ABORTED});
+    return msgCacheStatsSync(this.addon, this.ctx);
   }
 
   /** Register committees on the device (SURVEY 8f(5); call where the node fills its shuffling
@@ -1133,7 +1165,7 @@ class BlsGpuVerifier {
  */
 class BlsGpuSingleThreadVerifier {
   /**
-   * @param {{device?: number, devices?: number[], seed?: number}} options
+   * @param {{device?: number, devices?: number[], seed?: number, msgCacheEntries?: number}} options
    * @param {{metrics?: object|null, addon?: object}} modules
    */
   constructor(options = {}, modules = {}) {
@@ -1141,6 +1173,13 @@ class BlsGpuSingleThreadVerifier {
     this.seed = options.seed || 0;
     this.addon = modules.addon || loadAddon();
     this.ctx = this.addon.open(Array.isArray(options.devices) ? options.devices : options.device || 0);
+    this.msgCacheEntries = msgCacheOpen(this.addon, this.ctx, options.msgCacheEntries);
+  }
+
+  /** as BlsGpuVerifier.getMsgCacheStats */
+  getMsgCacheStats() {
+    if (!this.ctx) throw new QueueError({code: QueueErrorCode.QUEUE_ABORTED});
+    return msgCacheStatsSync(this.addon, this.ctx);
   }
 
   async verifySignatureSets(sets, opts = {}) {

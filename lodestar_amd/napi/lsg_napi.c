@@ -46,7 +46,10 @@
  *       (a set descriptor may then have pk_len 8 = LSG_PK_BITS: committee id + bits, n_pks bits)
  *   objectSigningRoots(ctx, objs: n x objLen B, objLen, domain: 32 B | n x 32 B) -> Uint8Array(n x 32)
  *                                                                      lsg_object_signing_roots
- *       (these five throw "does not support" when the loaded library lacks the entry point)
+ *   msgCacheSet(ctx, rows)                                             lsg_msg_cache_set
+ *   msgCacheStats(ctx) -> {lookups, hits, pending, inserts, evictions, bypassed, full, entries, capacity}
+ *                                                                      lsg_msg_cache_get_stats
+ *       (these seven throw "does not support" when the loaded library lacks the entry point)
  *   A set's message may be an SSZ object followed by its 32-byte domain (LSG_MSG_OBJECT): the
  *   descriptor's msgLen word of verifyPacked carries 0x80000000 | length; a set of verifySets
  *   carries messageObject: true beside message.
@@ -76,6 +79,8 @@ extern int lsg_submit_jobs_grouped(lsg_ctx* ctx, const lsg_job* jobs, size_t n_j
                                    const uint32_t* set_group, size_t n_groups, lsg_ticket* ticket) __attribute__((weak));
 extern int lsg_wait_jobs_grouped(lsg_ctx* ctx, lsg_ticket ticket, lsg_job_result* results, lsg_stats* stats,
                                  uint8_t* agg96, uint32_t* agg_n) __attribute__((weak));
+extern int lsg_msg_cache_set(lsg_ctx* ctx, size_t capacity) __attribute__((weak));
+extern int lsg_msg_cache_get_stats(lsg_ctx* ctx, lsg_msg_cache_stats* out) __attribute__((weak));
 
 #define LSG_NAPI_THREADS 16 /* package threads per context: one outstanding package each */
 
@@ -1135,6 +1140,56 @@ static napi_value js_committees_clear(napi_env env, napi_callback_info info) {
   return NULL;
 }
 
+/* msgCacheSet(ctx, rows): keep up to `rows` hashed messages H(m) per device across packages (0: off);
+ * msgCacheStats(ctx) -> the cache's counters summed over the devices (lsg_msg_cache_set,
+ * lsg_msg_cache_get_stats) */
+static napi_value js_msg_cache_set(napi_env env, napi_callback_info info) {
+  size_t argc = 2;
+  napi_value argv[2];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  lsg_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  double rows = -1;
+  if (argc < 2 || napi_get_value_double(env, argv[1], &rows) != napi_ok || !(rows >= 0) || rows > 2147483647.0) {
+    napi_throw_type_error(env, NULL, "lsg_napi: msgCacheSet(ctx, rows)");
+    return NULL;
+  }
+  if (!lsg_msg_cache_set) {
+    napi_throw_error(env, NULL, "lsg_napi: the loaded library does not support msgCacheSet (no lsg_msg_cache_set)");
+    return NULL;
+  }
+  int rc = lsg_msg_cache_set(ctx, (size_t)rows);
+  if (rc) return throw_lsg(env, ctx, "lsg_msg_cache_set", rc);
+  return NULL;
+}
+
+static napi_value js_msg_cache_stats(napi_env env, napi_callback_info info) {
+  size_t argc = 1;
+  napi_value argv[1];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  lsg_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  if (!lsg_msg_cache_get_stats) {
+    napi_throw_error(env, NULL, "lsg_napi: the loaded library does not support msgCacheStats (no lsg_msg_cache_get_stats)");
+    return NULL;
+  }
+  lsg_msg_cache_stats st;
+  int rc = lsg_msg_cache_get_stats(ctx, &st);
+  if (rc) return throw_lsg(env, ctx, "lsg_msg_cache_get_stats", rc);
+  napi_value o;
+  NAPI_CALL(env, napi_create_object(env, &o));
+  set_int(env, o, "lookups", (int64_t)st.lookups);
+  set_int(env, o, "hits", (int64_t)st.hits);
+  set_int(env, o, "pending", (int64_t)st.pending);
+  set_int(env, o, "inserts", (int64_t)st.inserts);
+  set_int(env, o, "evictions", (int64_t)st.evictions);
+  set_int(env, o, "bypassed", (int64_t)st.bypassed);
+  set_int(env, o, "full", (int64_t)st.full);
+  set_int(env, o, "entries", st.entries);
+  set_int(env, o, "capacity", st.capacity);
+  return o;
+}
+
 /* sign(ctx, sks: Uint8Array(32n, big-endian), msgs: Uint8Array(32n)) -> Uint8Array(96n) and
  * skToPk(ctx, sks) -> Uint8Array(96n): test/bench input generation on the GPU (lsg_sign,
  * lsg_sk_to_pk), not on the verify path */
@@ -1205,6 +1260,8 @@ static napi_value init(napi_env env, napi_value exports) {
       {"pubkeyValidate", NULL, js_pubkey_validate, NULL, NULL, NULL, napi_enumerable, NULL},
       {"committeesSet", NULL, js_committees_set, NULL, NULL, NULL, napi_enumerable, NULL},
       {"committeesClear", NULL, js_committees_clear, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"msgCacheSet", NULL, js_msg_cache_set, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"msgCacheStats", NULL, js_msg_cache_stats, NULL, NULL, NULL, napi_enumerable, NULL},
   };
   NAPI_CALL(env, napi_define_properties(env, exports, sizeof props / sizeof props[0], props));
   return exports;
