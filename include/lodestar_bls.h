@@ -85,6 +85,29 @@ extern "C" {
  * bits sets.  lsg_aggregate_pubkeys (one key list) does not take it: 8 stays an unknown key
  * length there.  LSG_JOB_VALIDATE_KEYS leaves such sets alone, as it leaves index sets alone. */
 #define LSG_PK_BITS 8u
+/* lsg_set.pk_len value for keys named by a LIST of committees + one participation bitfield over
+ * their concatenation (an EIP-7549 aggregate: committee_bits + aggregation_bits).  n_pks is the
+ * total bit count; pks points at 4 + 4 k + ceil(n_pks / 8) bytes, no alignment assumed: a uint32
+ * k, the number of committees (host byte order), then k uint32 committee ids as registered with
+ * lsg_committees_set, then the bitfield in SSZ order without a delimiter bit.  Bit off_c + i is
+ * member i of the c-th listed committee, off_c the sum of the lengths of the committees listed
+ * before it; bits at positions >= n_pks are ignored, whatever they hold.  The set behaves exactly
+ * as the same set with LSG_PK_INDEX and the participating members' table indices, in list order
+ * and then committee order -- aggregates, verdicts, error codes and their precedence, batch
+ * counters, lsg_stats, exported partials and grouped aggregates.  Ids may repeat and need not
+ * ascend; a listed committee may have no participant.
+ *   LSG_ERR_BAD_COMMITTEE (routed exactly like LSG_ERR_BAD_INDEX, as for LSG_PK_BITS): a listed id
+ *     is unknown or unset, n_pks differs from the sum of the listed committees' lengths, or
+ *     k == 0 with n_pks > 0;
+ *   LSG_ERR_EMPTY_AGGREGATE: no bit set among the first n_pks (k == 0, n_pks == 0 included);
+ *   LSG_ERR_INVALID_ARG from the entry point, with nothing staged and the context usable:
+ *     k > LSG_MAX_SET_COMMITTEES or pks == NULL (caller bugs, as a bad LSG_MSG_OBJECT length is).
+ * Honoured wherever LSG_PK_BITS is, and a package may mix byte, index, bits and multi sets
+ * (aggregated by k_pk_agg_bits_multi, launched only by packages that hold such a set).
+ * lsg_aggregate_pubkeys (one key list) does not take it: 12 stays an unknown key length there.
+ * LSG_JOB_VALIDATE_KEYS leaves such sets alone. */
+#define LSG_PK_BITS_MULTI 12u
+#define LSG_MAX_SET_COMMITTEES 64u
 
 /* or'ed into lsg_set.msg_len: msg points at an SSZ-serialized object followed by its 32-byte
  * domain; the message signed is computeSigningRoot(object, domain)
@@ -211,7 +234,9 @@ int lsg_device_name(lsg_ctx* ctx, char* buf, size_t len);
  * stage packages at once; the devices of a multi-device context are staged in parallel).
  * A committee + bits set (LSG_PK_BITS) of n bits counts 16 + ceil(n / 32) toward max_pks; its
  * bit arena is reserved once the context has a committee registered (call lsg_reserve after
- * lsg_committees_set, or again). */
+ * lsg_committees_set, or again).  A multi-committee set (LSG_PK_BITS_MULTI) of n bits over k
+ * listed committees counts 16 + 2 k + ceil(n / 32): every part starts on its own arena word
+ * (at most ceil(n / 32) + k words) and the plan holds 5 + 4 k words plus up to 32 lane pairs. */
 int lsg_reserve(lsg_ctx* ctx, size_t max_sets, size_t max_pks, size_t max_msg_bytes, int32_t n_slots);
 /* Device + pinned allocations made by this process so far (steady-state checks). */
 int lsg_allocation_count(lsg_ctx* ctx, uint64_t* n);
@@ -326,7 +351,8 @@ int lsg_aggregate_pubkeys(lsg_ctx* ctx, const uint8_t* pks, uint32_t pk_len, siz
                           int32_t* err_code);
 /* PublicKey.aggregate for n_sets sets in one device pass (utils.ts:11 getAggregatedPubkey over
  * a block's aggregate sets, indexedAttestation.ts:21-47): set i's keys are sets[i].pks /
- * pk_len / n_pks (bytes, table indices, or a committee id + bits; msg and sig are ignored).  out96[96 i..] = set i's
+ * pk_len / n_pks (bytes, table indices, a committee id + bits, or a committee list + bits
+ * (LSG_PK_BITS_MULTI: k_pk_agg_bits_multi); msg and sig are ignored).  out96[96 i..] = set i's
  * uncompressed sum; err[i] = its first bad key's BLST_* / LSG_ERR_BAD_INDEX, or
  * LSG_ERR_EMPTY_AGGREGATE for no keys, LSG_ERR_BAD_COMMITTEE for a LSG_PK_BITS set naming no
  * registered committee of its length.  Every input size runs the jobs path's fused gather +

@@ -40,6 +40,8 @@ LSG_ERR_BAD_INDEX = 102
 LSG_ERR_BAD_COMMITTEE = 103
 LSG_PK_INDEX = 4  # lsg_set.pk_len for keys named by pubkey-table index
 LSG_PK_BITS = 8  # lsg_set.pk_len for keys named by committee id + participation bits
+LSG_PK_BITS_MULTI = 12  # lsg_set.pk_len for keys named by a committee list + one bitfield over them
+LSG_MAX_SET_COMMITTEES = 64
 LSG_MSG_OBJECT = 0x80000000  # or'ed into lsg_set.msg_len: msg is an SSZ object + its 32-byte domain
 
 
@@ -91,16 +93,41 @@ class PkBits:
         return struct.pack("=I", self.committee) + self.bits
 
 
+class PkBitsMulti:
+    """A set's pubkeys given as a LIST of committees registered with Context.committees_set plus
+    one participation bitfield over their concatenation, in list order (lsg_set.pk_len =
+    LSG_PK_BITS_MULTI: an EIP-7549 aggregate's committee_bits + aggregation_bits).  `bits` is the
+    SSZ bitlist's bytes without its delimiter bit, `n_bits` the bit count, which must equal the
+    sum of the listed committees' lengths.  Ids may repeat and need not ascend; the library
+    answers more than LSG_MAX_SET_COMMITTEES of them with LSG_ERR_INVALID_ARG.  Accepted
+    wherever PkBits is."""
+
+    def __init__(self, committees, bits, n_bits):
+        self.committees = [int(c) for c in committees]
+        self.n_bits = int(n_bits)
+        nb = (self.n_bits + 7) // 8
+        self.bits = bytes(bits)[:nb].ljust(nb, b"\0")
+
+    def __len__(self):
+        return self.n_bits
+
+    def tobytes(self):
+        k = len(self.committees)
+        return struct.pack("=I%dI" % k, k, *self.committees) + self.bits
+
+
 def _key_form(pks):
-    """(pk_len, n_pks, bytes) of a set's keys: encoded keys, PkIndices or PkBits"""
+    """(pk_len, n_pks, bytes) of a set's keys: encoded keys, PkIndices, PkBits or PkBitsMulti"""
     if isinstance(pks, PkBits):
         return LSG_PK_BITS, pks.n_bits, pks.tobytes()
+    if isinstance(pks, PkBitsMulti):
+        return LSG_PK_BITS_MULTI, pks.n_bits, pks.tobytes()
     if isinstance(pks, PkIndices):
         return LSG_PK_INDEX, len(pks), pks.tobytes()
     pk_len = len(pks[0]) if pks else 96
     if any(len(p) != pk_len for p in pks):
         raise ValueError("all pubkeys of one set must share one encoding length")
-    if pk_len == LSG_PK_BITS:  # 8-byte "keys" are an unknown key length, never committee + bits
+    if pk_len in (LSG_PK_BITS, LSG_PK_BITS_MULTI):  # 8- and 12-byte "keys" are an unknown key length, never a bits form
         pk_len = 0
     return pk_len, len(pks), b"".join(pks)
 
@@ -348,7 +375,9 @@ class PreparedJobs:
                        "itemsize": ctypes.sizeof(LsgSet)})
         v = np.frombuffer(self.sets, dtype=dt)
         if n:
-            v["pks"][:n] = np.where(n_pks[:n] > 0, self._pk.ctypes.data + pk_off[:n], 0)
+            # (a multi-committee set always has a blob: its count word; NULL there is a caller bug)
+            has_keys = (n_pks[:n] > 0) | (pk_len[:n] == LSG_PK_BITS_MULTI)
+            v["pks"][:n] = np.where(has_keys, self._pk.ctypes.data + pk_off[:n], 0)
             v["pk_len"][:n] = pk_len[:n]
             v["n_pks"][:n] = n_pks[:n]
             v["msg"][:n] = np.where(msg_len[:n] > 0, self._msg.ctypes.data + msg_off[:n], 0)

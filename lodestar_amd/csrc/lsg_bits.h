@@ -67,3 +67,49 @@ LSG_HD int32_t lsg_bits_next(const uint32_t* bits, uint32_t n_bits, uint32_t inv
     return m;
   }
 }
+
+// ---- a set spanning several committees (LSG_PK_BITS_MULTI; k_pk_agg_bits_multi): its parts,
+// one per listed committee with a wanted member or a stored sum to add, each with its own
+// word-aligned field and mode.  Plan words (lsg_plan.hpp plan_multi):
+//   per set:  first part, part count (0: write the identity), output slot, pairs log2, first pair
+//   per part: committee id, arena word, n_bits (>= 1), mode (bit 0: complement)
+#define LSG_MULTI_SET_WORDS 5
+#define LSG_MULTI_PART_WORDS 4
+
+// Pair j's walk over the wanted members of parts [0, n_parts) of one set, dealt round robin by
+// their rank ACROSS the parts: the skip count left over when a part's walk ends carries into
+// the next part's lsg_bits_begin.
+struct lsg_multi_walk {
+  uint32_t c;       // current part
+  uint32_t open;    // its walk has begun
+  uint32_t skip;    // carried into the next part
+  lsg_bits_walk w;
+};
+
+LSG_HD lsg_multi_walk lsg_multi_begin(uint32_t j) {
+  lsg_multi_walk s;
+  s.c = 0;
+  s.open = 0;
+  s.skip = j;
+  s.w.k = s.w.w = s.w.skip = 0;
+  return s;
+}
+
+// the next member this pair takes: its index in part s.c (parts: that set's part records), or
+// -1 when every part is exhausted
+LSG_HD int32_t lsg_multi_next(const int32_t* parts, uint32_t n_parts, const uint32_t* bits, uint32_t stride,
+                              lsg_multi_walk& s) {
+  for (; s.c < n_parts; s.c++, s.open = 0) {
+    const int32_t* q = parts + LSG_MULTI_PART_WORDS * s.c;
+    const uint32_t* field = bits + (uint32_t)q[1];
+    const uint32_t n_bits = (uint32_t)q[2], inv = (q[3] & 1) ? ~0u : 0u;
+    if (!s.open) {
+      s.w = lsg_bits_begin(field, n_bits, inv, s.skip);
+      s.open = 1;
+    }
+    const int32_t m = lsg_bits_next(field, n_bits, inv, stride, s.w);
+    if (m >= 0) return m;
+    s.skip = s.w.skip;
+  }
+  return -1;
+}

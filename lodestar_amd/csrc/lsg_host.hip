@@ -227,6 +227,12 @@ struct Slot {
   HostBuf h_cbits;
   DevBuf d_cbits;
   bool pk_all_bits = false;
+  // sets given as a committee list + one bitfield (LSG_PK_BITS_MULTI): their parts' fields in the
+  // same bit arena, aggregated by k_pk_agg_bits_multi (mplan) after k_pk_agg_bits; such a set is
+  // a bits set to everything else (shape.bits_p / bits_kerr, pk_all_bits)
+  std::vector<MultiSet> multi_sets;
+  std::vector<MultiPart> multi_parts;
+  MultiPlan mplan;
   // KeyValidate of the byte keys of LSG_JOB_VALIDATE_KEYS jobs: n_kv list items (staged key,
   // its set) in the plan arena at kv_off, kv_off + n_kv; shape.kv_set[i] != 0: set i's keys are
   // on the list (empty when the package has no such job: nothing staged, nothing launched)
@@ -1028,6 +1034,11 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   bool all_index = true;  // every key names a table row: 4-byte key slots (a block body's
                           // ~3.7M signers cross PCIe as 15 MB instead of 355 MB)
   auto is_bits = [&](const lsg_set* q) { return bits_ok && q->pk_len == LSG_PK_BITS; };
+  // a committee list + one bitfield (LSG_PK_BITS_MULTI): staged part by part into the same arena,
+  // every part on its own word; the entry points have refused a set without a blob or with more
+  // than LSG_MAX_SET_COMMITTEES ids (one that comes through all the same is a bad committee)
+  auto is_multi = [&](const lsg_set* q) { return bits_ok && q->pk_len == LSG_PK_BITS_MULTI; };
+  size_t n_multi = 0;
   for (size_t i = 0; i < n; i++) {
     msg_total += msg_bytes(sets[i]->msg_len);
     any_obj = any_obj || msg_marked(sets[i]->msg_len);
@@ -1036,18 +1047,26 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
       bit_words += bits_words(sets[i]->n_pks);
       continue;
     }
+    if (is_multi(sets[i])) {
+      n_multi++;
+      bit_words += bits_words(sets[i]->n_pks) + (multi_set_ok(*sets[i]) ? multi_k(*sets[i]) : 0);
+      continue;
+    }
     npk += sets[i]->n_pks;
     if (sets[i]->n_pks && sets[i]->pk_len != LSG_PK_INDEX) all_index = false;
   }
   s->bits_sets.clear();
   s->shape.bits_p.clear();
   s->shape.bits_kerr.clear();
-  s->pk_all_bits = n > 0 && n_bits_sets == n;
+  s->multi_sets.clear();
+  s->multi_parts.clear();
+  s->pk_all_bits = n > 0 && n_bits_sets + n_multi == n;
   uint32_t* cbits = nullptr;
-  if (n_bits_sets) {
+  if (n_bits_sets + n_multi) {
     s->shape.bits_p.assign(n, -1);
     s->shape.bits_kerr.assign(n, 0);
     s->bits_sets.reserve(n_bits_sets);
+    s->multi_sets.reserve(n_multi);
     LSG_RC(ensure_host(s, s->h_cbits, 4 * bit_words));
     LSG_RC(ensure(s, s->d_cbits, 4 * bit_words));
     cbits = H_<uint32_t>(s->h_cbits);
@@ -1076,7 +1095,7 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
   s->shape.pk_first.resize(n);
   s->rnd.resize(n);
   size_t mo = 0, po = 0, nm = 0;
-  bool single = npk == n && n_bits_sets == 0;
+  bool single = npk == n && n_bits_sets + n_multi == 0;
   // open-addressing table over the messages: slot -> distinct message id (mfirst: its set),
   // with the message's 64-bit key beside it so that a probe compares bytes only on a key match
   size_t cap = 0;
@@ -1207,6 +1226,30 @@ int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, boo
       s->bits_sets.push_back(b);
       continue;
     }
+    if (is_multi(q)) {
+      const lsg_ctx* c = s->d->c;
+      s->shape.pk_cnt[i] = 0;
+      s->shape.pk_first[i] = (uint32_t)po;
+      MultiSet m;
+      m.out = (int32_t)i;
+      m.first_part = (uint32_t)s->multi_parts.size();
+      uint32_t ids[LSG_MAX_SET_COMMITTEES], lens[LSG_MAX_SET_COMMITTEES];
+      const uint32_t k = multi_set_ok(*q) ? multi_k(*q) : 0;
+      bool ok = multi_set_ok(*q) && (k > 0 || q->n_pks == 0);
+      uint64_t total = 0;
+      if (ok && k) memcpy(ids, q->pks + 4, 4 * (size_t)k);
+      for (uint32_t e = 0; e < k && ok; e++) {
+        ok = ids[e] < c->cm_ok.size() && c->cm_ok[ids[e]];
+        if (ok) total += (lens[e] = c->cm_len[ids[e]]);
+      }
+      if (!ok || total != q->n_pks)
+        s->shape.bits_kerr[i] = LSG_ERR_BAD_COMMITTEE;
+      else
+        m = multi_stage_set(ids, lens, k, q->pks + 4 + 4 * (size_t)k, q->n_pks, (int32_t)i, cbits, &bw, s->multi_parts);
+      s->shape.bits_p[i] = (int32_t)m.p;
+      s->multi_sets.push_back(m);
+      continue;
+    }
     s->shape.pk_cnt[i] = q->n_pks;
     s->shape.pk_first[i] = (uint32_t)po;
     if (q->n_pks != 1) single = false;
@@ -1295,7 +1338,18 @@ int run_pk_bits(Slot* s, uint32_t* dst) {
                                            (uint32_t)d->pktab_n, dst));
   return LSG_OK;
 }
-
+// ... and of its LSG_PK_BITS_MULTI sets (k_pk_agg_bits_multi, plan s->mplan): after
+// k_pk_agg_bits, into their own slots
+int run_pk_multi(Slot* s, uint32_t* dst) {
+  if (s->multi_sets.empty()) return LSG_OK;
+  Dev* d = s->d;
+  KL(s, "k_pk_agg_bits_multi",
+     lsgk::pk_agg_bits_multi(S_(s), (int)s->mplan.n_pairs, PL(s, s->mplan.pair_off), PL(s, s->mplan.set_off),
+                             PL(s, s->mplan.part_off), P_<uint32_t>(s->d_cbits), P_<uint32_t>(d->d_cm_idx),
+                             P_<uint32_t>(d->d_cm_off), P_<uint32_t>(d->d_cm_sum), P_<uint32_t>(d->d_pktab),
+                             P_<uint8_t>(d->d_pktab_ok), (uint32_t)d->pktab_n, dst));
+  return LSG_OK;
+}
 
 // Miller accumulation of planned items (after ev_sig on the main stream)
 int launch_accum(Slot* s, size_t n_items, size_t item_off, uint32_t* fall, bool single = false) {
@@ -1414,6 +1468,7 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
   // committee + bits sets: their aggregates over whatever run_pk_seg left in their slots (the
   // identity of a set without staged keys)
   LSG_RC(run_pk_bits(s, P_<uint32_t>(s->d_agg)));
+  LSG_RC(run_pk_multi(s, P_<uint32_t>(s->d_agg)));
   // flagged jobs' byte keys: KeyValidate codes per list item (d_pkp is free in a package: the
   // keys decode straight into their aggregates); applied to the sets after the signature stages
   if (s->n_kv)
@@ -1786,7 +1841,8 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
     for (size_t k = 0; k < nj; k++) {
       if (!(s->shape.jobs[k].flags & LSG_JOB_VALIDATE_KEYS)) continue;
       for (size_t i = s->shape.jobs[k].first; i < s->shape.jobs[k].first + s->shape.jobs[k].count; i++)
-        if (flat[i]->pk_len != LSG_PK_INDEX && flat[i]->pk_len != LSG_PK_BITS && s->shape.pk_cnt[i]) {
+        if (flat[i]->pk_len != LSG_PK_INDEX && flat[i]->pk_len != LSG_PK_BITS && flat[i]->pk_len != LSG_PK_BITS_MULTI &&
+            s->shape.pk_cnt[i]) {
           s->shape.kv_set[i] = 1;
           s->n_kv += s->shape.pk_cnt[i];
         }
@@ -1811,12 +1867,13 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   LSG_RC(size_state(s, s->n_sets, s->n_pks, A.groups.size(), n_msm, 1));
   s->agg = AggPlan();
   if (!s->single_keys && !s->pk_all_bits) {
-    if (s->n_pks >= AGG_TREE_MIN_KEYS && agg_tree_on() && s->bits_sets.empty())
+    if (s->n_pks >= AGG_TREE_MIN_KEYS && agg_tree_on() && s->bits_sets.empty() && s->multi_sets.empty())
       s->agg = plan_agg_tree(s);
     else
       s->pkagg = plan_pk_agg(s);
   }
   s->bplan = plan_bits(s->plan, s->bits_sets);
+  s->mplan = plan_multi(s->plan, s->multi_sets, s->multi_parts);
   // sets of the package group that share a message share one Miller pair: Π e(r_i pk_i, H(m))
   // = e(Σ r_i pk_i, H(m)) exactly.  Its per-set items are then never computed, so a failing
   // package group's chunks (phase B) run their own items and phase C goes per job.
@@ -2476,6 +2533,7 @@ int wait_pkg(lsg_ctx* c, CtxLock* lk, int p, int node_valid, lsg_job_result* res
 size_t set_key_bytes(const lsg_set& t) {
   if (!t.pks) return 0;
   if (t.pk_len == LSG_PK_BITS) return 4 + (((size_t)t.n_pks + 7) >> 3);
+  if (t.pk_len == LSG_PK_BITS_MULTI) return 4 + 4 * (size_t)multi_k(t) + (((size_t)t.n_pks + 7) >> 3);  // (k checked on entry)
   return (size_t)t.n_pks * (t.pk_len == LSG_PK_INDEX ? 4 : t.pk_len);
 }
 PendingPkg copy_pkg(const lsg_job* jobs, size_t n_jobs, uint64_t seed) {
@@ -3012,7 +3070,9 @@ int lsg_reserve(lsg_ctx* c, size_t max_sets, size_t max_pks, size_t max_msg_byte
       // the bit arena of committee + bits sets, once the context has committees (a context that
       // never registers one reserves what it did before): a bits set of n bits counts
       // 16 + ceil(n / 32) toward max_pks, which covers its 4 ceil(n / 32) arena bytes here and
-      // its plan words (6 + up to 32 lane pairs) below
+      // its plan words (6 + up to 32 lane pairs) below; a multi-committee set of n bits over k
+      // committees counts 16 + 2 k + ceil(n / 32): at most ceil(n / 32) + k arena words, and
+      // 5 + 4 k plan words + up to 32 lane pairs
       if (!c->cm_ok.empty()) {
         LSG_RC(ensure_host(s, s->h_cbits, 4 * max_pks));
         LSG_RC(ensure(s, s->d_cbits, 4 * max_pks));
@@ -3505,10 +3565,12 @@ int lsg_aggregate_pubkeys(lsg_ctx* c, const uint8_t* pks, uint32_t pk_len, size_
 
 int lsg_aggregate_pubkeys_multi(lsg_ctx* c, const lsg_set* sets, size_t n_sets, uint8_t* out96, int32_t* err) {
   if (!c || (n_sets && (!sets || !out96 || !err)) || n_sets > 0x7fffffffull) return LSG_ERR_INVALID_ARG;
-  for (size_t i = 0; i < n_sets; i++)
+  for (size_t i = 0; i < n_sets; i++) {
     if (sets[i].n_pks && (!sets[i].pks || (sets[i].pk_len != 48 && sets[i].pk_len != 96 && sets[i].pk_len != LSG_PK_INDEX &&
-                                            sets[i].pk_len != LSG_PK_BITS)))
+                                            sets[i].pk_len != LSG_PK_BITS && sets[i].pk_len != LSG_PK_BITS_MULTI)))
       return LSG_ERR_INVALID_ARG;
+    if (!multi_set_ok(sets[i])) return LSG_ERR_INVALID_ARG;
+  }
   LSG_ENTER(c);
   Dev* d = c->dev[0];
   Slot* s = &d->util;
@@ -3527,13 +3589,14 @@ int lsg_aggregate_pubkeys_multi(lsg_ctx* c, const lsg_set* sets, size_t n_sets, 
   const size_t np = s->n_pks;
   LSG_RC(size_state(s, n_sets, np, 1, 0));
   s->plan.clear();
-  const bool tree = np >= AGG_TREE_MIN_KEYS && agg_tree_on() && s->bits_sets.empty();
+  const bool tree = np >= AGG_TREE_MIN_KEYS && agg_tree_on() && s->bits_sets.empty() && s->multi_sets.empty();
   s->single_keys = false;
   if (tree)
     s->agg = plan_agg_tree(s);
   else if (!s->pk_all_bits)
     s->pkagg = plan_pk_agg(s);
   s->bplan = plan_bits(s->plan, s->bits_sets);
+  s->mplan = plan_multi(s->plan, s->multi_sets, s->multi_parts);
   LSG_RC(upload_plan(s));
   if (tree) {
     LSG_RC(launch_agg_tree(s, s->agg, P_<uint32_t>(s->d_agg)));
@@ -3541,6 +3604,7 @@ int lsg_aggregate_pubkeys_multi(lsg_ctx* c, const lsg_set* sets, size_t n_sets, 
     LSG_RC(run_pk_seg(s, s->pkagg, P_<uint32_t>(s->d_agg)));
   }
   LSG_RC(run_pk_bits(s, P_<uint32_t>(s->d_agg)));
+  LSG_RC(run_pk_multi(s, P_<uint32_t>(s->d_agg)));
   LSG_RC(ensure(s, s->d_aux, 96 * n_sets));
   KL(s, "k_g1p_to_bytes", lsgk::g1p_to_bytes(S_(s), (int)n_sets, P_<uint32_t>(s->d_agg), P_<uint8_t>(s->d_aux)));
   std::vector<int32_t> pkerr(std::max(np, (size_t)1));

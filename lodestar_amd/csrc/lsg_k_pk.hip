@@ -165,6 +165,80 @@ __global__ void LSG_KERNEL_ATTR k_pk_agg_bits(int n_pairs, const int32_t* __rest
   }
 }
 
+// PublicKey.aggregate of sets given as a committee list + one bitfield (LSG_PK_BITS_MULTI: an
+// EIP-7549 aggregate).  Lane pair `item` works for set entry pair_set[item] (lsg_plan.hpp
+// plan_multi; words: lsg_bits.h).  A set is parts, one per listed committee, each with its own
+// word-aligned field and mode; its pairs share the wanted members of ALL its parts round robin
+// by their rank across the parts (lsg_multi_next: the skip count left when a part ends carries
+// into the next), gathered as in k_pk_agg_bits with the next row in flight while this one is
+// added.  A member of a complement part is added NEGATED (y only), so one accumulator takes
+// every part; the complement parts' stored sums are then dealt round robin to the set's pairs
+// and added with the complete addition.  The aggregate is that signed sum: no subtraction at
+// the end, and no exceptional case (acc or a sum at infinity, acc == +-sum).  Butterfly and
+// store as in k_pk_agg_bits; a set without parts writes the identity.
+__global__ void LSG_KERNEL_ATTR k_pk_agg_bits_multi(int n_pairs, const int32_t* __restrict__ pair_set,
+                                                    const int32_t* __restrict__ set_plan,
+                                                    const int32_t* __restrict__ part_plan,
+                                                    const uint32_t* __restrict__ bits, const uint32_t* __restrict__ cm_idx,
+                                                    const uint32_t* __restrict__ cm_off, const uint32_t* __restrict__ cm_sum,
+                                                    const uint32_t* __restrict__ tab, const uint8_t* __restrict__ tab_ok,
+                                                    uint32_t tab_n, uint32_t* __restrict__ dst) {
+  lsg_lane_setup();
+  const size_t item = gtid() / LSG_GROUP;
+  const bool active = item < (size_t)n_pairs;
+  g1p_t acc = proj_inf<fp_t>();
+  int ips = 1, j = 0, out = 0;
+  if (active) {
+    const int32_t* q = set_plan + LSG_MULTI_SET_WORDS * (size_t)pair_set[item];
+    const int32_t* parts = part_plan + LSG_MULTI_PART_WORDS * (size_t)q[0];
+    const uint32_t n_parts = (uint32_t)q[1];
+    out = q[2];
+    ips = 1 << q[3];
+    j = (int)item - q[4];
+    // member m of the walk's current part: false for the infinity key; neg: a complement part
+    auto fetch = [&](const lsg_multi_walk& w, int32_t m, g1a_t& a, bool& neg) {
+      const int32_t* p = parts + LSG_MULTI_PART_WORDS * w.c;
+      const uint32_t idx = cm_idx[cm_off[(uint32_t)p[0]] + (uint32_t)m];
+      const uint8_t ok = idx < tab_n ? tab_ok[idx] : 0;
+      a = lane_load<g1a_t>(tab + (size_t)(ok == 1 ? idx : 0) * lsgl::W_TAB, 0);
+      neg = (p[3] & 1) != 0;
+      return ok == 1;
+    };
+    lsg_multi_walk w = lsg_multi_begin((uint32_t)j);
+    g1a_t a;
+    bool fin = false, neg = false;
+    int32_t m = lsg_multi_next(parts, n_parts, bits, (uint32_t)ips, w);
+    if (m >= 0) fin = fetch(w, m, a, neg);
+#pragma unroll 1
+    while (m >= 0) {
+      g1a_t cur = a;
+      const bool cur_fin = fin, cur_neg = neg;
+      m = lsg_multi_next(parts, n_parts, bits, (uint32_t)ips, w);
+      if (m >= 0) fin = fetch(w, m, a, neg);
+      if (cur_fin) {
+        if (cur_neg) cur.y = fp_neg(cur.y);
+        acc = proj_is_inf(acc) ? proj_from_aff(cur) : g1_add_mixed(acc, cur);
+      }
+    }
+    // the stored sums of the complement parts, the r-th of them to pair r mod ips
+    uint32_t r = 0;
+#pragma unroll 1
+    for (uint32_t c = 0; c < n_parts; c++) {
+      const int32_t* p = parts + LSG_MULTI_PART_WORDS * c;
+      if (!(p[3] & 1)) continue;
+      if ((int)(r & (uint32_t)(ips - 1)) == j) acc = g1_add(acc, lane_load<g1p_t>(cm_sum, (size_t)(uint32_t)p[0]));
+      r++;
+    }
+  }
+  // every lane shuffles; a lane adds while the partner is one of its own set's pairs
+#pragma unroll 1
+  for (int o = 16; o >= 1; o >>= 1) {
+    const g1p_t t = shfl_xor_t(acc, LSG_GROUP * o);
+    if (o < ips) acc = g1_add(acc, t);
+  }
+  if (active && j == 0) lane_store(dst, (size_t)out, acc);
+}
+
 // pubkey -> affine G1 + infinity flag: the rows (lsgl::W_TAB words each) of lsg_pubkey_table_set
 __global__ void LSG_KERNEL_ATTR k_pk_gather_aff(int n, const uint8_t* __restrict__ pk, uint32_t stride,
                                                 const uint32_t* __restrict__ pk_len, uint32_t* __restrict__ pts,
@@ -576,6 +650,13 @@ hipError_t pk_agg_bits(hipStream_t st, int n_pairs, const int32_t* pair_set, con
                        const uint8_t* tab_ok, uint32_t tab_n, uint32_t* dst) {
   LSG_LAUNCH_ITEMS(k_pk_agg_bits, n_pairs, st, n_pairs, pair_set, plan, bits, cm_idx, cm_off, cm_sum, tab, tab_ok, tab_n,
                    dst);
+}
+hipError_t pk_agg_bits_multi(hipStream_t st, int n_pairs, const int32_t* pair_set, const int32_t* set_plan,
+                             const int32_t* part_plan, const uint32_t* bits, const uint32_t* cm_idx, const uint32_t* cm_off,
+                             const uint32_t* cm_sum, const uint32_t* tab, const uint8_t* tab_ok, uint32_t tab_n,
+                             uint32_t* dst) {
+  LSG_LAUNCH_ITEMS(k_pk_agg_bits_multi, n_pairs, st, n_pairs, pair_set, set_plan, part_plan, bits, cm_idx, cm_off, cm_sum,
+                   tab, tab_ok, tab_n, dst);
 }
 hipError_t agg_leaf(hipStream_t st, const AggTreeArgs& a) {
   if (a.L <= 0) return hipSuccess;

@@ -99,6 +99,12 @@ hipError_t pk_agg_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t*
 hipError_t pk_agg_bits(hipStream_t st, int n_pairs, const int32_t* pair_set, const int32_t* plan, const uint32_t* bits,
                        const uint32_t* cm_idx, const uint32_t* cm_off, const uint32_t* cm_sum, const uint32_t* tab,
                        const uint8_t* tab_ok, uint32_t tab_n, uint32_t* dst);
+// ... and of the sets given as a committee list + one bitfield (k_pk_agg_bits_multi; plan:
+// lsg_plan.hpp plan_multi): pair_set / set_plan / part_plan are the plan's three arena ranges
+hipError_t pk_agg_bits_multi(hipStream_t st, int n_pairs, const int32_t* pair_set, const int32_t* set_plan,
+                             const int32_t* part_plan, const uint32_t* bits, const uint32_t* cm_idx, const uint32_t* cm_off,
+                             const uint32_t* cm_sum, const uint32_t* tab, const uint8_t* tab_ok, uint32_t tab_n,
+                             uint32_t* dst);
 // the batch-affine aggregation tree (lsg_k_pk.hip k_agg_*; plan: lsg_host.hip plan_agg_tree).
 // Level 0 holds every tree set's keys at an offset aligned to 2^L, padded with infinity up to
 // the next multiple (N0 points); level t + 1 point q is the sum of level t points 2q and

@@ -387,9 +387,19 @@ inline uint32_t msg_object_kind(uint32_t msg_len) {
 // A marked set must select a kind and carry its bytes: anything else is a caller bug, answered
 // with LSG_ERR_INVALID_ARG before a slot is taken.  Unmarked sets pass as they are.
 inline bool msg_set_ok(const lsg_set& t) { return !msg_marked(t.msg_len) || (t.msg && msg_object_kind(t.msg_len)); }
+// Likewise a multi-committee set (LSG_PK_BITS_MULTI) without a blob, or listing more than
+// LSG_MAX_SET_COMMITTEES committees.  multi_k: the blob's leading count.
+inline uint32_t multi_k(const lsg_set& t) {
+  uint32_t k = 0;
+  memcpy(&k, t.pks, 4);
+  return k;
+}
+inline bool multi_set_ok(const lsg_set& t) {
+  return t.pk_len != LSG_PK_BITS_MULTI || (t.pks && multi_k(t) <= LSG_MAX_SET_COMMITTEES);
+}
 inline bool msg_sets_ok(const lsg_set* sets, size_t n) {
   for (size_t i = 0; i < n; i++)
-    if (!msg_set_ok(sets[i])) return false;
+    if (!msg_set_ok(sets[i]) || !multi_set_ok(sets[i])) return false;
   return true;
 }
 inline bool msg_jobs_ok(const lsg_job* jobs, size_t n_jobs) {
@@ -662,6 +672,136 @@ inline BitsPlan plan_bits(std::vector<int32_t>& A, const std::vector<BitsSet>& s
     pair += (size_t)1 << lg[i];
   }
   P.n_pairs = pair;
+  P.pair_off = A.size();
+  for (size_t e = 0; e < order.size(); e++) A.insert(A.end(), (size_t)1 << lg[order[e]], (int32_t)e);
+  return P;
+}
+
+// ---- sets spanning several committees (LSG_PK_BITS_MULTI): a committee list + one bitfield
+// over the concatenation of the listed committees (an EIP-7549 aggregate).  The set is k parts,
+// one per listed committee; part c's sub-field starts at bit off_c of the caller's field --
+// generally not on a word boundary -- and is copied, shifted, into its own word-aligned run of
+// the bit arena, so the walk of lsg_bits.h runs on a part unchanged.  Each part has its own
+// mode (bits_complement).  The set's ITEMS are every wanted member of every part (sign + in
+// direct mode, - in complement mode) and every complement part's stored sum (sign +): the
+// aggregate is the signed sum of the items, no final subtraction.
+//
+// n_bits bits of src from bit bit_off on, as the words of a staged field (tail of the last
+// word zeroed, as bits_stage leaves it); src is read up to the byte of bit bit_off + n_bits - 1
+inline void bits_stage_shifted(uint32_t* dst, const uint8_t* src, uint64_t bit_off, uint32_t n_bits) {
+  const size_t nw = bits_words(n_bits);
+  const uint8_t* b = src + (bit_off >> 3);
+  const unsigned sh = (unsigned)(bit_off & 7);
+  const size_t nb = ((size_t)sh + n_bits + 7) >> 3;  // source bytes holding the run
+  for (size_t w = 0; w < nw; w++) {
+    uint64_t v = 0;  // the 5 bytes from 4 w on: 32 bits after any shift below 8
+    for (size_t k = 0; k < 5 && 4 * w + k < nb; k++) v |= (uint64_t)b[4 * w + k] << (8 * k);
+    dst[w] = (uint32_t)(v >> sh);
+  }
+  if (n_bits & 31) dst[nw - 1] &= (1u << (n_bits & 31)) - 1u;
+}
+// participants among the n_bits bits of src from bit bit_off on
+inline uint32_t bits_count_range(const uint8_t* src, uint64_t bit_off, uint32_t n_bits) {
+  uint32_t p = 0;
+  uint64_t k = bit_off;
+  const uint64_t end = bit_off + n_bits;
+  for (; k < end && (k & 7); k++) p += (src[k >> 3] >> (k & 7)) & 1u;
+  for (; k + 8 <= end; k += 8) p += (uint32_t)__builtin_popcount(src[k >> 3]);
+  for (; k < end; k++) p += (src[k >> 3] >> (k & 7)) & 1u;
+  return p;
+}
+
+struct MultiPart {
+  uint32_t committee = 0;
+  uint32_t word_off = 0;  // its field's first word in the bit arena
+  uint32_t n_bits = 0;
+  uint32_t p = 0;         // participants
+};
+// One multi set as staged: n_parts == 0 means "write the identity" (a set whose error the host
+// already knows, or with no participant).  items: wanted members + complement parts' sums.
+struct MultiSet {
+  uint32_t first_part = 0, n_parts = 0;
+  uint32_t p = 0;      // participants over all parts
+  uint32_t items = 0;
+  int32_t out = 0;     // aggregate slot (the set's staging position)
+};
+// A set of k registered committees (ids, their lengths lens: n_bits == their sum) as the stager
+// records it: the parts with an item appended to `parts`, their fields to the arena (*words in
+// use; at most ceil(n_bits / 32) + k words).  A part without a participant has no item and is
+// left out; with no participant at all the set is the identity entry and nothing is staged.
+inline MultiSet multi_stage_set(const uint32_t* ids, const uint32_t* lens, uint32_t k, const uint8_t* bits,
+                                uint32_t n_bits, int32_t out, uint32_t* arena, size_t* words,
+                                std::vector<MultiPart>& parts) {
+  MultiSet m;
+  m.out = out;
+  m.first_part = (uint32_t)parts.size();
+  if (!bits_count(bits, n_bits)) return m;
+  uint64_t off = 0;
+  for (uint32_t c = 0; c < k; off += lens[c], c++) {
+    MultiPart q;
+    q.p = bits_count_range(bits, off, lens[c]);
+    if (!q.p) continue;
+    q.committee = ids[c];
+    q.word_off = (uint32_t)*words;
+    q.n_bits = lens[c];
+    bits_stage_shifted(arena + *words, bits, off, lens[c]);
+    *words += bits_words(lens[c]);
+    parts.push_back(q);
+    m.n_parts++;
+    m.p += q.p;
+    m.items += bits_wanted(q.n_bits, q.p) + (bits_complement(q.n_bits, q.p) ? 1u : 0u);
+  }
+  return m;
+}
+// Plan of k_pk_agg_bits_multi (words: lsg_bits.h).  A set gets 2^l lane pairs from its item
+// count by the rule of bits_pairs_log2 -- at most one wave's 32 pairs, the serial fold grows
+// beyond -- and the sets are laid out widest first, so a set starts on a multiple of its width
+// and never straddles a wave.  While the launch is work-bound the fold doubles, as in plan_bits.
+constexpr int MULTI_SET_WORDS = LSG_MULTI_SET_WORDS;
+constexpr int MULTI_PART_WORDS = LSG_MULTI_PART_WORDS;
+struct MultiPlan {
+  size_t n_sets = 0, n_pairs = 0;
+  int fold = BITS_FOLD;
+  size_t set_off = 0;   // n_sets x MULTI_SET_WORDS words in the arena
+  size_t part_off = 0;  // every part x MULTI_PART_WORDS words
+  size_t pair_off = 0;  // n_pairs words: the plan entry each lane pair works for
+};
+inline MultiPlan plan_multi(std::vector<int32_t>& A, const std::vector<MultiSet>& sets,
+                            const std::vector<MultiPart>& parts) {
+  MultiPlan P;
+  P.n_sets = sets.size();
+  if (sets.empty()) return P;
+  std::vector<uint32_t> order(sets.size());
+  std::vector<int> lg(sets.size());
+  for (;; P.fold *= 2) {
+    size_t pairs = 0;
+    for (size_t i = 0; i < sets.size(); i++) {
+      order[i] = (uint32_t)i;
+      lg[i] = sets[i].n_parts ? bits_pairs_log2(sets[i].items, P.fold) : 0;
+      pairs += (size_t)1 << lg[i];
+    }
+    if (pairs <= BITS_WIDE_PAIRS || P.fold >= BITS_FOLD_WIDE) break;
+  }
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return lg[a] > lg[b]; });
+  P.set_off = A.size();
+  size_t pair = 0;
+  for (uint32_t i : order) {
+    const MultiSet& m = sets[i];
+    A.push_back((int32_t)m.first_part);
+    A.push_back((int32_t)m.n_parts);
+    A.push_back(m.out);
+    A.push_back(lg[i]);
+    A.push_back((int32_t)pair);
+    pair += (size_t)1 << lg[i];
+  }
+  P.n_pairs = pair;
+  P.part_off = A.size();
+  for (const MultiPart& q : parts) {
+    A.push_back((int32_t)q.committee);
+    A.push_back((int32_t)q.word_off);
+    A.push_back((int32_t)q.n_bits);
+    A.push_back(bits_complement(q.n_bits, q.p) ? 1 : 0);
+  }
   P.pair_off = A.size();
   for (size_t e = 0; e < order.size(); e++) A.insert(A.end(), (size_t)1 << lg[order[e]], (int32_t)e);
   return P;

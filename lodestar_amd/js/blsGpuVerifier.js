@@ -148,6 +148,11 @@ function serializeSet(set) {
     checkBitsSet(set);
     return {committee: set.committee, bits: set.bits, bitLen: set.bitLen, message: set.signingRoot, signature: set.signature};
   }
+  // ... or by a list of committees plus one bitfield over their concatenation (an Electra aggregate)
+  if (set.committees !== undefined) {
+    checkBitsMultiSet(set);
+    return {committees: set.committees, bits: set.bits, bitLen: set.bitLen, message: set.signingRoot, signature: set.signature};
+  }
   // signers named by validator index into the device pubkey table (SURVEY 8f(1)):
   // loadPubkeys() mirrors index2pubkey; the set carries its attesting indices
   if (set.pubkeyIndices !== undefined) {
@@ -218,6 +223,8 @@ function verifyDirect(addon, ctx, sets, seed, validate = false, onAggregates = n
 const MAX_COMMITTEE_ID = 1 << 20;
 const MAX_COMMITTEE_LEN = 131072;
 const PK_BITS = 8; // LSG_PK_BITS
+const PK_BITS_MULTI = 12; // LSG_PK_BITS_MULTI
+const MAX_SET_COMMITTEES = 64; // LSG_MAX_SET_COMMITTEES
 const NO_GROUP = 0xffffffff; // LSG_NO_GROUP
 
 /** A set that names its signers as {committee, bits, bitLen}: committee is an id given to
@@ -229,6 +236,26 @@ function checkBitsSet(set) {
   }
   if (!Number.isInteger(set.bitLen) || set.bitLen < 0 || set.bitLen > MAX_COMMITTEE_LEN) {
     throw Error("bitLen must be the committee's length");
+  }
+  if (!(set.bits instanceof Uint8Array) || set.bits.length < ((set.bitLen + 7) >> 3)) {
+    throw Error("bits must be a Uint8Array of at least ceil(bitLen / 8) bytes");
+  }
+}
+
+/** A set that names its signers as {committees, bits, bitLen} (EIP-7549: an aggregate spanning
+ * committees): committees lists ids given to loadCommittees -- at most 64, in the order their
+ * members appear in the bitfield; they may repeat -- bits is one participation bitfield over the
+ * concatenation of the listed committees (SSZ order, no delimiter bit), bitLen the sum of their
+ * lengths. */
+function checkBitsMultiSet(set) {
+  const ids = set.committees;
+  if (!(ids instanceof Uint32Array) && !Array.isArray(ids)) throw Error("committees must be an array of committee ids");
+  if (ids.length > MAX_SET_COMMITTEES) throw Error("a set lists at most 64 committees");
+  for (let c = 0; c < ids.length; c++) {
+    if (!Number.isInteger(ids[c]) || ids[c] < 0 || ids[c] >= MAX_COMMITTEE_ID) throw Error("committee must be an id below 2^20");
+  }
+  if (!Number.isInteger(set.bitLen) || set.bitLen < 0 || set.bitLen > MAX_SET_COMMITTEES * MAX_COMMITTEE_LEN) {
+    throw Error("bitLen must be the sum of the committees' lengths");
   }
   if (!(set.bits instanceof Uint8Array) || set.bits.length < ((set.bitLen + 7) >> 3)) {
     throw Error("bits must be a Uint8Array of at least ceil(bitLen / 8) bytes");
@@ -298,7 +325,7 @@ function msgCacheStatsSync(addon, ctx) {
 function getAggregatedPubkeysCount(sets) {
   let n = 0;
   for (const set of sets) {
-    if (set.committee !== undefined) n += set.bits instanceof Uint8Array ? countBits(set.bits, set.bitLen) : 0;
+    if (set.committee !== undefined || set.committees !== undefined) n += set.bits instanceof Uint8Array ? countBits(set.bits, set.bitLen) : 0;
     else if (set.pubkeyIndices !== undefined) n += set.pubkeyIndices.length;
     else if (set.type === SignatureSetType.aggregate) n += set.pubkeys.length;
   }
@@ -361,6 +388,10 @@ function checkSet(set) {
   if (set.signingObject !== undefined) checkMsgObject(set);
   if (set.committee !== undefined) {
     checkBitsSet(set);
+    return;
+  }
+  if (set.committees !== undefined) {
+    checkBitsMultiSet(set);
     return;
   }
   if (set.pubkeyIndices === undefined && set.type !== SignatureSetType.single && set.type !== SignatureSetType.aggregate) {
@@ -578,7 +609,9 @@ function packJobs(ranges, nSigs, into, minSigs = 0, grouped = false) {
           const set = sets[si];
           const d = SET_DESC_WORDS * k;
           const pk1 =
-            set.committee === undefined && set.pubkeyIndices === undefined && set.type === SignatureSetType.single ? set.pubkey : null;
+            set.committee === undefined && set.committees === undefined && set.pubkeyIndices === undefined && set.type === SignatureSetType.single
+              ? set.pubkey
+              : null;
           // the message: the signing root, or the signed object followed by its domain
           const dom = set.signingObject === undefined ? null : set.domain;
           if (dom !== null) checkMsgObject(set);
@@ -587,7 +620,7 @@ function packJobs(ranges, nSigs, into, minSigs = 0, grouped = false) {
           const sig = set.signature;
           const msgBytes = dom === null ? root.length : root.length + 32;
           if (grouped) groupOf(set, k);
-          if (pk1 instanceof Uint8Array && pk1.length !== PK_BITS && off + pk1.length + msgBytes + sig.length <= cap) {
+          if (pk1 instanceof Uint8Array && pk1.length !== PK_BITS && pk1.length !== PK_BITS_MULTI && off + pk1.length + msgBytes + sig.length <= cap) {
             // the common shape (one raw key): three copies, no helper calls
             arena.set(pk1, off);
             sd[d] = off;
@@ -617,6 +650,16 @@ function packJobs(ranges, nSigs, into, minSigs = 0, grouped = false) {
             put(set.bits.subarray(0, (set.bitLen + 7) >> 3));
             sd[d + 1] = PK_BITS;
             sd[d + 2] = set.bitLen;
+          } else if (set.committees !== undefined) {
+            // the count, the committee ids (host byte order), then the first ceil(bitLen / 8) bytes
+            checkBitsMultiSet(set);
+            const head = new Uint32Array(1 + set.committees.length);
+            head[0] = set.committees.length;
+            head.set(set.committees, 1);
+            sd[d] = put(new Uint8Array(head.buffer));
+            put(set.bits.subarray(0, (set.bitLen + 7) >> 3));
+            sd[d + 1] = PK_BITS_MULTI;
+            sd[d + 2] = set.bitLen;
           } else if (set.pubkeyIndices !== undefined) {
             const ix = set.pubkeyIndices instanceof Uint32Array ? set.pubkeyIndices : Uint32Array.from(set.pubkeyIndices);
             sd[d] = put(new Uint8Array(ix.buffer, ix.byteOffset, 4 * ix.length));
@@ -625,7 +668,8 @@ function packJobs(ranges, nSigs, into, minSigs = 0, grouped = false) {
           } else if (set.type === SignatureSetType.single) {
             const pk = pubkeyBytes(set.pubkey);
             sd[d] = put(pk);
-            sd[d + 1] = pk.length === PK_BITS ? 0 : pk.length; // (8 bytes: an unknown key length, not LSG_PK_BITS)
+            // (8 or 12 bytes: an unknown key length, not LSG_PK_BITS / LSG_PK_BITS_MULTI)
+            sd[d + 1] = pk.length === PK_BITS || pk.length === PK_BITS_MULTI ? 0 : pk.length;
             sd[d + 2] = 1;
           } else if (set.type === SignatureSetType.aggregate) {
             const pks = set.pubkeys;
@@ -636,7 +680,7 @@ function packJobs(ranges, nSigs, into, minSigs = 0, grouped = false) {
               if (b.length !== len) throw Error("every pubkey of an aggregate set must have the same encoding");
               put(b);
             }
-            sd[d + 1] = len === PK_BITS ? 0 : len;
+            sd[d + 1] = len === PK_BITS || len === PK_BITS_MULTI ? 0 : len;
             sd[d + 2] = pks.length;
           } else {
             throw Error("Unknown signature set type");
@@ -829,7 +873,9 @@ class BlsGpuVerifier {
   /** Register committees on the device (SURVEY 8f(5); call where the node fills its shuffling
    * and sync-committee caches): committee firstId + c <- committees[c], validator indices in
    * committee order (rows loaded with loadPubkeys).  An aggregate set may then carry
-   * {committee, bits, bitLen} instead of pubkeys or pubkeyIndices.  Returns per-committee codes
+   * {committee, bits, bitLen} instead of pubkeys or pubkeyIndices, or -- an Electra aggregate
+   * spanning committees -- {committees, bits, bitLen}: up to 64 ids and one bitfield over the
+   * concatenation of those committees.  Returns per-committee codes
    * (0 = registered; 102: a member names an unloaded index; 101: an empty committee). */
   loadCommittees(firstId, committees) {
     return loadCommitteesSync(this.addon, this.ctx, firstId, committees);
@@ -908,14 +954,25 @@ class BlsGpuVerifier {
     return Promise.all(
       sets.map((s) =>
         this._queueBlsWork(o, [
-          {
-            type: SignatureSetType.single,
-            pubkey: s.publicKey,
-            signingRoot: message,
-            signature: s.signature,
-            aggregateKey: s.aggregateKey,
-            aggregateTag: s.aggregateTag,
-          },
+          s.committees !== undefined
+            ? {
+                // an aggregate spanning committees goes through as it is
+                committees: s.committees,
+                bits: s.bits,
+                bitLen: s.bitLen,
+                signingRoot: message,
+                signature: s.signature,
+                aggregateKey: s.aggregateKey,
+                aggregateTag: s.aggregateTag,
+              }
+            : {
+                type: SignatureSetType.single,
+                pubkey: s.publicKey,
+                signingRoot: message,
+                signature: s.signature,
+                aggregateKey: s.aggregateKey,
+                aggregateTag: s.aggregateTag,
+              },
         ]).catch(() => false)
       )
     );

@@ -43,7 +43,8 @@
  *   pubkeyValidate(ctx, pks: n x pkLen B, pkLen) -> Int32Array         lsg_pubkey_validate
  *   committeesSet(ctx, firstId, indices: Uint32Array, offsets: Uint32Array) -> Int32Array
  *   committeesClear(ctx, firstId, n)                                   lsg_committees_set / _clear
- *       (a set descriptor may then have pk_len 8 = LSG_PK_BITS: committee id + bits, n_pks bits)
+ *       (a set descriptor may then have pk_len 8 = LSG_PK_BITS: committee id + bits, n_pks bits;
+ *       or pk_len 12 = LSG_PK_BITS_MULTI: count k, k committee ids, bits over their concatenation)
  *   objectSigningRoots(ctx, objs: n x objLen B, objLen, domain: 32 B | n x 32 B) -> Uint8Array(n x 32)
  *                                                                      lsg_object_signing_roots
  *   msgCacheSet(ctx, rows)                                             lsg_msg_cache_set
@@ -222,8 +223,9 @@ static int view_sets(napi_env env, napi_value arr, set_view* out) {
       napi_value k0;
       napi_get_element(env, pk, 0, &k0);
       if (get_bytes(env, k0, &d, &len)) goto bad;
-      /* (an 8-byte "key" is an unknown key length, never a committee + bits set: LSG_PK_BITS) */
-      q->pk_len = len == LSG_PK_BITS ? 0 : (uint32_t)len;
+      /* (an 8- or 12-byte "key" is an unknown key length, never a committee + bits set:
+       * LSG_PK_BITS, LSG_PK_BITS_MULTI) */
+      q->pk_len = len == LSG_PK_BITS || len == LSG_PK_BITS_MULTI ? 0 : (uint32_t)len;
       if (npk == 1) {
         q->pks = d;
       } else {
@@ -411,7 +413,19 @@ static int build_jobs(pkg_req* r, lsg_set** sets_out, lsg_job** jobs_out) {
     const uint32_t* d = r->sdesc + 7 * (size_t)i;
     lsg_set* q = &sets[i];
     /* a committee + bits set (LSG_PK_BITS): the committee id, then ceil(n_pks / 8) bytes of bits */
-    const uint64_t pk_bytes = d[1] == LSG_PK_BITS ? 4 + (((uint64_t)d[2] + 7) >> 3) : (uint64_t)d[1] * d[2];
+    uint64_t pk_bytes = d[1] == LSG_PK_BITS ? 4 + (((uint64_t)d[2] + 7) >> 3) : (uint64_t)d[1] * d[2];
+    /* a multi-committee set (LSG_PK_BITS_MULTI): the count k, k committee ids, then the bits -- its
+     * size comes from the blob's own leading count, which must itself lie inside the arena */
+    if (d[1] == LSG_PK_BITS_MULTI) {
+      uint32_t k = 0;
+      if ((uint64_t)d[0] + 4 > L) {
+        free(sets);
+        free(jobs);
+        return LSG_ERR_INVALID_ARG;
+      }
+      memcpy(&k, r->arena + d[0], 4);
+      pk_bytes = 4 + 4 * (uint64_t)k + (((uint64_t)d[2] + 7) >> 3);
+    }
     /* the length word of a message may carry LSG_MSG_OBJECT: its bytes are the masked length */
     const uint64_t msg_bytes = d[4] & ~LSG_MSG_OBJECT;
     if ((uint64_t)d[0] + pk_bytes > L || (uint64_t)d[3] + msg_bytes > L || (uint64_t)d[5] + d[6] > L) {
