@@ -577,6 +577,13 @@ int lsg_check_sums(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
  * (Y_6 .. Y_8), in the pair layout (Y_9 .. Y_11). */
 int lsg_check_fp2_lanes(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
 int lsg_check_g2_lanes(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+/* lsg_check_mf_lanes: the pieces of the layout that only the fused Miller kernel uses; 12 elements
+ * per item in (A .. F as for lsg_check_fp2_lanes, D .. F unused), 24 out, every lane-layout result
+ * converted back and followed by the pair form's: Y_0 = A B.c0 (Fp2 x Fp), Y_1 its pair-form twin;
+ * Y_2, Y_3 = xi A carried; Y_4, Y_5 = A + xi (B - C) with one carry; Y_6 .. Y_8 = v (A, B, C) =
+ * (xi C, A, B); Y_9 = 1, Y_10 = 0; elements 22, 23: B.c0 spread over both lanes as they hold it
+ * (word k of lane h at 2 k + h). */
+int lsg_check_mf_lanes(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
 /* Parity hooks of the layer between the products and the accept / reject rules (tests only;
  * none is on the verification path).  Elements travel in the pair layout above: 14 words, limb
  * L at word 2 (L mod 7) + L / 7.  Each returns LSG_ERR_INVALID_ARG for a null pointer with a

@@ -203,7 +203,7 @@ EXPORTS = [
     "lsg_final_submit_groups", "lsg_final_wait_groups", "lsg_aggregate_signatures",
     "lsg_signing_roots", "lsg_attestation_signing_roots", "lsg_jobs_partial_device", "lsg_final_submit_device",
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
-    "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums", "lsg_check_fp2_lanes", "lsg_check_g2_lanes",
+    "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums", "lsg_check_fp2_lanes", "lsg_check_g2_lanes", "lsg_check_mf_lanes",
     "lsg_check_canon", "lsg_check_fp2_roots", "lsg_check_batch_inv", "lsg_check_map_uniform",
     "lsg_check_batch_partial_rnd",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
@@ -288,6 +288,7 @@ def load_library(path=LIB_PATH):
         lib.lsg_check_sums.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_fp2_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_g2_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_mf_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_canon.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_char_p, ctypes.c_char_p]
         lib.lsg_check_fp2_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_batch_inv.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
@@ -902,6 +903,10 @@ class Context:
     def check_g2_lanes(self, words):
         """lsg_check_g2_lanes: `words` = 12 x 14 u32 per item; returns 24 x 14 u32 per item (raw)."""
         return self._check_lanes("lsg_check_g2_lanes", words)
+
+    def check_mf_lanes(self, words):
+        """lsg_check_mf_lanes: `words` = 12 x 14 u32 per item; returns 24 x 14 u32 per item (raw)."""
+        return self._check_lanes("lsg_check_mf_lanes", words)
 
     def check_canon(self, words, strings=()):
         """lsg_check_canon: `words` = 14 u32 per raw element, `strings` = 48-byte strings.  Returns

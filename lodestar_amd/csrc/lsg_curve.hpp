@@ -29,6 +29,12 @@ template <int K> LSG_INL fp2_t fmulk(const fp2_t& a) { return fp2_mulk<K>(a); }
 template <class F> LSG_INL F fsub2(const F& a, const F& b, const F& c) { return (fsum(a) - b - c).carry(); }
 LSG_INL fp_t fmul_b3(const fp_t& a) { return fp_mul12(a); }
 LSG_INL fp2_t fmul_b3(const fp2_t& a) { return fp2_mul_b3(a); }
+// the product by xi = 1 + u as a lazy sum and carried, the product by an Fp element
+template <int P0, int N0, int P1, int N1>
+LSG_INL auto fsum_mul_xi(const fp2s_t<P0, N0, P1, N1>& a) { return fp2s_mul_xi(a); }
+LSG_INL fp2s_t<1, 1, 2, 0> fsum_mul_xi(const fp2_t& a) { return fp2s_mul_xi(a); }
+LSG_INL fp2_t fmul_xi(const fp2_t& a) { return fp2_mul_xi(a); }
+LSG_INL fp2_t fmul_fp(const fp2_t& a, const fp_t& k) { return fp2_mul_fp(a, k); }
 LSG_INL bool fis_zero(const fp_t& a) { return fp_is_zero(a); }
 LSG_INL bool fis_zero(const fp2_t& a) { return fp2_is_zero(a); }
 LSG_INL bool feq(const fp_t& a, const fp_t& b) { return fp_eq(a, b); }

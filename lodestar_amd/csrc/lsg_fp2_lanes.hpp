@@ -4,10 +4,13 @@
 //
 // An Fp2 element still takes one lane pair, but the even lane holds all 14 limbs of c0 and the
 // odd lane all 14 limbs of c1 (fp2_t, lsg_tower.hpp, splits each component 7 + 7 over the pair).
-// 14 words per lane either way.  Each lane then runs a whole 14-column CIOS pass of its own:
+// 14 words per lane either way; k_miller_fused (lsg_k_miller.hip) runs all four of its phases in
+// this layout.  Each lane then runs a whole 14-column CIOS pass of its own:
 //   product  every lane computes REDC(P b_own + Q b_other) with P = a0 on both lanes and
 //            Q = -a1 on the even lane, a1 on the odd one: a0 b0 - a1 b1 | a0 b1 + a1 b0
 //   square   the even lane computes REDC((a0 + a1)(a0 - a1)), the odd one REDC(a1 (2 a0))
+//   by Fp    every lane computes REDC(a_own k), k's 14 limbs held by both lanes (fpv_t): the
+//            line of the fused Miller kernel evaluated at P (lsg_k_miller.hip)
 // so the per-step bookkeeping of the pair form (the m product and its broadcast, the 64-bit
 // shift, the hand-down of lane 1's low limb, the b broadcasts) is paid once per 42 (28) mads
 // instead of once per 14, the hand-down is gone, and b_own is a plain register read; b_other
@@ -23,6 +26,8 @@
 //   product: 3 terms (P b_own, Q b_other, m p), each below (2^29 + 8)^2 < 2^58.0001
 //   square:  2 terms, the operand product below (2^30 + 16)(2^29 + 16) < 2^59.1 (the operands
 //            a0 + a1, a0 - a1, 2 a0 are uncarried two-term sums) and m p below 2^58
+//   by Fp:   2 terms, a_own k and m p, each below (2^29 + 8)^2 < 2^58.0001 (both operands are
+//            carried values): inside the product's bound, on the square's pass (lanes_mul_pass)
 // so after 7 steps |t| < 21 * 2^58.0001 < 2^62.4 (square: 7 (2^59.1 + 2^58) < 2^62.4).  The
 // accumulators are carried once after step 7 (value-preserving: limbs back in [0, 2^29), the
 // top one below 2^34 in magnitude) and the last 7 steps add the same again: |t| < 2^63
@@ -111,6 +116,7 @@ LSG_PFN void lanes_mul_pass(uint32_t* r, const uint32_t* V, const uint32_t* s) {
 }
 // The operands of a lane from its own word and its partner's (odd: the lane holds c1).
 //   product: P = a0, Q = -a1 | a1        square: V = a0 + a1 | a1, s = a0 - a1 | 2 a0
+//   by xi = 1 + u: a0 - a1 | a1 + a0 (a limb of the lazy sum, no pass)
 LSG_PFN void lanes_mul_operand(uint32_t& P, uint32_t& Q, uint32_t own, uint32_t partner, bool odd) {
   P = odd ? partner : own;
   Q = odd ? own : 0u - partner;
@@ -119,6 +125,7 @@ LSG_PFN void lanes_sqr_operand(uint32_t& V, uint32_t& s, uint32_t own, uint32_t 
   V = odd ? own : own + partner;
   s = odd ? partner + partner : own - partner;
 }
+LSG_PFN uint32_t lanes_xi_operand(uint32_t own, uint32_t partner, bool odd) { return odd ? own + partner : own - partner; }
 
 #if LSG_PAIR_G == 2 && !defined(LSG_NO_FP2_LANES)
 #define LSG_FP2_LANES 1
@@ -187,6 +194,20 @@ LSG_PLEAF fp2v_t lanes_fp2_sqr_v(LSG_LANES_PARAMS(va)) {
   return r;
 }
 
+// An Fp element with all 14 limbs on both lanes of the pair: the Fp factor of the Fp2 x Fp leaf
+struct fpv_t {
+  uint32_t l[LSG_VL];
+};
+// a k = (a0 k) + (a1 k) u: one pass per lane on its own component, no cross-lane step
+LSG_PLEAF fp2v_t lanes_fp2_mul_fp_v(LSG_LANES_PARAMS(va), LSG_LANES_PARAMS(vk)) {
+  fp2v_t a = LSG_LANES_UNPACK(va), k = LSG_LANES_UNPACK(vk);
+#pragma unroll
+  for (int j = 0; j < LSG_VL; j++) LSG_LANES_HIDE(a.l[j]);  // (opaque operands: see lanes_fp2_mul_v)
+  fp2v_t r;
+  lanes_mul_pass(r.l, a.l, k.l);
+  return r;
+}
+
 // ------------------------------------------------------------------ conversions (DPP moves and selects)
 // fp2_t: lane h holds limbs 7h..7h+6 of both components.  Each lane sends the 7 words its
 // partner lacks (even: its half of c1, odd: its half of c0) in one swap per word.
@@ -209,6 +230,18 @@ LSG_PFN fp2_t fp2v_to_pair(const fp2v_t& a) {
     const uint32_t s = lanes_swap(odd ? a.l[k] : a.l[LSG_PL + k]);
     r.c0.l[k] = odd ? s : a.l[k];
     r.c1.l[k] = odd ? a.l[LSG_PL + k] : s;
+  }
+  return r;
+}
+// fp_t: lane h holds limbs 7h..7h+6.  Both lanes get all 14: 7 swaps and 14 selects.
+LSG_PFN fpv_t fpv_from_pair(const fp_t& a) {
+  const bool odd = lanes_odd();
+  fpv_t r;
+#pragma unroll
+  for (int k = 0; k < LSG_PL; k++) {
+    const uint32_t s = lanes_swap(a.l[k]);
+    r.l[k] = odd ? s : a.l[k];
+    r.l[LSG_PL + k] = odd ? a.l[k] : s;
   }
   return r;
 }
@@ -298,6 +331,20 @@ LSG_PFN fp2vs_t<K * P, K * N> fsum_mulk(const fp2vs_t<P, N>& a) {
   return r;
 }
 
+// (1 + u) a = (c0 - c1) + (c0 + c1) u as a lazy sum: the even lane takes own - partner, the odd
+// lane own + partner, one swap per limb.  The partner's sum has the same counts (P, N), so the
+// even lane's result has (P + N, P + N) and the odd lane's (2 P, 2 N): the type keeps the larger.
+constexpr int lanes_max(int a, int b) { return a > b ? a : b; }
+template <int P, int N>
+LSG_PFN fp2vs_t<lanes_max(P + N, 2 * P), lanes_max(P + N, 2 * N)> fsum_mul_xi(const fp2vs_t<P, N>& a) {
+  const bool odd = lanes_odd();
+  fp2vs_t<lanes_max(P + N, 2 * P), lanes_max(P + N, 2 * N)> r;
+#pragma unroll
+  for (int k = 0; k < LSG_VL; k++) r.l[k] = lanes_xi_operand(a.l[k], lanes_swap(a.l[k]), odd);
+  return r;
+}
+LSG_PFN fp2vs_t<2, 1> fsum_mul_xi(const fp2v_t& a) { return fsum_mul_xi(fsum(a)); }
+
 // ------------------------------------------------------------------ the generic names (lsg_curve.hpp)
 LSG_PFN fp2v_t fmul(const fp2v_t& a, const fp2v_t& b) { return lanes_fp2_mul_v(LSG_LANES_ARGS(a), LSG_LANES_ARGS(b)); }
 LSG_PFN fp2v_t fsqr(const fp2v_t& a) { return lanes_fp2_sqr_v(LSG_LANES_ARGS(a)); }
@@ -309,15 +356,14 @@ LSG_PFN fp2v_t fmulk(const fp2v_t& a) { return fsum(a).template carry_mul<K>(); 
 // 12 (1 + u) a = 12 ((c0 - c1) + (c0 + c1) u): the one linear operation that crosses the pair.
 // The even lane's a - partner is a sum of counts (1, 1), the odd lane's a + partner (2, 0):
 // both inside (2, 1), carried, then 12 times a carried value in one pass (as fp2_mul_b3).
-LSG_PFN fp2v_t fmul_b3(const fp2v_t& a) {
-  const bool odd = lanes_odd();
-  fp2vs_t<2, 1> x;
+LSG_PFN fp2v_t fmul_b3(const fp2v_t& a) { return fmulk<12>(fsum_mul_xi(a).carry()); }
+LSG_PFN fp2v_t fmul_xi(const fp2v_t& a) { return fsum_mul_xi(a).carry(); }
+// (k goes through an fp2v_t to share the argument packing: the copy is gone after inlining)
+LSG_PFN fp2v_t fmul_fp(const fp2v_t& a, const fpv_t& k) {
+  fp2v_t kv;
 #pragma unroll
-  for (int k = 0; k < LSG_VL; k++) {
-    const uint32_t o = lanes_swap(a.l[k]);
-    x.l[k] = odd ? a.l[k] + o : a.l[k] - o;
-  }
-  return fmulk<12>(x.carry());
+  for (int j = 0; j < LSG_VL; j++) kv.l[j] = k.l[j];
+  return lanes_fp2_mul_fp_v(LSG_LANES_ARGS(a), LSG_LANES_ARGS(kv));
 }
 LSG_PFN fp2v_t fselect(bool c, const fp2v_t& a, const fp2v_t& b) {  // c: the same on both lanes
   fp2v_t r;
@@ -327,4 +373,24 @@ LSG_PFN fp2v_t fselect(bool c, const fp2v_t& a, const fp2v_t& b) {  // c: the sa
 }
 // (a handful per item: through the pair form's canonical test)
 LSG_PFN bool fis_zero(const fp2v_t& a) { return fp2_is_zero(fp2v_to_pair(a)); }
+
+// ------------------------------------------------------------------ Fp6 = Fp2[v] / (v^3 - xi)
+struct fp6v_t {
+  fp2v_t c0, c1, c2;
+};
+LSG_PFN fp6v_t fp6_make(const fp2v_t& a, const fp2v_t& b, const fp2v_t& c) { return fp6v_t{a, b, c}; }
+LSG_PFN fp6v_t fp6_add(const fp6v_t& a, const fp6v_t& b) {
+  return fp6v_t{fadd(a.c0, b.c0), fadd(a.c1, b.c1), fadd(a.c2, b.c2)};
+}
+LSG_PFN fp6v_t fp6_mul_v(const fp6v_t& a) { return fp6v_t{fmul_xi(a.c2), a.c0, a.c1}; }
+// the output coefficients of the Karatsuba Fp6 product as sums (lsg_tower.hpp fp6_kar_s0/1/2)
+LSG_PFN fp2vs_t<3, 1> fp6_kar_s0(const fp2v_t& v0, const fp2v_t& v1, const fp2v_t& v2, const fp2v_t& m0) {
+  return fsum(v0) + fsum_mul_xi((fsum(m0) - v1 - v2).carry());
+}
+LSG_PFN fp2vs_t<3, 3> fp6_kar_s1(const fp2v_t& v0, const fp2v_t& v1, const fp2v_t& v2, const fp2v_t& m1) {
+  return (fsum(m1) - v0 - v1) + fsum_mul_xi(v2);
+}
+LSG_PFN fp2vs_t<2, 2> fp6_kar_s2(const fp2v_t& v0, const fp2v_t& v1, const fp2v_t& v2, const fp2v_t& m2) {
+  return (fsum(m2) - v0 - v2) + v1;
+}
 #endif  // LSG_PAIR_G == 2 && !LSG_NO_FP2_LANES

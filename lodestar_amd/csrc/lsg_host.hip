@@ -635,6 +635,9 @@ int slot_ready(Dev* d, Slot* s, int index) {
 // The fused Miller kernel (k_miller_fused: lines in LDS, four waves per item of four pairs) is
 // the default; LSG_MILLER_FUSED=0 selects the split pair k_miller_lines / k_miller_accum<K>.
 bool miller_fused() { return lsg_ab_long("LSG_MILLER_FUSED", 1) != 0; }
+// k_miller_fused runs with one Fp2 component per lane (lsg_fp2_lanes.hpp); LSG_MF_LANES=0 (A/B
+// build): its pair-form twin k_miller_fused_pair
+static bool mf_lanes_on() { return lsg_ab_long("LSG_MF_LANES", 1) != 0; }
 
 size_t slp_items_max();
 int miller_k_for(size_t n_sets) {
@@ -1375,9 +1378,14 @@ int launch_accum(Slot* s, size_t n_items, size_t item_off, uint32_t* fall, bool 
     return LSG_OK;
   }
   if (miller_fused()) {
-    KL(s, "k_miller_fused", lsgk::miller_fused(S_(s), ni, items, items + ni, P_<uint32_t>(s->d_P), P_<uint8_t>(s->d_pinf),
-                                              P_<uint8_t>(s->d_hinf), P_<int32_t>(s->d_seterr), P_<uint32_t>(s->d_H),
-                                              fall));
+    if (mf_lanes_on())
+      KL(s, "k_miller_fused", lsgk::miller_fused(S_(s), ni, items, items + ni, P_<uint32_t>(s->d_P), P_<uint8_t>(s->d_pinf),
+                                                P_<uint8_t>(s->d_hinf), P_<int32_t>(s->d_seterr), P_<uint32_t>(s->d_H),
+                                                fall));
+    else
+      KL(s, "k_miller_fused_pair",
+         lsgk::miller_fused(S_(s), ni, items, items + ni, P_<uint32_t>(s->d_P), P_<uint8_t>(s->d_pinf),
+                            P_<uint8_t>(s->d_hinf), P_<int32_t>(s->d_seterr), P_<uint32_t>(s->d_H), fall, true));
     return LSG_OK;
   }
   KL(s, "k_miller_accum",
@@ -4232,8 +4240,9 @@ int lsg_check_sums(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
   return LSG_OK;
 }
 
-// the component-per-lane Fp2 hooks (k_check_fp2_lanes, k_check_g2_lanes): EIN elements per item in, EOUT out
-static int check_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out, bool g2) {
+// the component-per-lane Fp2 hooks (k_check_fp2_lanes, k_check_g2_lanes, k_check_mf_lanes): EIN elements per
+// item in, EOUT out
+static int check_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out, bool g2, bool mf = false) {
   const size_t EIN = g2 ? lsgk::CHECK_G2L_IN : lsgk::CHECK_LANES_IN, EOUT = g2 ? lsgk::CHECK_G2L_OUT : lsgk::CHECK_LANES_OUT;
   if (!c || (n && (!in || !out)) || n > 0x7fffffffull / (4 * W_FP * EOUT)) return LSG_ERR_INVALID_ARG;
   LSG_ENTER(c);
@@ -4245,6 +4254,8 @@ static int check_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out, 
   LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, in, 4 * EIN * W_FP * n, hipMemcpyHostToDevice, s->st[0]));
   if (g2)
     KL(s, "k_check_g2_lanes", lsgk::check_g2_lanes(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  else if (mf)
+    KL(s, "k_check_mf_lanes", lsgk::check_mf_lanes(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
   else
     KL(s, "k_check_fp2_lanes", lsgk::check_fp2_lanes(S_(s), (int)n, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
   LSG_HIP(s, hipMemcpyAsync(out, s->d_Fb.p, 4 * EOUT * W_FP * n, hipMemcpyDeviceToHost, s->st[0]));
@@ -4253,6 +4264,9 @@ static int check_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out, 
 }
 int lsg_check_fp2_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_lanes(c, in, n, out, false); }
 int lsg_check_g2_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_lanes(c, in, n, out, true); }
+int lsg_check_mf_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
+  return check_lanes(c, in, n, out, false, true);
+}
 
 // the field-edge hooks (k_check_canon, k_check_from_bytes, k_check_fp2_roots, batch_inv, launch_hash)
 int lsg_check_canon(lsg_ctx* c, const uint32_t* in, size_t n, const uint8_t* bytes48, size_t nb, uint32_t* out,

@@ -135,7 +135,65 @@ LSG_DEVI void mf_put2(uint32_t* lds, int c, const fp2_t& v) {
   mf_put(lds, c, v.c0);
   mf_put(lds, c + 1, v.c1);
 }
-LSG_DEVI fp2_t mf_get2(uint32_t* lds, int c) { return fp2_t(mf_get(lds, c), mf_get(lds, c + 1)); }
+// The phases are templates over the layout F of an Fp2 value in registers: fp2v_t (one
+// component per lane, lsg_fp2_lanes.hpp: k_miller_fused) or fp2_t (k_miller_fused_pair).  Both
+// keep a value in components c and c + 1 of 7 words per lane; a lane's 14 fp2v_t words are
+// l[0..6] in component c and l[7..13] in c + 1.
+template <class F>
+LSG_DEVI F mf_get2(uint32_t* lds, int c);
+template <>
+LSG_DEVI fp2_t mf_get2<fp2_t>(uint32_t* lds, int c) {
+  return fp2_t(mf_get(lds, c), mf_get(lds, c + 1));
+}
+// the Fp coordinates of P, read in the pair form, as the factor of fmul_fp; and Fp component c
+// of f in the pair form for the final store
+template <class F>
+struct mf_layout;
+template <>
+struct mf_layout<fp2_t> {
+  static LSG_DEVI const fp_t& fp_in(const fp_t& a) { return a; }
+  static LSG_DEVI fp_t fp_out(uint32_t* lds, int c) { return mf_get(lds, c); }
+  static LSG_DEVI fp2_t one() { return fp2_one(); }
+};
+#ifdef LSG_FP2_LANES
+LSG_DEVI void mf_put2(uint32_t* lds, int c, const fp2v_t& v) {
+  uint32_t* p = mf_slot(lds, c);
+#pragma unroll
+  for (int k = 0; k < LSG_VL; k++) p[k * 64] = v.l[k];
+}
+template <>
+LSG_DEVI fp2v_t mf_get2<fp2v_t>(uint32_t* lds, int c) {
+  const uint32_t* p = mf_slot(lds, c);
+  fp2v_t v;
+#pragma unroll
+  for (int k = 0; k < LSG_VL; k++) v.l[k] = p[k * 64];
+  return v;
+}
+template <>
+struct mf_layout<fp2v_t> {
+  static LSG_DEVI fpv_t fp_in(const fp_t& a) { return fpv_from_pair(a); }
+  // 1 for the identity line, its lane selects made anew at each use: as a value of the whole
+  // kernel (the compiler merges it with the initial Z and f) its limbs sat in scratch
+  static LSG_DEVI fp2v_t one() {
+    uint32_t odd = pair_h();
+    asm volatile("" : "+v"(odd));
+    fp2v_t r;
+#pragma unroll
+    for (int k = 0; k < LSG_VL; k++) r.l[k] = odd ? 0u : fpc_t(FP_ONE).l[k];
+    return r;
+  }
+  // limbs 7h..7h+6 of Fp2 component c & 1 of the value in components c & ~1, c | 1: that
+  // component's lane (even: c0, odd: c1) keeps them in component (c & ~1) + h.  What
+  // fp2v_to_pair would move between registers is read from the partner's slot instead.
+  static LSG_DEVI fp_t fp_out(uint32_t* lds, int c) {
+    const uint32_t* p = lds + (size_t)((c & ~1) + (int)pair_h()) * 7 * 64 + ((threadIdx.x & 62) | (c & 1));
+    fp_t v;
+#pragma unroll
+    for (int k = 0; k < LSG_PL; k++) v.l[k] = p[k * 64];
+    return v;
+  }
+};
+#endif
 // Fp2 coefficient j (0..5: c0.c0, c0.c1, c0.c2, c1.c0, c1.c1, c1.c2) of f, product p, line k
 #define MF_FC(j) (MF_F + 2 * (j))
 #define MF_LC(k, j) (MF_L + 6 * (k) + 2 * (j))
@@ -143,38 +201,33 @@ LSG_DEVI fp2_t mf_get2(uint32_t* lds, int c) { return fp2_t(mf_get(lds, c), mf_g
 
 // f <- f^2 (S phase).  V0..5: t = a b (v0, v1, v2, m0, m1, m2 of the Karatsuba Fp6 product),
 // V6..11: u = (a + b)(a + v b).
+template <class F>
 LSG_DEVI void mf_sqr(uint32_t* lds, int w) {
   {
-    fp6_t x, y;
-    const fp6_t a = fp6_make(mf_get2(lds, MF_FC(0)), mf_get2(lds, MF_FC(1)), mf_get2(lds, MF_FC(2)));
-    const fp6_t b = fp6_make(mf_get2(lds, MF_FC(3)), mf_get2(lds, MF_FC(4)), mf_get2(lds, MF_FC(5)));
-    if (w < 2) {
-      x = a;
-      y = b;
-    } else {
+    const auto a = fp6_make(mf_get2<F>(lds, MF_FC(0)), mf_get2<F>(lds, MF_FC(1)), mf_get2<F>(lds, MF_FC(2)));
+    const auto b = fp6_make(mf_get2<F>(lds, MF_FC(3)), mf_get2<F>(lds, MF_FC(4)), mf_get2<F>(lds, MF_FC(5)));
+    auto x = a, y = b;
+    if (w >= 2) {
       x = fp6_add(a, b);
       y = fp6_add(a, fp6_mul_v(b));
     }
-    fp2_t p0, p1, p2;
-    if ((w & 1) == 0) {  // v0, v1, v2
-      p0 = fp2_mul(x.c0, y.c0);
-      p1 = fp2_mul(x.c1, y.c1);
-      p2 = fp2_mul(x.c2, y.c2);
-    } else {  // m0 = (x1 + x2)(y1 + y2), m1 = (x0 + x1)(y0 + y1), m2 = (x0 + x2)(y0 + y2)
-      p0 = fp2_mul(fp2_add(x.c1, x.c2), fp2_add(y.c1, y.c2));
-      p1 = fp2_mul(fp2_add(x.c0, x.c1), fp2_add(y.c0, y.c1));
-      p2 = fp2_mul(fp2_add(x.c0, x.c2), fp2_add(y.c0, y.c2));
+    // odd waves: m0 = (x1 + x2)(y1 + y2), m1 = (x0 + x1)(y0 + y1), m2 = (x0 + x2)(y0 + y2); even
+    // waves: v0, v1, v2.  The sums replace x and y before the first product, and each product
+    // goes to its slot at once: more values than these do not survive a leaf call in registers.
+    if (w & 1) {
+      x = fp6_make(fadd(x.c1, x.c2), fadd(x.c0, x.c1), fadd(x.c0, x.c2));
+      y = fp6_make(fadd(y.c1, y.c2), fadd(y.c0, y.c1), fadd(y.c0, y.c2));
     }
-    mf_put2(lds, MF_VC(3 * w), p0);
-    mf_put2(lds, MF_VC(3 * w + 1), p1);
-    mf_put2(lds, MF_VC(3 * w + 2), p2);
+    mf_put2(lds, MF_VC(3 * w), fmul(x.c0, y.c0));
+    mf_put2(lds, MF_VC(3 * w + 1), fmul(x.c1, y.c1));
+    mf_put2(lds, MF_VC(3 * w + 2), fmul(x.c2, y.c2));
   }
   __syncthreads();
   // Karatsuba Fp6 combination of t (V0..5): c0 = v0 + xi (m0 - v1 - v2), c1 = m1 - v0 - v1 + xi v2,
   // c2 = m2 - v0 - v2 + v1; likewise u (V6..11).  New f: c0 = u - t - v t, c1 = 2t.
   // The combinations are lazy sums regrouped for one carry per group (lsg_pairing.hpp mfc_sqr).
-  auto V = [&](int p) { return mf_get2(lds, MF_VC(p)); };
-  fp2_t o0, o1, o2;
+  auto V = [&](int p) { return mf_get2<F>(lds, MF_VC(p)); };
+  F o0, o1, o2;
   if (w == 0) {  // c1 = 2t
     o0 = mfc_sqr<0>(V);
     o1 = mfc_sqr<1>(V);
@@ -205,26 +258,27 @@ LSG_DEVI void mf_sqr(uint32_t* lds, int w) {
 //   P0 = l00 l00', P1 = l11 l11', P2 = l01 l01', P3 = (l00 + l01)(l00' + l01'),
 //   P4 = (l00 + l11)(l00' + l11'), P5 = (l01 + l11)(l01' + l11').
 // Waves 2pi and 2pi + 1 work on pair pi: three products each, then m0..m2 / m4, m5.
+template <class F>
 LSG_DEVI void mf_pair_lines(uint32_t* lds, int w) {
   const int pi = w >> 1, h = w & 1;
   {
-    const fp2_t a0 = mf_get2(lds, MF_LC(2 * pi, 0)), a1 = mf_get2(lds, MF_LC(2 * pi, 1)),
-                a2 = mf_get2(lds, MF_LC(2 * pi, 2));
-    const fp2_t b0 = mf_get2(lds, MF_LC(2 * pi + 1, 0)), b1 = mf_get2(lds, MF_LC(2 * pi + 1, 1)),
-                b2 = mf_get2(lds, MF_LC(2 * pi + 1, 2));
+    const F a0 = mf_get2<F>(lds, MF_LC(2 * pi, 0)), a1 = mf_get2<F>(lds, MF_LC(2 * pi, 1)),
+                a2 = mf_get2<F>(lds, MF_LC(2 * pi, 2));
+    const F b0 = mf_get2<F>(lds, MF_LC(2 * pi + 1, 0)), b1 = mf_get2<F>(lds, MF_LC(2 * pi + 1, 1)),
+                b2 = mf_get2<F>(lds, MF_LC(2 * pi + 1, 2));
     if (h == 0) {
-      mf_put2(lds, MF_VC(6 * pi), fp2_mul(a0, b0));
-      mf_put2(lds, MF_VC(6 * pi + 1), fp2_mul(a2, b2));
-      mf_put2(lds, MF_VC(6 * pi + 2), fp2_mul(a1, b1));
+      mf_put2(lds, MF_VC(6 * pi), fmul(a0, b0));
+      mf_put2(lds, MF_VC(6 * pi + 1), fmul(a2, b2));
+      mf_put2(lds, MF_VC(6 * pi + 2), fmul(a1, b1));
     } else {
-      mf_put2(lds, MF_VC(6 * pi + 3), fp2_mul(fp2_add(a0, a1), fp2_add(b0, b1)));
-      mf_put2(lds, MF_VC(6 * pi + 4), fp2_mul(fp2_add(a0, a2), fp2_add(b0, b2)));
-      mf_put2(lds, MF_VC(6 * pi + 5), fp2_mul(fp2_add(a1, a2), fp2_add(b1, b2)));
+      mf_put2(lds, MF_VC(6 * pi + 3), fmul(fadd(a0, a1), fadd(b0, b1)));
+      mf_put2(lds, MF_VC(6 * pi + 4), fmul(fadd(a0, a2), fadd(b0, b2)));
+      mf_put2(lds, MF_VC(6 * pi + 5), fmul(fadd(a1, a2), fadd(b1, b2)));
     }
   }
   __syncthreads();
   // the lines of pair pi were read before the barrier: their slots take M
-  auto V = [&](int p) { return mf_get2(lds, MF_VC(6 * pi + p)); };
+  auto V = [&](int p) { return mf_get2<F>(lds, MF_VC(6 * pi + p)); };
   if (h == 0) {
     mf_put2(lds, MF_LC(2 * pi, 0), mfc_pair<0>(V));
     mf_put2(lds, MF_LC(2 * pi, 1), mfc_pair<1>(V));
@@ -243,50 +297,51 @@ LSG_DEVI void mf_pair_lines(uint32_t* lds, int w) {
 //   V6 b0 m4   V7 b1 m5   V8 (b0+b1)(m4+m5)   V9 b2 m4   V10 b2 m5
 //   V11 s0 q0  V12 s1 q1  V13 s2 q2  V14 (s0+s1)(q0+q1)  V15 (s1+s2)(q1+q2)  V16 (s0+s2)(q0+q2)
 //   with s = a + b, q = (m0, m1 + m4, m2 + m5); split 5/4/4/4 over the waves.
+template <class F>
 LSG_DEVI void mf_mul_pair(uint32_t* lds, int w, int k) {
   {
-    const fp2_t m0 = mf_get2(lds, MF_LC(2 * k, 0)), m1 = mf_get2(lds, MF_LC(2 * k, 1)), m2 = mf_get2(lds, MF_LC(2 * k, 2));
+    const F m0 = mf_get2<F>(lds, MF_LC(2 * k, 0)), m1 = mf_get2<F>(lds, MF_LC(2 * k, 1)), m2 = mf_get2<F>(lds, MF_LC(2 * k, 2));
     if (w == 0) {
-      const fp2_t a0 = mf_get2(lds, MF_FC(0)), a1 = mf_get2(lds, MF_FC(1)), a2 = mf_get2(lds, MF_FC(2));
-      mf_put2(lds, MF_VC(0), fp2_mul(a0, m0));
-      mf_put2(lds, MF_VC(1), fp2_mul(a1, m1));
-      mf_put2(lds, MF_VC(2), fp2_mul(a2, m2));
-      mf_put2(lds, MF_VC(3), fp2_mul(fp2_add(a0, a1), fp2_add(m0, m1)));
-      mf_put2(lds, MF_VC(4), fp2_mul(fp2_add(a1, a2), fp2_add(m1, m2)));
+      const F a0 = mf_get2<F>(lds, MF_FC(0)), a1 = mf_get2<F>(lds, MF_FC(1)), a2 = mf_get2<F>(lds, MF_FC(2));
+      mf_put2(lds, MF_VC(0), fmul(a0, m0));
+      mf_put2(lds, MF_VC(1), fmul(a1, m1));
+      mf_put2(lds, MF_VC(2), fmul(a2, m2));
+      mf_put2(lds, MF_VC(3), fmul(fadd(a0, a1), fadd(m0, m1)));
+      mf_put2(lds, MF_VC(4), fmul(fadd(a1, a2), fadd(m1, m2)));
     } else if (w == 1) {
-      const fp2_t m4 = mf_get2(lds, MF_LC(2 * k + 1, 0)), m5 = mf_get2(lds, MF_LC(2 * k + 1, 1));
-      const fp2_t b0 = mf_get2(lds, MF_FC(3)), b1 = mf_get2(lds, MF_FC(4));
-      mf_put2(lds, MF_VC(5), fp2_mul(fp2_add(mf_get2(lds, MF_FC(0)), mf_get2(lds, MF_FC(2))), fp2_add(m0, m2)));
-      mf_put2(lds, MF_VC(6), fp2_mul(b0, m4));
-      mf_put2(lds, MF_VC(7), fp2_mul(b1, m5));
-      mf_put2(lds, MF_VC(8), fp2_mul(fp2_add(b0, b1), fp2_add(m4, m5)));
+      const F m4 = mf_get2<F>(lds, MF_LC(2 * k + 1, 0)), m5 = mf_get2<F>(lds, MF_LC(2 * k + 1, 1));
+      const F b0 = mf_get2<F>(lds, MF_FC(3)), b1 = mf_get2<F>(lds, MF_FC(4));
+      mf_put2(lds, MF_VC(5), fmul(fadd(mf_get2<F>(lds, MF_FC(0)), mf_get2<F>(lds, MF_FC(2))), fadd(m0, m2)));
+      mf_put2(lds, MF_VC(6), fmul(b0, m4));
+      mf_put2(lds, MF_VC(7), fmul(b1, m5));
+      mf_put2(lds, MF_VC(8), fmul(fadd(b0, b1), fadd(m4, m5)));
     } else if (w == 2) {
-      const fp2_t m4 = mf_get2(lds, MF_LC(2 * k + 1, 0)), m5 = mf_get2(lds, MF_LC(2 * k + 1, 1));
-      const fp2_t b2 = mf_get2(lds, MF_FC(5));
-      mf_put2(lds, MF_VC(9), fp2_mul(b2, m4));
-      mf_put2(lds, MF_VC(10), fp2_mul(b2, m5));
-      const fp2_t s0 = fp2_add(mf_get2(lds, MF_FC(0)), mf_get2(lds, MF_FC(3)));
-      const fp2_t s1 = fp2_add(mf_get2(lds, MF_FC(1)), mf_get2(lds, MF_FC(4)));
-      mf_put2(lds, MF_VC(11), fp2_mul(s0, m0));
-      mf_put2(lds, MF_VC(12), fp2_mul(s1, fp2_add(m1, m4)));
+      const F m4 = mf_get2<F>(lds, MF_LC(2 * k + 1, 0)), m5 = mf_get2<F>(lds, MF_LC(2 * k + 1, 1));
+      const F b2 = mf_get2<F>(lds, MF_FC(5));
+      mf_put2(lds, MF_VC(9), fmul(b2, m4));
+      mf_put2(lds, MF_VC(10), fmul(b2, m5));
+      const F s0 = fadd(mf_get2<F>(lds, MF_FC(0)), mf_get2<F>(lds, MF_FC(3)));
+      const F s1 = fadd(mf_get2<F>(lds, MF_FC(1)), mf_get2<F>(lds, MF_FC(4)));
+      mf_put2(lds, MF_VC(11), fmul(s0, m0));
+      mf_put2(lds, MF_VC(12), fmul(s1, fadd(m1, m4)));
     } else {
-      const fp2_t m4 = mf_get2(lds, MF_LC(2 * k + 1, 0)), m5 = mf_get2(lds, MF_LC(2 * k + 1, 1));
-      const fp2_t s0 = fp2_add(mf_get2(lds, MF_FC(0)), mf_get2(lds, MF_FC(3)));
-      const fp2_t s1 = fp2_add(mf_get2(lds, MF_FC(1)), mf_get2(lds, MF_FC(4)));
-      const fp2_t s2 = fp2_add(mf_get2(lds, MF_FC(2)), mf_get2(lds, MF_FC(5)));
-      const fp2_t q1 = fp2_add(m1, m4), q2 = fp2_add(m2, m5);
-      mf_put2(lds, MF_VC(13), fp2_mul(s2, q2));
-      mf_put2(lds, MF_VC(14), fp2_mul(fp2_add(s0, s1), fp2_add(m0, q1)));
-      mf_put2(lds, MF_VC(15), fp2_mul(fp2_add(s1, s2), fp2_add(q1, q2)));
-      mf_put2(lds, MF_VC(16), fp2_mul(fp2_add(s0, s2), fp2_add(m0, q2)));
+      const F m4 = mf_get2<F>(lds, MF_LC(2 * k + 1, 0)), m5 = mf_get2<F>(lds, MF_LC(2 * k + 1, 1));
+      const F s0 = fadd(mf_get2<F>(lds, MF_FC(0)), mf_get2<F>(lds, MF_FC(3)));
+      const F s1 = fadd(mf_get2<F>(lds, MF_FC(1)), mf_get2<F>(lds, MF_FC(4)));
+      const F s2 = fadd(mf_get2<F>(lds, MF_FC(2)), mf_get2<F>(lds, MF_FC(5)));
+      const F q1 = fadd(m1, m4), q2 = fadd(m2, m5);
+      mf_put2(lds, MF_VC(13), fmul(s2, q2));
+      mf_put2(lds, MF_VC(14), fmul(fadd(s0, s1), fadd(m0, q1)));
+      mf_put2(lds, MF_VC(15), fmul(fadd(s1, s2), fadd(q1, q2)));
+      mf_put2(lds, MF_VC(16), fmul(fadd(s0, s2), fadd(m0, q2)));
     }
   }
   __syncthreads();
-  auto V = [&](int p) { return mf_get2(lds, MF_VC(p)); };
+  auto V = [&](int p) { return mf_get2<F>(lds, MF_VC(p)); };
   // t0 = a M0, n = b (m4 + m5 v), t2 = s q (Karatsuba over Fp6, as in mf_sqr);
   // f'.c0 = t0 + v t1 = t0 + (xi n1, xi n2, n0);  f'.c1 = t2 - t0 - t1 = t2 - t0 - (xi n2, n0, n1):
   // each coefficient one regrouped lazy sum (lsg_pairing.hpp mfc_mul)
-  fp2_t o0, o1;
+  F o0, o1;
   int j0, j1 = -1;
   if (w == 0) {  // c0.0, c0.1
     o0 = mfc_mul<0>(V);
@@ -315,63 +370,65 @@ LSG_DEVI void mf_mul_pair(uint32_t* lds, int w, int k) {
 // line_eval (lsg_pairing.hpp), the same formulas in the same order, but each line
 // coefficient is evaluated at P and written to its slot as soon as it exists, and T's
 // coordinates go back to their slots as soon as they are final.  Computed first and written
-// last (the generic step), the line's three Fp2 values were live across the remaining point
-// products and went to scratch (176 B per lane).
-#ifndef LSG_MF_STAGED
-#define LSG_MF_STAGED 1
-#endif
-LSG_DEVI void mf_put_line(uint32_t* lds, int wl, bool use, const fp2_t& l00, const fp2_t& l01P, const fp2_t& l11P) {
-  mf_put2(lds, MF_LC(wl, 0), fp2_select(use, l00, fp2_one()));
-  mf_put2(lds, MF_LC(wl, 1), fp2_select(use, l01P, fp2_zero()));
-  mf_put2(lds, MF_LC(wl, 2), fp2_select(use, l11P, fp2_zero()));
+// last (ml_dbl_step_raw + line_eval, the split kernels' steps, once an alternative here), the
+// line's three Fp2 values were live across the remaining point products and went to scratch
+// (176 B per lane).
+template <class F>
+LSG_DEVI void mf_put_line(uint32_t* lds, int wl, bool use, const F& l00, const F& l01P, const F& l11P) {
+  mf_put2(lds, MF_LC(wl, 0), fselect(use, l00, mf_layout<F>::one()));
+  mf_put2(lds, MF_LC(wl, 1), fselect(use, l01P, fzero<F>()));
+  mf_put2(lds, MF_LC(wl, 2), fselect(use, l11P, fzero<F>()));
 }
+template <class F>
 LSG_DEVI void mf_dbl_line(uint32_t* lds, int wl, bool use, const uint32_t* __restrict__ P, size_t sl) {
   const int tb = MF_T + 6 * wl;
-  fp2_t t0, t1, t2, v1;
+  F t0, t1, t2, v1;
   {
-    const fp2_t X = mf_get2(lds, tb), Y = mf_get2(lds, tb + 2), Z = mf_get2(lds, tb + 4);
-    t0 = fp2_sqr(Y);
-    t1 = fp2_mul(Y, Z);
-    t2 = fp2_mul_b3(fp2_sqr(Z));
-    const fp2_t XX = fp2_sqr(X);
-    v1 = fp2_mul(X, Y);
+    const F X = mf_get2<F>(lds, tb), Y = mf_get2<F>(lds, tb + 2), Z = mf_get2<F>(lds, tb + 4);
+    t0 = fsqr(Y);
+    t1 = fmul(Y, Z);
+    t2 = fmul_b3(fsqr(Z));
+    const F XX = fsqr(X);
+    v1 = fmul(X, Y);
     const g1a_t Pk = lane_load<g1a_t>(P, sl);
-    mf_put_line(lds, wl, use, fp2_sub(t2, t0), fp2_mul_fp(fp2_mulk<3>(XX), Pk.x),
-                fp2_mul_fp((-fp2s(t1)).carry_mul<2>(), Pk.y));
+    mf_put_line(lds, wl, use, fsub(t2, t0), fmul_fp(fmulk<3>(XX), mf_layout<F>::fp_in(Pk.x)),
+                fmul_fp((-fsum(t1)).template carry_mul<2>(), mf_layout<F>::fp_in(Pk.y)));
   }
-  fp2_t Z3 = fp2_mulk<8>(t0);
-  fp2_t X3 = fp2_mul(t2, Z3);
-  fp2_t Y3 = fp2_add(t0, t2);
-  mf_put2(lds, tb + 4, fp2_mul(t1, Z3));
-  const fp2_t s0 = (fp2s(t0) - fp2s_mulk<3>(fp2s(t2))).carry();  // t0 - 3 t2
-  Y3 = fp2_mul(s0, Y3);
-  mf_put2(lds, tb + 2, fp2_add(X3, Y3));
-  X3 = fp2_mul(s0, v1);
-  mf_put2(lds, tb, fp2_mulk<2>(X3));
+  F Z3 = fmulk<8>(t0);
+  F X3 = fmul(t2, Z3);
+  F Y3 = fadd(t0, t2);
+  mf_put2(lds, tb + 4, fmul(t1, Z3));
+  const F s0 = (fsum(t0) - fsum_mulk<3>(fsum(t2))).carry();  // t0 - 3 t2
+  Y3 = fmul(s0, Y3);
+  mf_put2(lds, tb + 2, fadd(X3, Y3));
+  X3 = fmul(s0, v1);
+  mf_put2(lds, tb, fmulk<2>(X3));
 }
+template <class F>
 LSG_DEVI void mf_add_line(uint32_t* lds, int wl, bool use, const uint32_t* __restrict__ P, const uint32_t* __restrict__ H,
                           size_t sl) {
   const int tb = MF_T + 6 * wl;
-  fp2_t theta, delta;
+  F theta, delta;
   {
-    const g2a_t Q = lane_load<g2a_t>(H, sl);
-    const fp2_t Z = mf_get2(lds, tb + 4);
-    theta = fp2_sub(mf_get2(lds, tb + 2), fp2_mul(Q.y, Z));
-    delta = fp2_sub(mf_get2(lds, tb), fp2_mul(Q.x, Z));
-    const fp2_t l00 = fp2_sub(fp2_mul(delta, Q.y), fp2_mul(theta, Q.x));
+    const aff_t<F> Q = g2_layout<F>::in(lane_load<g2a_t>(H, sl));
+    const F Z = mf_get2<F>(lds, tb + 4);
+    theta = fsub(mf_get2<F>(lds, tb + 2), fmul(Q.y, Z));
+    delta = fsub(mf_get2<F>(lds, tb), fmul(Q.x, Z));
+    const F l00 = fsub(fmul(delta, Q.y), fmul(theta, Q.x));
     const g1a_t Pk = lane_load<g1a_t>(P, sl);
-    mf_put_line(lds, wl, use, l00, fp2_mul_fp(theta, Pk.x), fp2_mul_fp(fp2_neg(delta), Pk.y));
+    mf_put_line(lds, wl, use, l00, fmul_fp(theta, mf_layout<F>::fp_in(Pk.x)),
+                fmul_fp(fneg(delta), mf_layout<F>::fp_in(Pk.y)));
   }
-  const fp2_t C = fp2_sqr(theta);
-  const fp2_t D = fp2_sqr(delta);
-  const fp2_t E = fp2_mul(D, delta);
-  const fp2_t F = fp2_mul(mf_get2(lds, tb + 4), C);
-  const fp2_t G = fp2_mul(mf_get2(lds, tb), D);
-  const fp2_t Hs = (fp2s(E) + F - fp2s_mulk<2>(fp2s(G))).carry();  // E + F - 2G
-  mf_put2(lds, tb, fp2_mul(delta, Hs));
-  const fp2_t Y3 = fp2_sub(fp2_mul(theta, fp2_sub(G, Hs)), fp2_mul(E, mf_get2(lds, tb + 2)));
+  const F C = fsqr(theta);
+  const F D = fsqr(delta);
+  const F E = fmul(D, delta);
+  const F Fz = fmul(mf_get2<F>(lds, tb + 4), C);
+  const F G = fmul(mf_get2<F>(lds, tb), D);
+  const F Hs = (fsum(E) + Fz - fsum_mulk<2>(fsum(G))).carry();  // E + F - 2G
+  mf_put2(lds, tb, fmul(delta, Hs));
+  const F Y3 = fsub(fmul(theta, fsub(G, Hs)), fmul(E, mf_get2<F>(lds, tb + 2)));
   mf_put2(lds, tb + 2, Y3);
-  mf_put2(lds, tb + 4, fp2_mul(E, mf_get2(lds, tb + 4)));
+  mf_put2(lds, tb + 4, fmul(E, mf_get2<F>(lds, tb + 4)));
 }
 
 // Issue priority of the fused kernel's waves (s_setprio; 0 = the default of every wave).  Its
@@ -385,14 +442,12 @@ LSG_DEVI void mf_add_line(uint32_t* lds, int wl, bool use, const uint32_t* __res
 #ifndef LSG_MF_WAVES
 #define LSG_MF_WAVES 2  // waves per SIMD the register budget is sized for (256 VGPR + AGPR)
 #endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSG_MF_WAVES)))
-k_miller_fused(int n_items, const int32_t* __restrict__ item_first, const int32_t* __restrict__ item_cnt,
-               const uint32_t* __restrict__ P, const uint8_t* __restrict__ pinf, const uint8_t* __restrict__ hinf,
-               const int32_t* __restrict__ err, const uint32_t* __restrict__ H, uint32_t* __restrict__ f_out) {
-  // dynamic LDS (MF_LDS_BYTES at launch): the compiler then sizes registers for
-  // LSG_MF_WAVES waves per SIMD instead of the one workgroup per CU the LDS allows, so the
-  // other kernels of the pipeline can share the SIMDs while this one waits at its barriers
-  extern __shared__ uint32_t lds[];
+#define MF_KERNEL_PARAMS                                                                                        \
+  int n_items, const int32_t *__restrict__ item_first, const int32_t *__restrict__ item_cnt,                   \
+      const uint32_t *__restrict__ P, const uint8_t *__restrict__ pinf, const uint8_t *__restrict__ hinf,      \
+      const int32_t *__restrict__ err, const uint32_t *__restrict__ H, uint32_t *__restrict__ f_out
+template <class F>
+LSG_DEVI void mf_body(uint32_t* lds, MF_KERNEL_PARAMS) {
 #if LSG_MF_PRIO
   __builtin_amdgcn_s_setprio(LSG_MF_PRIO);
 #endif
@@ -405,9 +460,9 @@ k_miller_fused(int n_items, const int32_t* __restrict__ item_first, const int32_
   // the lanes whose pair contributes, as a wave mask (SGPRs) rather than a live VGPR
   const uint64_t use_mask = __ballot(live && w < cnt && err[si] == 0 && !pinf[si] && !hinf[si]);
   // nothing stays in registers across the loop: T lives in LDS, Q (addition steps) and P are
-  // re-read from global memory (L2 hits)
+  // re-read from global memory (L2 hits) and converted to the layout F there
   {
-    const g2p_t T = proj_from_aff(lane_load<g2a_t>(H, (size_t)si));
+    const proj_t<F> T = proj_from_aff(g2_layout<F>::in(lane_load<g2a_t>(H, (size_t)si)));
     mf_put2(lds, MF_T + 6 * w, T.X);
     mf_put2(lds, MF_T + 6 * w + 2, T.Y);
     mf_put2(lds, MF_T + 6 * w + 4, T.Z);
@@ -417,45 +472,30 @@ k_miller_fused(int n_items, const int32_t* __restrict__ item_first, const int32_
     // slot addresses and point pointers were spilled to scratch and reloaded every step
     int wl = w, sl = si;
     asm volatile("" : "+s"(wl), "+v"(sl));
-#if LSG_MF_STAGED
     const bool use = (use_mask >> __lane_id()) & 1u;
     if (add)
-      mf_add_line(lds, wl, use, P, H, (size_t)sl);
+      mf_add_line<F>(lds, wl, use, P, H, (size_t)sl);
     else
-      mf_dbl_line(lds, wl, use, P, (size_t)sl);
-#else
-    g2p_t T;  // this wave's own slots: no other wave touches them
-    T.X = mf_get2(lds, MF_T + 6 * wl);
-    T.Y = mf_get2(lds, MF_T + 6 * wl + 2);
-    T.Z = mf_get2(lds, MF_T + 6 * wl + 4);
-    line_t L = add ? ml_add_step_raw(T, lane_load<g2a_t>(H, (size_t)sl)) : ml_dbl_step_raw(T);
-    mf_put2(lds, MF_T + 6 * wl, T.X);
-    mf_put2(lds, MF_T + 6 * wl + 2, T.Y);
-    mf_put2(lds, MF_T + 6 * wl + 4, T.Z);
-    const g1a_t Pk = lane_load<g1a_t>(P, (size_t)sl);
-    L = line_eval(L, Pk.x, Pk.y);
-    const bool use = (use_mask >> __lane_id()) & 1u;
-    mf_put2(lds, MF_LC(wl, 0), fp2_select(use, L.l00, fp2_one()));
-    mf_put2(lds, MF_LC(wl, 1), fp2_select(use, L.l01, fp2_zero()));
-    mf_put2(lds, MF_LC(wl, 2), fp2_select(use, L.l11, fp2_zero()));
-#endif
+      mf_dbl_line<F>(lds, wl, use, P, (size_t)sl);
     __syncthreads();
-    mf_pair_lines(lds, wl);
+    mf_pair_lines<F>(lds, wl);
 #pragma unroll 1
-    for (int k = 0; k < 2; k++) mf_mul_pair(lds, wl, k);
+    for (int k = 0; k < 2; k++) mf_mul_pair<F>(lds, wl, k);
   };
-  // f = 1 (each wave writes a third of the coefficients' limbs: c0.c0 = 1, the rest 0)
+  // f = 1: waves 0 and 1 write three Fp2 coefficients each (c0.c0 = 1, the rest 0)
   if (w < 2) {
-    mf_put2(lds, MF_FC(3 * w), w == 0 ? fp2_one() : fp2_zero());
-    mf_put2(lds, MF_FC(3 * w + 1), fp2_zero());
-    mf_put2(lds, MF_FC(3 * w + 2), fp2_zero());
+    mf_put2(lds, MF_FC(3 * w), w == 0 ? fone<F>() : fzero<F>());
+    mf_put2(lds, MF_FC(3 * w + 1), fzero<F>());
+    mf_put2(lds, MF_FC(3 * w + 2), fzero<F>());
   }
   const uint64_t xa = ((uint64_t)LSG_X_ABS_HI << 32) | LSG_X_ABS_LO;
   line_phase(false);  // the first doubling
   line_phase(true);   // bit 62 of |x|
 #pragma unroll 1
   for (int b = 61; b >= 0; b--) {
-    mf_sqr(lds, w);
+    int ws = w;  // (re-materialised as in line_phase: its slot addresses are not kept across the loop)
+    asm volatile("" : "+s"(ws));
+    mf_sqr<F>(lds, ws);
     line_phase(false);
     if ((xa >> b) & 1u) line_phase(true);
   }
@@ -465,25 +505,60 @@ k_miller_fused(int n_items, const int32_t* __restrict__ item_first, const int32_
 #pragma unroll
     for (int j = 0; j < 3; j++) {
       const int c = 3 * w + j;
-      fp_t v = mf_get(lds, MF_F + c);
+      fp_t v = mf_layout<F>::fp_out(lds, MF_F + c);
       if (c >= 6) v = fp_neg(v);
 #pragma unroll
       for (int k = 0; k < LSG_PL; k++) o[(7 * c + k) * LSG_GROUP] = v.l[k];
     }
   }
 }
+// dynamic LDS (MF_LDS_BYTES at launch): the compiler then sizes registers for LSG_MF_WAVES
+// waves per SIMD instead of the one workgroup per CU the LDS allows, so the other kernels of
+// the pipeline can share the SIMDs while this one waits at its barriers
+#define MF_KERNEL_ATTR __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSG_MF_WAVES)))
+#define MF_KERNEL_ARGS n_items, item_first, item_cnt, P, pinf, hinf, err, H, f_out
+#ifdef LSG_FP2_LANES
+__global__ void MF_KERNEL_ATTR k_miller_fused(MF_KERNEL_PARAMS) {
+  extern __shared__ uint32_t lds[];
+  mf_body<fp2v_t>(lds, MF_KERNEL_ARGS);
+}
+// the same kernel on the pair form: the A/B library's LSG_MF_LANES=0 and the device tests
+__global__ void MF_KERNEL_ATTR k_miller_fused_pair(MF_KERNEL_PARAMS) {
+  extern __shared__ uint32_t lds[];
+  mf_body<fp2_t>(lds, MF_KERNEL_ARGS);
+}
+#else
+__global__ void MF_KERNEL_ATTR k_miller_fused(MF_KERNEL_PARAMS) {
+  extern __shared__ uint32_t lds[];
+  mf_body<fp2_t>(lds, MF_KERNEL_ARGS);
+}
+#endif
 
 namespace lsgk {
-hipError_t miller_fused(hipStream_t st, int n_items, const int32_t* item_first, const int32_t* item_cnt,
-                        const uint32_t* P, const uint8_t* pinf, const uint8_t* hinf, const int32_t* err,
-                        const uint32_t* H, uint32_t* f) {
-  if (n_items <= 0) return hipSuccess;
-  static const hipError_t attr = hipFuncSetAttribute((const void*)k_miller_fused,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)MF_LDS_BYTES);
+template <class K>
+static hipError_t mf_launch(K kernel, hipError_t attr, hipStream_t st, int n_items, const int32_t* item_first,
+                            const int32_t* item_cnt, const uint32_t* P, const uint8_t* pinf, const uint8_t* hinf,
+                            const int32_t* err, const uint32_t* H, uint32_t* f) {
   if (attr != hipSuccess) return attr;
-  hipLaunchKernelGGL(k_miller_fused, dim3((n_items + MF_ITEMS - 1) / MF_ITEMS), dim3(256), MF_LDS_BYTES, st, n_items, item_first,
+  hipLaunchKernelGGL(kernel, dim3((n_items + MF_ITEMS - 1) / MF_ITEMS), dim3(256), MF_LDS_BYTES, st, n_items, item_first,
                      item_cnt, P, pinf, hinf, err, H, f);
   return hipGetLastError();
+}
+hipError_t miller_fused(hipStream_t st, int n_items, const int32_t* item_first, const int32_t* item_cnt,
+                        const uint32_t* P, const uint8_t* pinf, const uint8_t* hinf, const int32_t* err,
+                        const uint32_t* H, uint32_t* f, bool pair_form) {
+  if (n_items <= 0) return hipSuccess;
+#ifdef LSG_FP2_LANES
+  if (pair_form) {
+    static const hipError_t attr_pair = hipFuncSetAttribute(
+        (const void*)k_miller_fused_pair, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MF_LDS_BYTES);
+    return mf_launch(k_miller_fused_pair, attr_pair, st, n_items, item_first, item_cnt, P, pinf, hinf, err, H, f);
+  }
+#endif
+  (void)pair_form;
+  static const hipError_t attr = hipFuncSetAttribute((const void*)k_miller_fused,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)MF_LDS_BYTES);
+  return mf_launch(k_miller_fused, attr, st, n_items, item_first, item_cnt, P, pinf, hinf, err, H, f);
 }
 hipError_t miller_lines_list(hipStream_t st, int n, const int32_t* list, const uint32_t* H, uint32_t* lines) {
   LSG_LAUNCH_ITEMS(k_miller_lines_list, n, st, n, list, H, lines);

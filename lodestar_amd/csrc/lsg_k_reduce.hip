@@ -391,6 +391,44 @@ __global__ void LSG_KERNEL_ATTR k_check_g2_lanes(int n, const uint32_t* __restri
   putv(jac_add_proj(Jv, g2v_from_pair(Q)));
   putp(jac_add_proj(J, Q));
 }
+// k_check_mf_lanes: the pieces the fused Miller kernel adds to the layout; 12 elements in
+// (A .. F as above), 24 out, each lane-layout result converted back beside its pair-form twin:
+//    0  fmul_fp(A, B.c0)            1  fp2_mul_fp(A, B.c0)
+//    2  fmul_xi(A)                  3  fp2_mul_xi(A)
+//    4  A + xi (B - C), one carry   5  the same on fp2s_t
+//    6..8  fp6_mul_v((A, B, C))     9  fone     10  fzero
+//   11  B.c0 spread over both lanes (fpv_from_pair) as the lanes hold it: word k of lane h at 2 k + h
+__global__ void LSG_KERNEL_ATTR k_check_mf_lanes(int n, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  (void)lead;
+  auto el2 = [&](int j) {
+    return fp2_t(lane_load<fp_t>(in, (size_t)lsgk::CHECK_LANES_IN * item + 2 * j),
+                 lane_load<fp_t>(in, (size_t)lsgk::CHECK_LANES_IN * item + 2 * j + 1));
+  };
+  int o = 0;
+  auto put2 = [&](const fp2_t& w) {
+    lane_store(out, (size_t)lsgk::CHECK_LANES_OUT * item + (size_t)o, w.c0);
+    lane_store(out, (size_t)lsgk::CHECK_LANES_OUT * item + (size_t)o + 1, w.c1);
+    o += 2;
+  };
+  auto put = [&](const fp2v_t& v) { put2(fp2v_to_pair(v)); };
+  const fp2_t Ap = el2(0), Bp = el2(1), Cp = el2(2);
+  const fp2v_t A = fp2v_from_pair(Ap), B = fp2v_from_pair(Bp), C = fp2v_from_pair(Cp);
+  const fpv_t k = fpv_from_pair(Bp.c0);
+  put(fmul_fp(A, k));
+  put2(fp2_mul_fp(Ap, Bp.c0));
+  put(fmul_xi(A));
+  put2(fp2_mul_xi(Ap));
+  put((fsum(A) + fsum_mul_xi(fsum(B) - C)).carry());
+  put2((fp2s(Ap) + fp2s_mul_xi(fp2s(Bp) - Cp)).carry());
+  const fp6v_t v = fp6_mul_v(fp6_make(A, B, C));
+  put(v.c0);
+  put(v.c1);
+  put(v.c2);
+  put(fone<fp2v_t>());
+  put(fzero<fp2v_t>());
+  lane_store(out + (size_t)lsgk::CHECK_LANES_OUT * lsgl::W_FP * item + (size_t)o * lsgl::W_FP, 0, k);
+}
 #endif
 
 // parity hooks of the layer between the products and the accept / reject rules: canonical
@@ -529,7 +567,11 @@ hipError_t check_fp2_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* 
 hipError_t check_g2_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
   LSG_LAUNCH_ITEMS(k_check_g2_lanes, n, st, n, in, out);
 }
+hipError_t check_mf_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
+  LSG_LAUNCH_ITEMS(k_check_mf_lanes, n, st, n, in, out);
+}
 #else  // -DLSG_NO_FP2_LANES: the layout is not built
+hipError_t check_mf_lanes(hipStream_t, int, const uint32_t*, uint32_t*) { return hipErrorNotSupported; }
 hipError_t check_fp2_lanes(hipStream_t, int, const uint32_t*, uint32_t*) { return hipErrorNotSupported; }
 hipError_t check_g2_lanes(hipStream_t, int, const uint32_t*, uint32_t*) { return hipErrorNotSupported; }
 #endif

@@ -143,10 +143,11 @@ hipError_t g1p_to_bytes(hipStream_t st, int n, const uint32_t* pts, uint8_t* out
 hipError_t sk_to_pk(hipStream_t st, int n, const uint8_t* sks, uint8_t* out96);
 
 // ---- Miller loop (lsg_k_miller.hip)                                   SURVEY 8a M5
-// lines in LDS, four waves per item of <= 4 sets (f_item = prod of the item's pairs)
+// lines in LDS, four waves per item of <= 4 sets (f_item = prod of the item's pairs); pair_form:
+// the twin that keeps Fp2 in the pair form (k_miller_fused_pair) instead of one component per lane
 hipError_t miller_fused(hipStream_t st, int n_items, const int32_t* item_first, const int32_t* item_cnt,
                         const uint32_t* P, const uint8_t* pinf, const uint8_t* hinf, const int32_t* err,
-                        const uint32_t* H, uint32_t* f);
+                        const uint32_t* H, uint32_t* f, bool pair_form = false);
 hipError_t miller_lines(hipStream_t st, int n, const uint32_t* H, uint32_t* lines);
 // list form, one pair per item: item k = set list[k]; lines stored by item (n items)
 hipError_t miller_lines_list(hipStream_t st, int n, const int32_t* list, const uint32_t* H, uint32_t* lines);
@@ -185,6 +186,7 @@ hipError_t check_sums(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 constexpr int CHECK_LANES_IN = 12, CHECK_LANES_OUT = 24, CHECK_G2L_IN = 12, CHECK_G2L_OUT = 24;  // elements per item
 hipError_t check_fp2_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t check_g2_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
+hipError_t check_mf_lanes(hipStream_t st, int n, const uint32_t* in, uint32_t* out);  // CHECK_LANES_IN / _OUT
 // the field-edge hooks (lodestar_bls.h lsg_check_canon, lsg_check_fp2_roots)
 constexpr int CHECK_CANON_OUT = 54, CHECK_ROOTS_OUT = 58;  // words per item out
 hipError_t check_canon(hipStream_t st, int n, const uint32_t* in, uint32_t* out);

@@ -79,40 +79,42 @@ LSG_INL line_t line_eval(line_t L, const fp_t& xP, const fp_t& yP) {
 // holds those forms and compares).
 // S phase, f <- f^2: V0..5 the Karatsuba products of t = a b, V6..11 those of
 // u = (a + b)(a + v b).  J = 0..2: new c1.J = 2 t_J;  J = 3..5: new c0.(J-3) = (u - t - v t)_(J-3).
+// The products come in the layout V returns them in (fp2_t, or fp2v_t of lsg_fp2_lanes.hpp whose
+// sums count the larger of the two lanes' terms): every grouping below fits both.
 template <int J, class G>
-LSG_INL fp2_t mfc_sqr(const G& V) {
+LSG_INL auto mfc_sqr(const G& V) {
   if constexpr (J == 0) {
     return fp6_kar_s0(V(0), V(1), V(2), V(3)).template carry_mul<2>();
   } else if constexpr (J == 1) {
     return fp6_kar_s1(V(0), V(1), V(2), V(4)).template carry_mul<2>();
   } else if constexpr (J == 2) {
     return fp6_kar_s2(V(0), V(1), V(2), V(5)).template carry_mul<2>();
-  } else if constexpr (J == 3) {  // u0 - t0 - xi t2
-    const fp2_t d = (fp6_kar_s0(V(6), V(7), V(8), V(9)) - fp6_kar_s0(V(0), V(1), V(2), V(3))).carry();
-    const fp2_t t2 = fp6_kar_s2(V(0), V(1), V(2), V(5)).carry();
-    return (fp2s(d) - fp2s_mul_xi(t2)).carry();
+  } else if constexpr (J == 3) {  // u0 - t0 - xi t2 = V6 - V0 + xi ((m0' - v1' - v2') - (m0 - v1 - v2) - t2)
+    const auto e = ((fsum(V(9)) - V(7) - V(8)) - (fsum(V(3)) - V(1) - V(2))).carry();
+    const auto g = (fsum(e) - fp6_kar_s2(V(0), V(1), V(2), V(5))).carry();
+    return (fsum(V(6)) - V(0) + fsum_mul_xi(g)).carry();
   } else if constexpr (J == 4) {  // u1 - t1 - t0, with u1 - t1 = (m1' - v0' - v1') - (m1 - v0 - v1) + xi (v2' - v2)
-    const fp2_t d = ((fp2s(V(10)) - V(6) - V(7)) - (fp2s(V(4)) - V(0) - V(1))).carry();
-    const fp2_t e = (fp2s(d) + fp2s_mul_xi(fp2s(V(8)) - V(2))).carry();
-    return (fp2s(e) - fp6_kar_s0(V(0), V(1), V(2), V(3))).carry();
+    const auto d = ((fsum(V(10)) - V(6) - V(7)) - (fsum(V(4)) - V(0) - V(1))).carry();
+    const auto e = (fsum(d) + fsum_mul_xi(fsum(V(8)) - V(2))).carry();
+    return (fsum(e) - fp6_kar_s0(V(0), V(1), V(2), V(3))).carry();
   } else {  // u2 - t2 - t1, with u2 - t2 = (m2' - v0' - v2') - (m2 - v0 - v2) + v1' - v1
-    const fp2_t d = ((fp2s(V(11)) - V(6) - V(8)) - (fp2s(V(5)) - V(0) - V(2))).carry();
-    const fp2_t t1 = fp6_kar_s1(V(0), V(1), V(2), V(4)).carry();
-    return (fp2s(d) + V(7) - V(1) - t1).carry();
+    const auto d = ((fsum(V(11)) - V(6) - V(8)) - (fsum(V(5)) - V(0) - V(2))).carry();
+    const auto t1 = fp6_kar_s1(V(0), V(1), V(2), V(4)).carry();
+    return (fsum(d) + V(7) - V(1) - t1).carry();
   }
 }
 // P phase, M = l l' of two sparse lines from P0..P5 = V(0..5) (see mf_pair_lines):
 // J = 0: m0 = P0 + xi P1, 1: m1 = P3 - P0 - P2, 2: m4 = P4 - P0 - P1, 3: m5 = P5 - P2 - P1
 template <int J, class G>
-LSG_INL fp2_t mfc_pair(const G& V) {
+LSG_INL auto mfc_pair(const G& V) {
   if constexpr (J == 0) {
-    return (fp2s(V(0)) + fp2s_mul_xi(V(1))).carry();
+    return (fsum(V(0)) + fsum_mul_xi(V(1))).carry();
   } else if constexpr (J == 1) {
-    return fp2_sub2(V(3), V(0), V(2));
+    return fsub2(V(3), V(0), V(2));
   } else if constexpr (J == 2) {
-    return fp2_sub2(V(4), V(0), V(1));
+    return fsub2(V(4), V(0), V(1));
   } else {
-    return fp2_sub2(V(5), V(2), V(1));
+    return fsub2(V(5), V(2), V(1));
   }
 }
 // M phase, f <- f M from V0..16 (see mf_mul_pair): t0 = a M0 from V0..5 (m0 = V4, m1 = V3,
@@ -121,28 +123,28 @@ LSG_INL fp2_t mfc_pair(const G& V) {
 // t0_0 + xi n1, t0_1 + xi n2, t0_2 + n0;  J = 3..5: f'.c1.(J-3) = (t2 - t0 - v n)_(J-3), i.e.
 // t2_0 - t0_0 - xi n2, t2_1 - t0_1 - n0, t2_2 - t0_2 - n1.
 template <int J, class G>
-LSG_INL fp2_t mfc_mul(const G& V) {
+LSG_INL auto mfc_mul(const G& V) {
   if constexpr (J == 0) {  // V0 + xi (V4 - V1 - V2 + V8 - V6 - V7)
-    const fp2_t g = (fp2s(V(4)) - V(1) - V(2) + V(8)).carry();
-    const fp2_t h = (fp2s(g) - V(6) - V(7)).carry();
-    return (fp2s(V(0)) + fp2s_mul_xi(h)).carry();
+    const auto g = (fsum(V(4)) - V(1) - V(2) + V(8)).carry();
+    const auto h = (fsum(g) - V(6) - V(7)).carry();
+    return (fsum(V(0)) + fsum_mul_xi(h)).carry();
   } else if constexpr (J == 1) {  // V3 - V0 - V1 + xi (V2 + V7 + V9)
-    const fp2_t h = (fp2s(V(2)) + V(7) + V(9)).carry();
-    return ((fp2s(V(3)) - V(0) - V(1)) + fp2s_mul_xi(h)).carry();
+    const auto h = (fsum(V(2)) + V(7) + V(9)).carry();
+    return ((fsum(V(3)) - V(0) - V(1)) + fsum_mul_xi(h)).carry();
   } else if constexpr (J == 2) {  // V5 - V0 - V2 + V1 + V6 + xi V10
-    const fp2_t n0 = (fp2s(V(6)) + fp2s_mul_xi(V(10))).carry();
-    return (fp2s(V(5)) - V(0) - V(2) + V(1) + n0).carry();
+    const auto n0 = (fsum(V(6)) + fsum_mul_xi(V(10))).carry();
+    return (fsum(V(5)) - V(0) - V(2) + V(1) + n0).carry();
   } else if constexpr (J == 3) {  // V11 - V0 + xi (V15 - V12 - V13 - V4 + V1 + V2 - V7 - V9)
-    const fp2_t g = (fp2s(V(15)) - V(12) - V(13) + V(1) + V(2)).carry();
-    const fp2_t h = (fp2s(g) - V(4) - V(7) - V(9)).carry();
-    return (fp2s(V(11)) - V(0) + fp2s_mul_xi(h)).carry();
+    const auto g = (fsum(V(15)) - V(12) - V(13) + V(1) + V(2)).carry();
+    const auto h = (fsum(g) - V(4) - V(7) - V(9)).carry();
+    return (fsum(V(11)) - V(0) + fsum_mul_xi(h)).carry();
   } else if constexpr (J == 4) {  // (V14 - V11 - V12) - (V3 - V0 - V1) - V6 + xi (V13 - V2 - V10)
-    const fp2_t a = ((fp2s(V(14)) - V(11) - V(12)) - (fp2s(V(3)) - V(0) - V(1))).carry();
-    const fp2_t b = fp2_sub2(V(13), V(2), V(10));
-    return (fp2s(a) - V(6) + fp2s_mul_xi(b)).carry();
+    const auto a = ((fsum(V(14)) - V(11) - V(12)) - (fsum(V(3)) - V(0) - V(1))).carry();
+    const auto b = fsub2(V(13), V(2), V(10));
+    return (fsum(a) - V(6) + fsum_mul_xi(b)).carry();
   } else {  // V16 + V12 + V0 + V2 + V6 + V7 - V11 - V13 - V5 - V1 - V8
-    const fp2_t g = (fp2s(V(11)) + V(13) + V(5) - V(16) - V(12) - V(0)).carry();
-    return (fp2s(V(2)) + V(6) + V(7) - V(1) - V(8) - g).carry();
+    const auto g = (fsum(V(11)) + V(13) + V(5) - V(16) - V(12) - V(0)).carry();
+    return (fsum(V(2)) + V(6) + V(7) - V(1) - V(8) - g).carry();
   }
 }
 
