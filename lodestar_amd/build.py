@@ -19,7 +19,7 @@ HEADERS = ["lsg_types.hpp", "lsg_fp_lane.hpp", "lsg_fp_elem.hpp", "lsg_tower.hpp
            "lsg_pairing.hpp", "lsg_constants.hpp", "lsg_fp_pair.hpp", "lsg_constants_r29.hpp", "lsg_io.hpp",
            "lsg_serial.h", "lsg_kcommon.hpp", "lsg_launch.h", "lsg_layout.h", "lsg_slp_progs.h", "lsg_slp_exec.hpp", "lsg_inv.hpp",
            "lsg_ab.h", "lsg_plan.hpp", "lsg_bits.h", "lsg_ssz.hpp", "lsg_fp2_lanes.hpp",
-           "lsg_msg_cache.hpp"]
+           "lsg_msg_cache.hpp", "lsg_stage.hpp"]
 OBJ = os.path.join(HERE, "_obj")
 # The A/B and test build (lsg_ab.h): the orchestration compiled with -DLSG_AB (its switches read
 # from the environment) plus the row-backend serial kernels (LSG_SERIAL=row); every other

@@ -18,13 +18,18 @@
 //     worker.ts (phase B) and then the jobs of failing chunks (phase C) checked, on the
 //     per-set values still resident, so per-job verdicts and the batch_retries /
 //     batch_sigs_success counters are the reference's.
-// Which file holds what: this one has the device side -- streams, events, buffers, staging,
+// Which file holds what: this one has the device side -- streams, events, buffers, copies,
 // kernel launches, tickets, locks.  The policy over small integers is host-only code in
 // lsg_plan.hpp (namespace lsgp), tested on the CPU by tests/native/plancheck.cpp: the staging
 // order and 16-job chunks of a package (PkgShape), its phase-A groups (plan_groups), the
-// Miller items and segmented reductions of a phase (plan_phase, plan_seg), the deserializeSet
-// rule (first_key_error) and the verdict rules (resolve_package, which calls back into
-// run_fallback_phase here for every phase B0 / B / C1 / C2 it needs).
+// Miller items and segmented reductions of a phase (plan_phase, plan_seg), the KeyValidate and
+// per-message lists (plan_validate_keys, plan_msg_lists), the deserializeSet rule
+// (first_key_error) and the verdict rules (resolve_package, which calls back into
+// run_fallback_phase here for every phase B0 / B / C1 / C2 it needs).  How the caller's sets
+// become the staged bytes is host-only too, lsg_stage.hpp, tested by tests/native/stagecheck.cpp:
+// the staging arena's layout (the one statement of its size), the distinct-message table, the
+// message-cache decisions, committee and key-slot staging, the randomizers; stage_sets here
+// sizes the buffers between its measuring and filling pass and issues the copies.
 // Per device a context owns LSG_SLOTS pipeline slots (two streams each, all buffers
 // preallocated by lsg_reserve); several devices share one ticket (whole jobs per device, one
 // all-gather of the 576-byte partials, one node final exponentiation: SURVEY.md 8e).
@@ -55,9 +60,11 @@
 #include "lsg_ab.h"
 #include "lsg_msg_cache.hpp"
 #include "lsg_plan.hpp"
+#include "lsg_stage.hpp"
 
 using namespace lsgl;
 using namespace lsgp;
+static_assert(lsgp::MC_ROW == LSG_MC_ROW, "the stager's row marker is the one the kernels read");
 
 namespace {
 
@@ -76,13 +83,6 @@ uint64_t now_ns() {
   timespec ts;
   clock_gettime(CLOCK_MONOTONIC, &ts);  // process.hrtime's clock (the Node host's metrics)
   return (uint64_t)ts.tv_sec * 1000000000ull + (uint64_t)ts.tv_nsec;
-}
-
-uint64_t splitmix64(uint64_t& s) {
-  uint64_t z = (s += 0x9e3779b97f4a7c15ull);
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
 }
 
 // OS CSPRNG bytes (getrandom(2)); false if the kernel cannot provide them.  There is no
@@ -178,7 +178,9 @@ struct AggPlan {
 };
 constexpr size_t AGG_TREE_MIN_KEYS = 32768;  // smaller packages: the serial fold + butterfly
 
-struct Slot {
+// (Staged, lsg_stage.hpp: what stage_sets leaves on the host -- n_sets, n_pks, pk_stride, rnd, the
+// distinct messages and message-cache words, the bits and multi sets, the package's shape)
+struct Slot : Staged {
   Dev* d = nullptr;
   int index = 0;
   hipStream_t st[2] = {nullptr, nullptr};  // [0] main, [1] side
@@ -194,50 +196,26 @@ struct Slot {
   // inputs (device copies of the pinned staging arena)
   DevBuf d_sig, d_siglen, d_msg, d_msgoff, d_msglen, d_pk, d_pklen, d_rnd, d_mode, d_dst;
   HostBuf h_arena;
-  size_t n_sets = 0, n_pks = 0;
-  std::vector<uint64_t> rnd;
-  // distinct messages of the staged package: set i hashes message msg_id[i] (n_msgs of them);
-  // msg_dedup when some sets share one (a committee's attestations sign one AttestationData)
-  size_t n_msgs = 0;
-  bool msg_dedup = false;
-  bool msg_objs = false;  // a staged message is an SSZ object + domain (LSG_MSG_OBJECT)
-  std::vector<uint32_t> mtab, mfirst;
-  std::vector<uint64_t> mkey;
-  std::vector<uint32_t> msg_id;  // host copy of the set -> message map (msg_dedup)
+  MsgTable mtab;  // the distinct-message table's storage, reused from package to package
   // the message cache (lsg_msg_cache_set).  mc_ok: this package may use it (set by
-  // the submitter); mc_on: it was staged through it -- n_miss of the n_msgs distinct messages
-  // are staged and hashed, mc_hits come from arena rows (mc_pins: pinned until the launch's
-  // completion is observed), mc_pend rows are written by k_h2c_cache_store and published then.
-  // Plan arena: one source word per distinct message at mc_src_off, the (miss, row) pairs of
-  // the store at mc_st_off.
-  bool mc_ok = false, mc_on = false;
-  uint64_t mc_epoch = 0;
-  size_t n_miss = 0, mc_hits = 0, mc_src_off = 0, mc_st_off = 0;
-  std::vector<uint32_t> mc_pins, mc_pend;
-  std::vector<int32_t> mc_store;
+  // the submitter); Staged::mc_on: it was staged through it
+  bool mc_ok = false;
   DevBuf d_Hx, d_hinfx;  // the misses' points when some message hit
   SegPlan msum;                  // msg_agg: per message, the masked scaled keys of the package group
   DevBuf d_mmask, d_PmP, d_Pm, d_pinfm, d_errm;
-  bool single_keys = false;  // every set has exactly one key (key i is set i's)
   // sets given as committee id + participation bits (LSG_PK_BITS): their
   // fields staged into the bit arena (h_cbits -> d_cbits, allocated by the first such package),
-  // aggregated by k_pk_agg_bits (bplan) instead of run_pk_seg; pk_all_bits: no other kind of set
-  std::vector<BitsSet> bits_sets;
+  // aggregated by k_pk_agg_bits (bplan) instead of run_pk_seg
   BitsPlan bplan;
   HostBuf h_cbits;
   DevBuf d_cbits;
-  bool pk_all_bits = false;
   // sets given as a committee list + one bitfield (LSG_PK_BITS_MULTI): their parts' fields in the
-  // same bit arena, aggregated by k_pk_agg_bits_multi (mplan) after k_pk_agg_bits; such a set is
-  // a bits set to everything else (shape.bits_p / bits_kerr, pk_all_bits)
-  std::vector<MultiSet> multi_sets;
-  std::vector<MultiPart> multi_parts;
+  // same bit arena, aggregated by k_pk_agg_bits_multi (mplan) after k_pk_agg_bits
   MultiPlan mplan;
   // KeyValidate of the byte keys of LSG_JOB_VALIDATE_KEYS jobs: n_kv list items (staged key,
   // its set) in the plan arena at kv_off, kv_off + n_kv; shape.kv_set[i] != 0: set i's keys are
   // on the list (empty when the package has no such job: nothing staged, nothing launched)
   size_t n_kv = 0, kv_off = 0;
-  uint32_t pk_stride = 96;   // bytes per key slot in d_pk: 4 when every key is a table index
   // per-set state
   DevBuf d_ub, d_sigaff, d_siginf, d_seterr, d_pkp, d_pkerr, d_agg, d_P, d_pinf, d_H, d_hinf, d_rs, d_rs2, d_fall,
       d_fall2;
@@ -267,9 +245,8 @@ struct Slot {
   // ticket state
   int kind = SLOT_FREE;
   uint64_t serial = 0;
-  // this device's share of the package (jobs in staging order, sub-package bounds of a
-  // coalesced launch, per-set key counts), its phase-A groups and the switches read for it
-  PkgShape shape;
+  // (Staged::shape: this device's share of the package -- jobs in staging order, sub-package
+  // bounds of a coalesced launch, per-set key counts); its phase-A groups and the switches read for it
   GroupPlan gp;
   Switches sw;
   int K = 4;  // Miller pairs per item for this package
@@ -711,9 +688,7 @@ size_t binv_iv_words(size_t n) {
 // inputs for up to n sets / np keys / mb message bytes
 int size_inputs(Slot* s, size_t n, size_t np, size_t mb) {
   const size_t nn = std::max(n, (size_t)1), pp = std::max(np, (size_t)1);
-  auto al = [](size_t x) { return (x + 7) & ~(size_t)7; };
-  const size_t arena = al(192 * nn) + al(4 * nn) * 4 + al(4 * pp) + al(8 * nn) + al(96 * pp) + al(std::max(mb, (size_t)1)) + nn;
-  LSG_RC(ensure_host(s, s->h_arena, arena));
+  LSG_RC(ensure_host(s, s->h_arena, stage_layout(n, np, 96, mb).bytes));  // (96: the wider key slot)
   LSG_RC(ensure(s, s->d_sig, 192 * nn));
   LSG_RC(ensure(s, s->d_siglen, 4 * nn));
   LSG_RC(ensure(s, s->d_msg, std::max(mb, (size_t)1)));
@@ -1004,329 +979,48 @@ int launch_hash(Slot* s, int n, uint32_t* H, uint8_t* hinf) {
 }
 
 // ---- staging: the package's sets into the slot's pinned arena (order given by `order`),
-// randomizers drawn here (seed == 0: OS CSPRNG; else deterministic, for tests)
-// 64-bit mix of a message (its length and 8-byte words; signing roots are SHA-256 outputs).
-// msg_len as the set carries it: an LSG_MSG_OBJECT marker goes into the mix, not the byte count
-static uint64_t msg_key(const uint8_t* m, uint32_t msg_len) {
-  uint64_t h = 0x9e3779b97f4a7c15ull ^ msg_len;
-  const uint32_t len = msg_bytes(msg_len);
-  uint32_t k = 0;
-  for (; k + 8 <= len; k += 8) {
-    uint64_t w;
-    memcpy(&w, m + k, 8);
-    h = (h ^ w) * 0xff51afd7ed558ccdull;
-    h ^= h >> 32;
-  }
-  for (; k < len; k++) h = (h ^ m[k]) * 0x100000001b3ull;
-  return h ^ (h >> 29);
-}
-
-// bits_ok: a set with pk_len == LSG_PK_BITS names its keys by committee id + participation bits
-// (the entry points that take sets); false where the caller passes one key list of one length
-// (lsg_aggregate_pubkeys, the table and KeyValidate calls), which keeps treating 8 as an
-// unknown key length.  Such a set stages its id and bits only -- no key slots, no per-key
-// error entries -- and its set-level errors are resolved here: an unknown or unset committee
-// or a length mismatch (LSG_ERR_BAD_COMMITTEE, shape.bits_kerr), no participant (shape.bits_p 0).
-// rnd_in: the caller's randomizers, one per staged set, in place of the draws
-// (lsg_check_batch_partial_rnd; each nonzero, checked at the entry point).
+// randomizers drawn here (seed == 0: OS CSPRNG; else deterministic, for tests).  What is staged
+// and how is lsg_stage.hpp's (stage_measure, stage_fill and the meaning of scale, noscale, dedup,
+// bits_ok, rnd_in); this is the device side: the buffers sized between the two passes, the copies.
 int stage_sets(Slot* s, const lsg_set* const* sets, size_t n, uint64_t seed, bool scale,
                const std::vector<uint8_t>* noscale = nullptr, bool dedup = false, bool bits_ok = false,
                const uint64_t* rnd_in = nullptr) {
-  size_t npk = 0, msg_total = 0, n_bits_sets = 0, bit_words = 0;
-  bool any_obj = false;   // a message is an SSZ object + domain (LSG_MSG_OBJECT): k_msg_roots runs
-  bool all_index = true;  // every key names a table row: 4-byte key slots (a block body's
-                          // ~3.7M signers cross PCIe as 15 MB instead of 355 MB)
-  auto is_bits = [&](const lsg_set* q) { return bits_ok && q->pk_len == LSG_PK_BITS; };
-  // a committee list + one bitfield (LSG_PK_BITS_MULTI): staged part by part into the same arena,
-  // every part on its own word; the entry points have refused a set without a blob or with more
-  // than LSG_MAX_SET_COMMITTEES ids (one that comes through all the same is a bad committee)
-  auto is_multi = [&](const lsg_set* q) { return bits_ok && q->pk_len == LSG_PK_BITS_MULTI; };
-  size_t n_multi = 0;
-  for (size_t i = 0; i < n; i++) {
-    msg_total += msg_bytes(sets[i]->msg_len);
-    any_obj = any_obj || msg_marked(sets[i]->msg_len);
-    if (is_bits(sets[i])) {
-      n_bits_sets++;
-      bit_words += bits_words(sets[i]->n_pks);
-      continue;
-    }
-    if (is_multi(sets[i])) {
-      n_multi++;
-      bit_words += bits_words(sets[i]->n_pks) + (multi_set_ok(*sets[i]) ? multi_k(*sets[i]) : 0);
-      continue;
-    }
-    npk += sets[i]->n_pks;
-    if (sets[i]->n_pks && sets[i]->pk_len != LSG_PK_INDEX) all_index = false;
+  const StageSizes z = stage_measure(sets, n, bits_ok);
+  if (z.n_bits_sets + z.n_multi) {
+    LSG_RC(ensure_host(s, s->h_cbits, 4 * z.bit_words));
+    LSG_RC(ensure(s, s->d_cbits, 4 * z.bit_words));
   }
-  s->bits_sets.clear();
-  s->shape.bits_p.clear();
-  s->shape.bits_kerr.clear();
-  s->multi_sets.clear();
-  s->multi_parts.clear();
-  s->pk_all_bits = n > 0 && n_bits_sets + n_multi == n;
-  uint32_t* cbits = nullptr;
-  if (n_bits_sets + n_multi) {
-    s->shape.bits_p.assign(n, -1);
-    s->shape.bits_kerr.assign(n, 0);
-    s->bits_sets.reserve(n_bits_sets);
-    s->multi_sets.reserve(n_multi);
-    LSG_RC(ensure_host(s, s->h_cbits, 4 * bit_words));
-    LSG_RC(ensure(s, s->d_cbits, 4 * bit_words));
-    cbits = H_<uint32_t>(s->h_cbits);
-  }
-  size_t bw = 0;  // words of the bit arena in use
-  const size_t ks = all_index ? 4 : 96;
-  s->pk_stride = (uint32_t)ks;
-  s->n_sets = n;
-  s->n_pks = npk;
-  LSG_RC(size_inputs(s, n, npk, msg_total));
-  const size_t nn = std::max(n, (size_t)1), np = std::max(npk, (size_t)1);
-  auto al = [](size_t x) { return (x + 7) & ~(size_t)7; };
-  const size_t o_sig = 0, o_siglen = al(o_sig + 192 * nn), o_msgoff = al(o_siglen + 4 * nn),
-               o_msglen = al(o_msgoff + 4 * nn), o_mid = al(o_msglen + 4 * nn), o_pklen = al(o_mid + 4 * nn),
-               o_rnd = al(o_pklen + 4 * np), o_pk = al(o_rnd + 8 * nn), o_msg = al(o_pk + ks * np);
-  uint8_t* A = H_<uint8_t>(s->h_arena);
-  uint32_t* siglen = (uint32_t*)(A + o_siglen);
-  uint32_t* msgoff = (uint32_t*)(A + o_msgoff);
-  uint32_t* msglen = (uint32_t*)(A + o_msglen);
-  uint32_t* mid = (uint32_t*)(A + o_mid);
-  uint32_t* pklen = (uint32_t*)(A + o_pklen);
-  uint64_t* rnd = (uint64_t*)(A + o_rnd);
-  siglen[0] = msgoff[0] = msglen[0] = pklen[0] = 0;
-  rnd[0] = 0;
-  s->shape.pk_cnt.resize(n);
-  s->shape.pk_first.resize(n);
-  s->rnd.resize(n);
-  size_t mo = 0, po = 0, nm = 0;
-  bool single = npk == n && n_bits_sets + n_multi == 0;
-  // open-addressing table over the messages: slot -> distinct message id (mfirst: its set),
-  // with the message's 64-bit key beside it so that a probe compares bytes only on a key match
-  size_t cap = 0;
+  LSG_RC(size_inputs(s, n, z.npk, z.msg_total));
+  const StageLayout L = stage_layout(n, z.npk, z.pk_stride(), z.msg_total);
   static const bool dedup_on = lsg_ab_long("LSG_MSG_DEDUP", 1) != 0;
-  // a package whose sample of 256 evenly spaced sets shows no repeated message is taken as all
-  // distinct and staged without the table (the firehose of distinct gossip messages pays ~5 us,
-  // not the table's ~1 ms under the context lock); committee-shaped packages repeat at once
-  auto sample_repeats = [&]() {
-    const size_t k = std::min(n, (size_t)256), step = n / k;
-    uint64_t seen[512];
-    bool used[512] = {false};
-    for (size_t j = 0; j < k; j++) {
-      const lsg_set* q = sets[j * step];
-      const uint64_t key = msg_key(q->msg, q->msg_len);
-      for (size_t h = (size_t)key & 511;; h = (h + 1) & 511) {
-        if (!used[h]) {
-          used[h] = true;
-          seen[h] = key;
-          break;
-        }
-        if (seen[h] == key) return true;
-      }
-    }
-    return false;
-  };
-  // the message cache (package staging only: s->mc_ok): every distinct message is looked up, so
-  // the table is always built -- the sample would hide messages that repeat across packages
-  MsgCache* mc = dedup && dedup_on && s->mc_ok && s->d->mc.capacity() ? &s->d->mc : nullptr;
-  s->mc_on = mc != nullptr;
-  s->n_miss = s->mc_hits = 0;
-  s->mc_pins.clear();
-  s->mc_pend.clear();
-  bool miss_obj = false;
-  if (mc) {
-    s->mc_epoch = mc->epoch();
-    s->mc_src_off = s->plan.size();
-    s->plan.resize(s->mc_src_off + n);
-  }
-  std::vector<int32_t>& mc_store = s->mc_store;  // (miss, row) pairs, appended to the plan below
-  mc_store.clear();
-  if (dedup && dedup_on && n > 0 && (mc || (n > 1 && sample_repeats()))) {
-    cap = 16;
-    while (cap < 2 * n) cap <<= 1;
-    s->mtab.assign(cap, UINT32_MAX);
-    s->mkey.resize(cap);
-    s->mfirst.resize(n);
-  }
-  for (size_t i = 0; i < n; i++) {
-    const lsg_set* q = sets[i];
-    siglen[i] = q->sig_len;
-    uint8_t* sg = A + o_sig + 192 * i;
-    if ((q->sig_len == 96 || q->sig_len == 192) && q->sig)
-      memcpy(sg, q->sig, q->sig_len);
-    else
-      memset(sg, 0, 96);
-    uint32_t id = (uint32_t)nm;
-    uint64_t key = 0;
-    if (cap) {
-      key = msg_key(q->msg, q->msg_len);
-      for (size_t h = (size_t)key & (cap - 1);; h = (h + 1) & (cap - 1)) {
-        const uint32_t e = s->mtab[h];
-        if (e == UINT32_MAX) {
-          s->mtab[h] = id;
-          s->mkey[h] = key;
-          s->mfirst[id] = (uint32_t)i;
-          break;
-        }
-        if (s->mkey[h] != key) continue;
-        const lsg_set* r = sets[s->mfirst[e]];
-        if (r->msg_len == q->msg_len && (q->msg_len == 0 || memcmp(r->msg, q->msg, msg_bytes(q->msg_len)) == 0)) {
-          id = e;
-          break;
-        }
-      }
-    }
-    mid[i] = id;
-    if (id == nm && mc) {  // a new message: from its cache row, or staged (and hashed) as a miss
-      const uint32_t mb = msg_bytes(q->msg_len);
-      uint32_t row = 0;
-      bool hit = false, store = false;
-      if (!MsgCache::cacheable(mb) || !q->msg) {
-        mc->note_bypass();
-      } else {
-        const MsgCache::Result r = mc->lookup(key, q->msg, q->msg_len, mb, &row);
-        hit = r == MsgCache::HIT;
-        store = r == MsgCache::MISS && mc->allot(key, q->msg, q->msg_len, mb, &row);
-      }
-      if (hit) {
-        s->mc_pins.push_back(row);
-        s->mc_hits++;
-        s->plan[s->mc_src_off + nm] = (int32_t)(LSG_MC_ROW | row);
-      } else {
-        const size_t k = s->n_miss++;
-        if (store) {
-          s->mc_pend.push_back(row);
-          mc_store.push_back((int32_t)k);
-          mc_store.push_back((int32_t)row);
-        }
-        s->plan[s->mc_src_off + nm] = (int32_t)k;
-        msgoff[k] = (uint32_t)mo;
-        msglen[k] = q->msg_len;
-        miss_obj = miss_obj || msg_marked(q->msg_len);
-        if (mb) memcpy(A + o_msg + mo, q->msg, mb);
-        mo += mb;
-      }
-      nm++;
-    } else if (id == nm) {  // a new message: staged once
-      msgoff[nm] = (uint32_t)mo;
-      msglen[nm] = q->msg_len;  // (with its marker: k_msg_roots turns the payload into a 32-byte message)
-      const uint32_t mb = msg_bytes(q->msg_len);
-      if (mb) memcpy(A + o_msg + mo, q->msg, mb);
-      mo += mb;
-      nm++;
-    }
-    if (is_bits(q)) {
-      const lsg_ctx* c = s->d->c;
-      s->shape.pk_cnt[i] = 0;
-      s->shape.pk_first[i] = (uint32_t)po;
-      BitsSet b;
-      b.out = (int32_t)i;
-      uint32_t id = 0;
-      if (q->pks) memcpy(&id, q->pks, 4);
-      if (!q->pks || id >= c->cm_ok.size() || !c->cm_ok[id] || c->cm_len[id] != q->n_pks)
-        s->shape.bits_kerr[i] = LSG_ERR_BAD_COMMITTEE;
-      else
-        b = bits_stage_set(id, q->pks + 4, q->n_pks, (int32_t)i, cbits, &bw);
-      s->shape.bits_p[i] = (int32_t)b.p;
-      s->bits_sets.push_back(b);
-      continue;
-    }
-    if (is_multi(q)) {
-      const lsg_ctx* c = s->d->c;
-      s->shape.pk_cnt[i] = 0;
-      s->shape.pk_first[i] = (uint32_t)po;
-      MultiSet m;
-      m.out = (int32_t)i;
-      m.first_part = (uint32_t)s->multi_parts.size();
-      uint32_t ids[LSG_MAX_SET_COMMITTEES], lens[LSG_MAX_SET_COMMITTEES];
-      const uint32_t k = multi_set_ok(*q) ? multi_k(*q) : 0;
-      bool ok = multi_set_ok(*q) && (k > 0 || q->n_pks == 0);
-      uint64_t total = 0;
-      if (ok && k) memcpy(ids, q->pks + 4, 4 * (size_t)k);
-      for (uint32_t e = 0; e < k && ok; e++) {
-        ok = ids[e] < c->cm_ok.size() && c->cm_ok[ids[e]];
-        if (ok) total += (lens[e] = c->cm_len[ids[e]]);
-      }
-      if (!ok || total != q->n_pks)
-        s->shape.bits_kerr[i] = LSG_ERR_BAD_COMMITTEE;
-      else
-        m = multi_stage_set(ids, lens, k, q->pks + 4 + 4 * (size_t)k, q->n_pks, (int32_t)i, cbits, &bw, s->multi_parts);
-      s->shape.bits_p[i] = (int32_t)m.p;
-      s->multi_sets.push_back(m);
-      continue;
-    }
-    s->shape.pk_cnt[i] = q->n_pks;
-    s->shape.pk_first[i] = (uint32_t)po;
-    if (q->n_pks != 1) single = false;
-    if (all_index) {  // the set's indices are contiguous in the caller's buffer
-      std::fill(pklen + po, pklen + po + q->n_pks, (uint32_t)LSG_PK_INDEX);
-      if (q->pks)
-        memcpy(A + o_pk + 4 * po, q->pks, 4 * (size_t)q->n_pks);
-      else
-        memset(A + o_pk + 4 * po, 0, 4 * (size_t)q->n_pks);
-      po += q->n_pks;
-      continue;
-    }
-    for (uint32_t k = 0; k < q->n_pks; k++) {
-      pklen[po] = q->pk_len;
-      uint8_t* pd = A + o_pk + 96 * po;
-      if ((q->pk_len == 48 || q->pk_len == 96 || q->pk_len == LSG_PK_INDEX) && q->pks)
-        memcpy(pd, q->pks + (size_t)q->pk_len * k, q->pk_len);
-      else
-        memset(pd, 0, 4);
-      po++;
-    }
-  }
-  s->single_keys = single && n > 0;
-  s->n_msgs = nm;
-  s->msg_objs = mc ? miss_obj : any_obj;
-  if (mc) {  // the source words of the nm distinct messages stay; the store's pairs follow them
-    s->plan.resize(s->mc_src_off + nm);
-    s->mc_st_off = s->plan.size();
-    s->plan.insert(s->plan.end(), mc_store.begin(), mc_store.end());
-  }
-  s->msg_dedup = nm < n;
-  if (s->msg_dedup) s->msg_id.assign(mid, mid + n);
-  if (scale && n) {
-    if (rnd_in) {
-      memcpy(rnd, rnd_in, 8 * n);
-    } else if (seed == 0) {
-      if (!os_random(rnd, 8 * n)) {
-        set_err(s->d->c, "no entropy for the RLC randomizers (getrandom failed)");
-        return LSG_ERR_ENTROPY;
-      }
-      for (size_t i = 0; i < n; i++)
-        while (rnd[i] == 0)
-          if (!os_random(&rnd[i], 8)) {
-            set_err(s->d->c, "no entropy for the RLC randomizers (getrandom failed)");
-            return LSG_ERR_ENTROPY;
-          }
-    } else {
-      uint64_t sd = seed;
-      for (size_t i = 0; i < n; i++) {
-        uint64_t r;
-        do r = splitmix64(sd);
-        while (r == 0);
-        rnd[i] = r;
-      }
-    }
-  } else if (n) {
-    memset(rnd, 0, 8 * n);
-  }
-  // sets that form a group of their own are verified as they are (maybeBatch.ts:34-38: one
-  // set is a plain verify): r_i = 0 means "not scaled" to k_pk_scale and k_sig_scale
-  if (scale && noscale)
-    for (size_t i = 0; i < n; i++)
-      if ((*noscale)[i]) rnd[i] = 0;
-  memcpy(s->rnd.data(), rnd, 8 * n);
+  StageOpts o;
+  o.scale = scale;
+  o.noscale = noscale;
+  o.dedup = dedup;
+  o.dedup_on = dedup_on;
+  o.bits_ok = bits_ok;
+  o.rnd_in = rnd_in;
+  o.seed = seed;
+  const lsg_ctx* c = s->d->c;
+  const Committees cm{c->cm_len.data(), c->cm_ok.data(), c->cm_ok.size()};
+  uint8_t* A = H_<uint8_t>(s->h_arena);
+  uint32_t* cbits = H_<uint32_t>(s->h_cbits);
+  // (the message cache: package staging only, s->mc_ok)
+  const int rc = stage_fill(A, L, cbits, sets, n, z, o, s->mc_ok ? &s->d->mc : nullptr, cm, s->mtab, s->plan, *s, MsgKey(),
+                            os_random);
+  if (rc == LSG_ERR_ENTROPY) set_err(s->d->c, "no entropy for the RLC randomizers (getrandom failed)");
+  LSG_RC(rc);
   hipStream_t S = s->st[0];
   struct {
     DevBuf* d;
     size_t off, len;
-  } cp[] = {{&s->d_sig, o_sig, 192 * nn},      {&s->d_siglen, o_siglen, 4 * nn}, {&s->d_msg, o_msg, std::max(mc ? mo : msg_total, (size_t)1)},
-            {&s->d_msgoff, o_msgoff, 4 * nn}, {&s->d_msglen, o_msglen, 4 * nn}, {&s->d_pk, o_pk, ks * np},
-            {&s->d_pklen, o_pklen, 4 * np},   {&s->d_rnd, o_rnd, 8 * nn}};
+  } cp[] = {{&s->d_sig, L.sig, 192 * L.nn},      {&s->d_siglen, L.siglen, 4 * L.nn},
+            {&s->d_msg, L.msg, std::max(s->mc_on ? s->msg_used : z.msg_total, (size_t)1)},
+            {&s->d_msgoff, L.msgoff, 4 * L.nn}, {&s->d_msglen, L.msglen, 4 * L.nn}, {&s->d_pk, L.pk, L.stride * L.np},
+            {&s->d_pklen, L.pklen, 4 * L.np},   {&s->d_rnd, L.rnd, 8 * L.nn}};
   for (auto& x : cp) LSG_HIP(s, hipMemcpyAsync(x.d->p, A + x.off, x.len, hipMemcpyHostToDevice, S));
-  if (s->msg_dedup) LSG_HIP(s, hipMemcpyAsync(s->d_mid.p, A + o_mid, 4 * n, hipMemcpyHostToDevice, S));
-  if (bw) LSG_HIP(s, hipMemcpyAsync(s->d_cbits.p, cbits, 4 * bw, hipMemcpyHostToDevice, S));
+  if (s->msg_dedup) LSG_HIP(s, hipMemcpyAsync(s->d_mid.p, A + L.mid, 4 * n, hipMemcpyHostToDevice, S));
+  if (s->bit_words) LSG_HIP(s, hipMemcpyAsync(s->d_cbits.p, cbits, 4 * s->bit_words, hipMemcpyHostToDevice, S));
   return LSG_OK;
 }
 
@@ -1838,33 +1532,8 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   LSG_RC(src);
   if (dev_msgs && !flat.empty())  // (placeholders are never merged: message i is set i's)
     LSG_HIP(s, hipMemcpyAsync(s->d_msg.p, dev_msgs, 32 * flat.size(), hipMemcpyDeviceToDevice, s->st[0]));
-  // the byte keys of LSG_JOB_VALIDATE_KEYS jobs, compacted (table rows were validated when the
-  // node cached them: the flag leaves index keys alone)
-  s->n_kv = 0;
-  s->shape.kv_set.clear();
-  bool any_kv = false;
-  for (size_t k = 0; k < nj && !any_kv; k++) any_kv = (s->shape.jobs[k].flags & LSG_JOB_VALIDATE_KEYS) != 0;
-  if (any_kv) {
-    s->shape.kv_set.assign(flat.size(), 0);
-    for (size_t k = 0; k < nj; k++) {
-      if (!(s->shape.jobs[k].flags & LSG_JOB_VALIDATE_KEYS)) continue;
-      for (size_t i = s->shape.jobs[k].first; i < s->shape.jobs[k].first + s->shape.jobs[k].count; i++)
-        if (flat[i]->pk_len != LSG_PK_INDEX && flat[i]->pk_len != LSG_PK_BITS && flat[i]->pk_len != LSG_PK_BITS_MULTI &&
-            s->shape.pk_cnt[i]) {
-          s->shape.kv_set[i] = 1;
-          s->n_kv += s->shape.pk_cnt[i];
-        }
-    }
-    s->kv_off = s->plan.size();
-    s->plan.resize(s->kv_off + 2 * s->n_kv);
-    size_t q = 0;
-    for (size_t i = 0; i < flat.size(); i++)  // (staging order: a set's keys are adjacent)
-      for (uint32_t k = 0; s->shape.kv_set[i] && k < s->shape.pk_cnt[i]; k++, q++) {
-        s->plan[s->kv_off + q] = (int32_t)(s->shape.pk_first[i] + k);
-        s->plan[s->kv_off + s->n_kv + q] = (int32_t)i;
-      }
-    if (!s->n_kv) s->shape.kv_set.clear();
-  }
+  // the byte keys of LSG_JOB_VALIDATE_KEYS jobs, compacted
+  s->n_kv = plan_validate_keys(s->shape, flat.data(), flat.size(), s->plan, &s->kv_off);
   const uint64_t th1 = trace_host() ? now_ns() : 0;
   PhasePlan& A = s->phA;
   A = PhasePlan();
@@ -1888,19 +1557,7 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   A.agg_g = -1;
   if (s->msg_dedup && !s->gp.chunk_mode && s->gp.big_g >= 0 && s->sw.msg_agg && s->n_msgs <= (size_t)8192 &&
       s->sw.slp_items > 0) {
-    const Grp& g = A.groups[(size_t)s->gp.big_g];
-    std::vector<int32_t> cnt(s->n_msgs, 0), off(s->n_msgs), fill;
-    for (size_t i = g.first; i < g.first + g.len; i++) cnt[s->msg_id[i]]++;
-    int32_t tot = 0;
-    for (size_t j = 0; j < s->n_msgs; j++) {
-      off[j] = tot;
-      tot += cnt[j];
-    }
-    fill = off;
-    const size_t idx_off = s->plan.size();
-    s->plan.resize(idx_off + (size_t)tot);
-    for (size_t i = g.first; i < g.first + g.len; i++) s->plan[idx_off + (size_t)fill[s->msg_id[i]]++] = (int32_t)i;
-    s->msum = slot_seg(s, 0, off, cnt, true, idx_off, 0);
+    s->msum = plan_msg_lists(s->plan, s->msg_id.data(), s->n_msgs, A.groups[(size_t)s->gp.big_g], s->sw.seg_fold_wide);
     A.agg_g = s->gp.big_g;
     A.n_magg = s->n_msgs;
   }

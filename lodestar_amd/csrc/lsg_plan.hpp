@@ -2,9 +2,12 @@
 // groups, how Miller items and segmented reductions are planned, and how per-job verdicts and
 // the batch counters follow from group verdicts (the reference's worker.ts:30-106 rules plus
 // the phases B0 / B / C1 / C2).  Small integers in, small integers out: no device, no
-// environment, no Slot.  lsg_host.hip includes it and supplies the device side (staging,
-// launches, the `check` callable of resolve_package); tests/native/plancheck.cpp drives it on
-// the CPU.
+// environment, no Slot.  Also the two lists a package adds to the plan arena beside its groups:
+// the KeyValidate list of LSG_JOB_VALIDATE_KEYS jobs (plan_validate_keys) and the per-message set
+// lists of the package group (plan_msg_lists).  lsg_host.hip includes it and supplies the device
+// side (launches, the `check` callable of resolve_package); how sets are staged is
+// lsg_stage.hpp's, built on the types here.  tests/native/plancheck.cpp drives it on the CPU
+// (tests/native/stagecheck.cpp the two lists).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -181,6 +184,25 @@ struct Grp {
   size_t first = 0, len = 0;
   bool msm = false;
 };
+
+// Sets of group g that share a message share one Miller pair (msg_agg): per distinct message
+// (msg_id[i]: set i's, n_msgs of them) the list of g's sets that sign it, appended to the arena
+// in set order, and the segmented sum (op 0) over those lists, result j = message j's.
+inline SegPlan plan_msg_lists(std::vector<int32_t>& A, const uint32_t* msg_id, size_t n_msgs, const Grp& g,
+                              int fold_wide) {
+  std::vector<int32_t> cnt(n_msgs, 0), off(n_msgs), fill;
+  for (size_t i = g.first; i < g.first + g.len; i++) cnt[msg_id[i]]++;
+  int32_t tot = 0;
+  for (size_t j = 0; j < n_msgs; j++) {
+    off[j] = tot;
+    tot += cnt[j];
+  }
+  fill = off;
+  const size_t idx_off = A.size();
+  A.resize(idx_off + (size_t)tot);
+  for (size_t i = g.first; i < g.first + g.len; i++) A[idx_off + (size_t)fill[msg_id[i]]++] = (int32_t)i;
+  return plan_seg(A, 0, off, cnt, true, idx_off, 0, fold_wide);
+}
 
 // ---- group stages of one phase (no host synchronisation).  Groups with msm sum their
 // signatures by the bucket MSM over the unscaled points in d_rs (MSM groups must come first);
@@ -556,6 +578,39 @@ inline int32_t first_key_error(const PkgShape& sh, const int32_t* pkerr, size_t 
     }
   }
   return 0;
+}
+
+// KeyValidate of the byte keys of LSG_JOB_VALIDATE_KEYS jobs (table rows were validated when
+// the node cached them: the flag leaves index keys alone, and sets given by committee bits).  sets: the staged sets in staging order, sh.pk_cnt / pk_first theirs.  Sets
+// sh.kv_set (empty when no key is listed) and appends the list to the arena at *kv_off: the n
+// staged keys in staging order (a set's keys are adjacent), then the set of each.  Returns n.
+inline size_t plan_validate_keys(PkgShape& sh, const lsg_set* const* sets, size_t n_sets, std::vector<int32_t>& A,
+                                 size_t* kv_off) {
+  sh.kv_set.clear();
+  bool any_kv = false;
+  for (size_t k = 0; k < sh.jobs.size() && !any_kv; k++) any_kv = (sh.jobs[k].flags & LSG_JOB_VALIDATE_KEYS) != 0;
+  if (!any_kv) return 0;
+  size_t n_kv = 0;
+  sh.kv_set.assign(n_sets, 0);
+  for (const JobRec& J : sh.jobs) {
+    if (!(J.flags & LSG_JOB_VALIDATE_KEYS)) continue;
+    for (size_t i = J.first; i < J.first + J.count; i++)
+      if (sets[i]->pk_len != LSG_PK_INDEX && sets[i]->pk_len != LSG_PK_BITS && sets[i]->pk_len != LSG_PK_BITS_MULTI &&
+          sh.pk_cnt[i]) {
+        sh.kv_set[i] = 1;
+        n_kv += sh.pk_cnt[i];
+      }
+  }
+  *kv_off = A.size();
+  A.resize(*kv_off + 2 * n_kv);
+  size_t q = 0;
+  for (size_t i = 0; i < n_sets; i++)
+    for (uint32_t k = 0; sh.kv_set[i] && k < sh.pk_cnt[i]; k++, q++) {
+      A[*kv_off + q] = (int32_t)(sh.pk_first[i] + k);
+      A[*kv_off + n_kv + q] = (int32_t)i;
+    }
+  if (!n_kv) sh.kv_set.clear();
+  return n_kv;
 }
 
 // ---- committee-resident keys: a set given as committee id + participation

@@ -173,7 +173,7 @@ def test_adversarial_jobs_match_oracle(ctx):
 @pytest.mark.parametrize("agg", ["0", "1"])
 def test_shared_messages_match_oracle(ctx, ab_ctx, monkeypatch, agg):
     """Sets that sign one message (a committee's attestations) share one hash_to_G2 per
-    package (stage_sets message table, k_h2c_gather) and, with LSG_MSG_AGG=1, one Miller pair
+    package (lsg_stage.hpp MsgTable, k_h2c_gather) and, with LSG_MSG_AGG=1, one Miller pair
     (the masked sum of their scaled keys): verdicts, errors and counters stay the oracle's,
     with corrupted sets inside the shared groups and sets whose corruption gives them a
     message of their own."""
@@ -405,7 +405,7 @@ def test_sharded_verifier_gpu_backend(ctx):
 
 def _splitmix_rands(seed, n):
     """The randomizers lsg_batch_partial derives from a nonzero seed on a single-device
-    context (lsg_host.hip stage_sets: splitmix64, zero draws skipped)."""
+    context (lsg_stage.hpp draw_randomizers: splitmix64, zero draws skipped)."""
     M = (1 << 64) - 1
     s, out = seed, []
     while len(out) < n:

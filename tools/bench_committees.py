@@ -77,7 +77,7 @@ def build(ctx, blocks, validators, participation, seed=1):
 
 
 def staged_key_bytes(shape):
-    """bytes staged per package for the sets' keys, from the shapes (lsg_host.hip stage_sets,
+    """bytes staged per package for the sets' keys, from the shapes (lsg_stage.hpp stage_fill,
     lsg_plan.hpp plan_bits): by index, 4 bytes of index and a 4-byte length word per participant;
     by bits, the field's words plus 6 plan words and one pair-table word per lane pair"""
     index = sum(8 * p for _, p in shape)

@@ -14,7 +14,7 @@ for at least --seconds with --depth packages in flight and ends with every packa
 
 One JSON line per leg: sets/s, keys/s, p50 package latency, median submit_us, a MODEL of the
 bytes staged per package for the sets' keys (staged_key_bytes_model_*: not read back from the
-library but computed here from the shapes by the rules of stage_sets and plan_multi -- 8 bytes
+library but computed here from the shapes by the rules of stage_fill (lsg_stage.hpp) and plan_multi -- 8 bytes
 per key by index, the index and its length word, against the parts' arena words plus the plan
 words by committee list),
 and the aggregation kernels' time per package from lsg_last_kernel_times (k_pk_agg_seg and its
@@ -98,7 +98,7 @@ def reserve_units(shape):
 
 
 def staged_key_bytes(shape):
-    """a model of the bytes staged per package for the sets' keys, from the shapes (lsg_host.hip stage_sets,
+    """a model of the bytes staged per package for the sets' keys, from the shapes (lsg_stage.hpp stage_fill,
     lsg_plan.hpp plan_multi): by index, 4 bytes of index and a 4-byte length word per
     participant; by committee list, the words of every part with a participant plus 5 plan
     words per set, 4 per part and one pair-table word per lane pair"""
