@@ -584,6 +584,14 @@ int lsg_check_g2_lanes(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out
  * (xi C, A, B); Y_9 = 1, Y_10 = 0; elements 22, 23: B.c0 spread over both lanes as they hold it
  * (word k of lane h at 2 k + h). */
 int lsg_check_mf_lanes(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out);
+/* lsg_check_pow_lanes: the fixed-exponent power kernel with one Fp element per lane
+ * (k_fp_pow_lanes: the square roots of the signature decode and the SSWU map in large launches)
+ * on the caller's limb words: n raw elements in the pair layout in, out[i] = in[i]^e / R^(e-1)
+ * raw, for id 0: e = p - 2, 1: (p + 1) / 4, 2: (p - 3) / 4.  lsg_check_pow_pair: the pair form's
+ * power (pair_pow_plan, what the single kernels run) on the same words; the two agree word for
+ * word.  LSG_ERR_INVALID_ARG for another id.  Tests only. */
+int lsg_check_pow_lanes(lsg_ctx* ctx, int32_t id, const uint32_t* in, size_t n, uint32_t* out);
+int lsg_check_pow_pair(lsg_ctx* ctx, int32_t id, const uint32_t* in, size_t n, uint32_t* out);
 /* Parity hooks of the layer between the products and the accept / reject rules (tests only;
  * none is on the verification path).  Elements travel in the pair layout above: 14 words, limb
  * L at word 2 (L mod 7) + L / 7.  Each returns LSG_ERR_INVALID_ARG for a null pointer with a

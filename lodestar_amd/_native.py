@@ -205,7 +205,7 @@ EXPORTS = [
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
     "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums", "lsg_check_fp2_lanes", "lsg_check_g2_lanes", "lsg_check_mf_lanes",
     "lsg_check_canon", "lsg_check_fp2_roots", "lsg_check_batch_inv", "lsg_check_map_uniform",
-    "lsg_check_batch_partial_rnd",
+    "lsg_check_batch_partial_rnd", "lsg_check_pow_lanes", "lsg_check_pow_pair",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
     "lsg_object_signing_roots",
@@ -289,6 +289,8 @@ def load_library(path=LIB_PATH):
         lib.lsg_check_fp2_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_g2_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_mf_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_pow_lanes.argtypes = [vp, i32, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_pow_pair.argtypes = [vp, i32, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_canon.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_char_p, ctypes.c_char_p]
         lib.lsg_check_fp2_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_batch_inv.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
@@ -907,6 +909,17 @@ class Context:
     def check_mf_lanes(self, words):
         """lsg_check_mf_lanes: `words` = 12 x 14 u32 per item; returns 24 x 14 u32 per item (raw)."""
         return self._check_lanes("lsg_check_mf_lanes", words)
+
+    def check_pow(self, pow_id, words, lanes=True):
+        """lsg_check_pow_lanes (lanes) / lsg_check_pow_pair: `words` = 14 u32 per raw element;
+        returns 14 u32 per element, the element raised to the fixed exponent `pow_id` (raw)."""
+        n = len(words) // 14
+        assert len(words) == 14 * n
+        fn = "lsg_check_pow_lanes" if lanes else "lsg_check_pow_pair"
+        out = ctypes.create_string_buffer(4 * 14 * max(n, 1))
+        src = struct.pack(f"<{len(words)}I", *words)
+        self._check(getattr(self.lib, fn)(self.h, pow_id, src, n, out), fn)
+        return list(struct.unpack(f"<{14 * n}I", out.raw[:4 * 14 * n]))
 
     def check_canon(self, words, strings=()):
         """lsg_check_canon: `words` = 14 u32 per raw element, `strings` = 48-byte strings.  Returns

@@ -7,6 +7,13 @@
 #include <stdlib.h>
 #include <string.h>
 
+// The square roots of sig_decode and h2c_map run their powers with one element per lane
+// (k_fp_pow_lanes) from this many power operands per launch on: one per signature, two per
+// message (LSG_POW_LANES=0/1, LSG_POW_LANES_MIN=<items> in the A/B build; measured:
+// profiles/r17_powlanes_threshold.txt)
+#define LSG_POW_LANES_DEFAULT 1
+#define LSG_POW_LANES_MIN_DEFAULT 65536
+
 #ifdef LSG_AB
 // integer switch `name`, `dflt` when unset
 static inline long lsg_ab_long(const char* name, long dflt) {

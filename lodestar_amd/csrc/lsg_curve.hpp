@@ -572,7 +572,11 @@ LSG_INL bool g2_on_curve_aff(const g2a_t& a) {
 #endif
 
 // blst POINTonE2_Uncompress_Z (96 bytes).  Sets *inf for the infinity encoding.
-LSG_INL int g2_uncompress(g2a_t& out, bool& inf, const uint8_t* in) {
+// Cut at the square root (whose two powers the stage kernels of lsg_k_sig.hip run outside):
+// g2_uncompress_parse returns the final code, or LSG_UNCOMPRESS_PENDING with x, rhs = x^3 + b
+// and the sign flag for g2_uncompress_finish, which takes the root of rhs (ok: it is one).
+#define LSG_UNCOMPRESS_PENDING (-1)
+LSG_INL int g2_uncompress_parse(g2a_t& out, bool& inf, fp2_t& x, fp2_t& rhs, bool& want, const uint8_t* in) {
   uint8_t in0 = in[0];
   inf = false;
   if (!(in0 & 0x80)) return LSG_BLST_BAD_ENCODING;
@@ -591,16 +595,26 @@ LSG_INL int g2_uncompress(g2a_t& out, bool& inf, const uint8_t* in) {
   x1 = fp_mask_flags(x1);
   fp_t x0 = fp_from_be48(in + 48);
   if (!fp_canon_lt_p(x1) || !fp_canon_lt_p(x0)) return LSG_BLST_BAD_ENCODING;
-  fp2_t x = fp2_make(fp_to_mont(x0), fp_to_mont(x1));
-  fp2_t rhs = fp2_add(fp2_mul(fp2_sqr(x), x), FP2_B_G2);
-  fp2_t y;
-  if (!fp2_sqrt(y, rhs)) return LSG_BLST_POINT_NOT_ON_CURVE;
-  bool want = (in0 & 0x20) != 0;
+  x = fp2_make(fp_to_mont(x0), fp_to_mont(x1));
+  rhs = fp2_add(fp2_mul(fp2_sqr(x), x), FP2_B_G2);
+  want = (in0 & 0x20) != 0;
+  return LSG_UNCOMPRESS_PENDING;
+}
+LSG_INL int g2_uncompress_finish(g2a_t& out, const fp2_t& x, fp2_t y, bool ok, bool want) {
+  if (!ok) return LSG_BLST_POINT_NOT_ON_CURVE;
   if (fp2_lexi_largest(y) != want) y = fp2_neg(y);
   out.x = x;
   out.y = y;
   if (fp2_is_zero(x)) return LSG_BLST_POINT_NOT_IN_GROUP;
   return LSG_BLST_SUCCESS;
+}
+LSG_INL int g2_uncompress(g2a_t& out, bool& inf, const uint8_t* in) {
+  fp2_t x, rhs, y;
+  bool want;
+  int e = g2_uncompress_parse(out, inf, x, rhs, want, in);
+  if (e != LSG_UNCOMPRESS_PENDING) return e;
+  bool ok = fp2_sqrt(y, rhs);
+  return g2_uncompress_finish(out, x, y, ok, want);
 }
 
 // blst POINTonE2_Deserialize_Z for 192-byte uncompressed input

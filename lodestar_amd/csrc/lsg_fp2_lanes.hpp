@@ -114,6 +114,123 @@ LSG_PFN void lanes_mul_pass(uint32_t* r, const uint32_t* V, const uint32_t* s) {
   }
   lanes_tail(t, r);
 }
+// r = REDC(a a), each cross product once.  At step i position j of the accumulators holds column
+// i + j, so step i adds a_i a_i at position i and a_w (2 a_i) at every position w > i: 105 product
+// mads for lanes_mul_pass's 196.  Every term of column c is added at a step <= c, so the column
+// is complete when lanes_reduce_step retires it: the m sequence, and after lanes_tail the 14
+// words, are those of lanes_mul_pass(r, a, a).  Per step a column takes one product term below
+// (2^30 + 16)(2^29 + 8) < 2^59.1 and m p below 2^58: the square's bound above.
+LSG_PFN void lanes_sqr_pass(uint32_t* r, const uint32_t* a) {
+  uint32_t p[LSG_VL];
+#pragma unroll
+  for (int j = 0; j < LSG_VL; j++) p[j] = LSG_P[j];
+  int64_t t[LSG_VL];
+#pragma unroll
+  for (int j = 0; j < LSG_VL; j++) t[j] = 0;
+#pragma unroll
+  for (int i = 0; i < LSG_VL; i++) {
+    uint32_t ai = a[i], di = a[i] + a[i];
+    LSG_LANES_HIDE(ai);
+    LSG_LANES_HIDE(di);
+    t[i] += (int64_t)(int32_t)a[i] * (int32_t)ai;
+#pragma unroll
+    for (int w = i + 1; w < LSG_VL; w++) t[w] += (int64_t)(int32_t)a[w] * (int32_t)di;
+    lanes_reduce_step(t, p, i);
+  }
+  lanes_tail(t, r);
+}
+
+// ------------------------------------------------------------------ Fp with one ELEMENT per lane
+// All 14 limbs of an Fp element on one lane and no cross-lane step at all: the layout of the
+// fixed-exponent powers of k_fp_pow_lanes (lsg_k_reduce.hip), 64 elements per wave.  A product
+// is lanes_mul_pass, a square lanes_sqr_pass; the integers are the pair form's at every step.
+struct fpl_t {
+  uint32_t l[LSG_VL];
+};
+LSG_PFN fpl_t lanes_fp_hide(fpl_t a) {  // (opaque operands: see lanes_fp2_mul_v)
+#pragma unroll
+  for (int k = 0; k < LSG_VL; k++) LSG_LANES_HIDE(a.l[k]);
+  return a;
+}
+LSG_PFN fpl_t lanes_fp_mul(const fpl_t& a, const fpl_t& b) {
+  const fpl_t x = lanes_fp_hide(a), y = lanes_fp_hide(b);
+  fpl_t r;
+  lanes_mul_pass(r.l, x.l, y.l);
+  return r;
+}
+LSG_PFN fpl_t lanes_fp_sqr(const fpl_t& a) {
+  const fpl_t x = lanes_fp_hide(a);
+  fpl_t r;
+  lanes_sqr_pass(r.l, x.l);
+  return r;
+}
+LSG_PFN fpl_t lanes_fp_select(bool c, const fpl_t& a, const fpl_t& b) {
+  fpl_t r;
+#pragma unroll
+  for (int k = 0; k < LSG_VL; k++) r.l[k] = c ? a.l[k] : b.l[k];
+  return r;
+}
+// a^e by the compile-time plan LSG_POW_PLANS[id] (lsg_fp_pair.hpp): pair_pow_plan's table, windows
+// and loops, so the result is word for word pair_pow_plan(a, id).  id is wave-uniform.  The
+// table is eight named values: as an array it went to scratch (464 bytes per lane).
+#ifdef LSG_POW_IDS
+LSG_PFN fpl_t lanes_pow_plan(const fpl_t& a, int id) {
+  const pow_plan_t& P = LSG_POW_PLANS[id];
+  const fpl_t a2 = lanes_fp_sqr(a);
+  const fpl_t T0 = a;
+  const fpl_t T1 = lanes_fp_mul(T0, a2);
+  const fpl_t T2 = lanes_fp_mul(T1, a2);
+  const fpl_t T3 = lanes_fp_mul(T2, a2);
+  const fpl_t T4 = lanes_fp_mul(T3, a2);
+  const fpl_t T5 = lanes_fp_mul(T4, a2);
+  const fpl_t T6 = lanes_fp_mul(T5, a2);
+  const fpl_t T7 = lanes_fp_mul(T6, a2);
+  auto pick = [&](uint32_t k) {
+    fpl_t tv = T0;
+    tv = lanes_fp_select(k == 1u, T1, tv);
+    tv = lanes_fp_select(k == 2u, T2, tv);
+    tv = lanes_fp_select(k == 3u, T3, tv);
+    tv = lanes_fp_select(k == 4u, T4, tv);
+    tv = lanes_fp_select(k == 5u, T5, tv);
+    tv = lanes_fp_select(k == 6u, T6, tv);
+    tv = lanes_fp_select(k == 7u, T7, tv);
+    return tv;
+  };
+  fpl_t r = pick(P.step[0] & 0xffu);
+  const int n = P.n;
+#pragma unroll 1
+  for (int w = 1; w < n; w++) {
+    const uint32_t s = P.step[w];
+#pragma unroll 1
+    for (uint32_t b = s >> 8; b; b--) r = lanes_fp_sqr(r);
+    r = lanes_fp_mul(r, pick(s & 0xffu));
+  }
+#pragma unroll 1
+  for (int b = P.tail; b; b--) r = lanes_fp_sqr(r);
+  return r;
+}
+#endif
+// An fp_t in the pair item-major layout (lane_store<fp_t>) is 14 consecutive words, limb 7 h + k
+// at word 2 k + h: one lane reads or writes its element as seven 8-byte words.
+LSG_PFN fpl_t lanes_fp_load(const uint32_t* mem, size_t i) {
+  const uint32_t* w = mem + i * LSG_VL;
+  fpl_t r;
+#pragma unroll
+  for (int k = 0; k < LSG_VL / 2; k++) {
+    r.l[k] = w[2 * k];
+    r.l[LSG_VL / 2 + k] = w[2 * k + 1];
+  }
+  return r;
+}
+LSG_PFN void lanes_fp_store(uint32_t* mem, size_t i, const fpl_t& a) {
+  uint32_t* w = mem + i * LSG_VL;
+#pragma unroll
+  for (int k = 0; k < LSG_VL / 2; k++) {
+    w[2 * k] = a.l[k];
+    w[2 * k + 1] = a.l[LSG_VL / 2 + k];
+  }
+}
+
 // The operands of a lane from its own word and its partner's (odd: the lane holds c1).
 //   product: P = a0, Q = -a1 | a1        square: V = a0 + a1 | a1, s = a0 - a1 | 2 a0
 //   by xi = 1 + u: a0 - a1 | a1 + a0 (a limb of the lazy sum, no pass)

@@ -120,26 +120,51 @@ LSG_INL fp2_t sswu_tv1(const fp2_t& u) {
 LSG_INL fp2_t fp2_inv_with_norm_inv(const fp2_t& a, const fp_t& ni) {
   return fp2_t(fp_mul(a.c0, ni), fp_neg(fp_mul(a.c1, ni)));
 }
-LSG_BIGFN g2a_t map_to_curve_sswu_ni(fp2_t u, fp_t ni) {
+// Cut at the two powers (which the stage kernels of lsg_k_hash.hip run outside, one element
+// per lane): stage a up to gx1 and gx2 -- the first power takes N(gx1) --, stage b from the
+// candidate s1 to the chosen x, gx and the second power's operand c, stage c from t = c^((p-3)/4)
+// to the point.  map_to_curve_sswu_ni is the three composed.
+struct sswu_mid_t {
+  fp2_t zu2, x1, x2, gx1, gx2;
+};
+LSG_BIGFN sswu_mid_t sswu_stage_a(fp2_t u, fp_t ni) {
+  sswu_mid_t m;
   fp2_t u2 = fp2_sqr(u);
-  fp2_t zu2 = fp2_mul(SSWU_Z, u2);
-  fp2_t tv1 = fp2_add(fp2_sqr(zu2), zu2);
+  m.zu2 = fp2_mul(SSWU_Z, u2);
+  fp2_t tv1 = fp2_add(fp2_sqr(m.zu2), m.zu2);
   bool exc = fp2_is_zero(tv1);
   fp2_t x1 = fp2_mul(SSWU_MINUS_B_OVER_A, fp2_add(fp2_one(), fp2_inv_with_norm_inv(tv1, ni)));
-  x1 = fp2_select(exc, SSWU_B_OVER_ZA, x1);
-  fp2_t gx1 = fp2_add(fp2_mul(fp2_add(fp2_sqr(x1), SSWU_A), x1), SSWU_B);
-  fp2_t x2 = fp2_mul(zu2, x1);
-  fp2_t gx2 = fp2_add(fp2_mul(fp2_add(fp2_sqr(x2), SSWU_A), x2), SSWU_B);
-  bool sq1;
-  fp_t s1 = fp2_norm_sqrt_candidate(gx1, &sq1);
-  fp_t s2 = fp_mul(fp_mul(fp2_norm(zu2), fp2_norm(u)), fp_mul(s1, fp_t(SSWU_NZ_POW_P1D4)));
+  m.x1 = fp2_select(exc, SSWU_B_OVER_ZA, x1);
+  m.gx1 = fp2_add(fp2_mul(fp2_add(fp2_sqr(m.x1), SSWU_A), m.x1), SSWU_B);
+  m.x2 = fp2_mul(m.zu2, m.x1);
+  m.gx2 = fp2_add(fp2_mul(fp2_add(fp2_sqr(m.x2), SSWU_A), m.x2), SSWU_B);
+  return m;
+}
+// n = N(gx1), s1 = n^((p+1)/4); x, gx: the chosen candidate; returns c (fp2_sqrt_root_c)
+LSG_BIGFN fp_t sswu_stage_b(fp2_t& x, fp2_t& gx, const sswu_mid_t& m, const fp2_t& u, const fp_t& n, const fp_t& s1) {
+  bool sq1 = fp_is_root_of(s1, n);
+  fp_t s2 = fp_mul(fp_mul(fp2_norm(m.zu2), fp2_norm(u)), fp_mul(s1, fp_t(SSWU_NZ_POW_P1D4)));
+  x = fp2_select(sq1, m.x1, m.x2);
+  gx = fp2_select(sq1, m.gx1, m.gx2);
+  return fp2_sqrt_root_c(gx, fp_select(sq1, s1, s2));
+}
+LSG_BIGFN g2a_t sswu_stage_c(const fp2_t& u, const fp2_t& x, const fp2_t& gx, const fp_t& c, const fp_t& t) {
   g2a_t r;
-  r.x = fp2_select(sq1, x1, x2);
+  r.x = x;
   fp2_t y;
-  (void)fp2_sqrt_with_norm_root(y, fp2_select(sq1, gx1, gx2), fp_select(sq1, s1, s2));
+  (void)fp2_sqrt_root_finish(y, gx, c, t);
   if (fp2_sgn0(u) != fp2_sgn0(y)) y = fp2_neg(y);
   r.y = y;
   return r;
+}
+LSG_BIGFN g2a_t map_to_curve_sswu_ni(fp2_t u, fp_t ni) {
+  const sswu_mid_t m = sswu_stage_a(u, ni);
+  fp_t n = fp2_norm(m.gx1);
+  fp_t s1 = fp_pow_id(n, LSG_POW_SQRT);
+  fp2_t x, gx;
+  fp_t c = sswu_stage_b(x, gx, m, u, n, s1);
+  fp_t t = fp_pow_id(c, LSG_POW_SQRT34);
+  return sswu_stage_c(u, x, gx, c, t);
 }
 LSG_BIGFN g2a_t map_to_curve_sswu(fp2_t u) { return map_to_curve_sswu_ni(u, fp_inv(fp2_norm(sswu_tv1(u)))); }
 

@@ -220,6 +220,9 @@ struct Slot : Staged {
   DevBuf d_ub, d_sigaff, d_siginf, d_seterr, d_pkp, d_pkerr, d_agg, d_P, d_pinf, d_H, d_hinf, d_rs, d_rs2, d_fall,
       d_fall2;
   DevBuf d_Pp, d_zP, d_zPi, d_U, d_nrm, d_nrmi, d_Hp, d_zN, d_zNi, d_mid, d_Hm, d_hinfm;
+  // the stage state and the powers' operands / results of the one-element-per-lane square roots
+  // (lsg_launch.h PowLanes): the signature decode's and the SSWU map's (2 items per set)
+  DevBuf d_pwsig, d_pwmap;
   DevBuf binv_lv[2], binv_iv[2];
   DevBuf d_lines;
   bool rs2_ready = false;
@@ -549,7 +552,8 @@ void slot_destroy(Slot* s) {
                     &s->d_nodeF, &s->d_nodeV, &s->d_plan, &s->d_mid, &s->d_Hm, &s->d_hinfm,
                     &s->d_mmask, &s->d_PmP, &s->d_Pm, &s->d_pinfm, &s->d_errm, &s->d_xport,
                     &s->d_agga, &s->d_aggi, &s->d_aggpre, &s->d_aggtot, &s->d_aggflag, &s->d_cbits,
-                    &s->d_gplan, &s->d_gsum, &s->d_gagg, &s->d_gtmp[0], &s->d_gtmp[1], &s->d_Hx, &s->d_hinfx};
+                    &s->d_gplan, &s->d_gsum, &s->d_gagg, &s->d_gtmp[0], &s->d_gtmp[1], &s->d_Hx, &s->d_hinfx,
+                    &s->d_pwsig, &s->d_pwmap};
   for (DevBuf* b : bufs) free_dev(*b);
   for (auto& u : s->seg_tmp)
     for (DevBuf& b : u) free_dev(b);
@@ -733,6 +737,8 @@ int size_state(Slot* s, size_t n, size_t np, size_t ng, size_t n_msm, int pkg = 
              {&s->d_Hp, 4 * W_G2P * nn},
              {&s->d_zN, 4 * W_FP * nn},
              {&s->d_zNi, 4 * W_FP * nn},
+             {&s->d_pwsig, 4 * (lsgk::POW_SIG_STATE + 2 * W_FP) * nn},
+             {&s->d_pwmap, 4 * (lsgk::POW_MAP_STATE + 2 * W_FP) * 2 * nn},
              {&s->binv_lv[0], 4 * W_FP * binv_lv_words(2 * nn)},
              {&s->binv_iv[0], 4 * W_FP * binv_iv_words(2 * nn)},
              {&s->binv_lv[1], 4 * W_FP * binv_lv_words(nn)},
@@ -881,6 +887,29 @@ static bool binv_block_on() { return lsg_ab_long("LSG_BINV_BLOCK", 1) != 0; }
 // the G2 [x] chains of k_sig_subgroup and k_h2c_clear with one Fp2 component per lane
 // (lsg_fp2_lanes.hpp); LSG_FP2_LANES=0 (A/B build): the kernels' pair-form twins
 static bool fp2_lanes_on() { return lsg_ab_long("LSG_FP2_LANES", 1) != 0; }
+// The square-root powers of sig_decode and h2c_map with one element per lane (k_fp_pow_lanes)
+// from LSG_POW_LANES_MIN power operands per launch on (one per signature, two per message); below
+// it the single pair-form kernels, whose latency a lone set or a small package keeps.  The
+// default is a wave of the power kernel for every SIMD of the device (65,536 elements): with
+// fewer, a launch alone on the device lasts as long as one wave, and a lane-form power is 1.65
+// times the pair form's instructions (profiles/r17_powlanes_threshold.txt).  b: the slot's
+// scratch for `items` items of `state` words.
+lsgk::PowLanes pow_lanes(const DevBuf& b, size_t items, size_t state) {
+  lsgk::PowLanes pw;
+  if (lsg_ab_long("LSG_POW_LANES", LSG_POW_LANES_DEFAULT) == 0 || b.cap < 4 * (state + 2 * W_FP) * items) return pw;
+  pw.min_items = (int)std::max(1L, std::min(lsg_ab_long("LSG_POW_LANES_MIN", LSG_POW_LANES_MIN_DEFAULT), 0x7fffffffL));
+  pw.state = P_<uint32_t>(b);
+  pw.pa = pw.state + state * items;
+  pw.pb = pw.pa + W_FP * items;
+  return pw;
+}
+// a zero-length entry of the kernel times when the launch ran the lane-form powers: the stage
+// labels k_sig_decode and k_h2c_map cover their whole wrapper on either path
+#define KL_POW(s, pw, items)                                          \
+  do {                                                                \
+    if ((pw).on((int)(items))) KL(s, "k_fp_pow_lanes", hipSuccess);   \
+  } while (0)
+
 // G2 membership of the slot's n decoded signatures (d_sigaff, d_siginf) into d_seterr
 int launch_sig_subgroup(Slot* s, int n) {
   if (fp2_lanes_on())
@@ -964,7 +993,9 @@ size_t slp_items_max() {
 int launch_hash(Slot* s, int n, uint32_t* H, uint8_t* hinf) {
   KL(s, "k_h2c_prep", lsgk::h2c_prep(S_(s), n, P_<uint8_t>(s->d_ub), P_<uint32_t>(s->d_U), P_<uint32_t>(s->d_nrm)));
   LSG_RC(batch_inv(s, 0, "binv_sswu", P_<uint32_t>(s->d_nrm), 2 * (size_t)n, P_<uint32_t>(s->d_nrmi)));
-  KL(s, "k_h2c_map", lsgk::h2c_map(S_(s), n, P_<uint32_t>(s->d_U), P_<uint32_t>(s->d_nrmi), P_<uint32_t>(s->d_Hp)));
+  const lsgk::PowLanes pw = pow_lanes(s->d_pwmap, 2 * (size_t)n, lsgk::POW_MAP_STATE);
+  KL(s, "k_h2c_map", lsgk::h2c_map(S_(s), n, P_<uint32_t>(s->d_U), P_<uint32_t>(s->d_nrmi), P_<uint32_t>(s->d_Hp), pw));
+  KL_POW(s, pw, 2 * (size_t)n);
   if ((size_t)n <= slp_items_max()) {  // small packages: clearing + affine as one program per set
     KL(s, "k_slp_h2c", lsg_slp_h2c_clear(S_(s), n, P_<uint32_t>(s->d_Hp), H, hinf));
     return LSG_OK;
@@ -1180,8 +1211,10 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
                                      P_<uint32_t>(s->d_zP), P_<uint8_t>(s->d_pinf)));
   LSG_RC(batch_inv(s, 1, "binv_pk", P_<uint32_t>(s->d_zP), (size_t)n, P_<uint32_t>(s->d_zPi)));
   KL(s, "k_pk_affine", lsgk::pk_affine(S_(s), n, P_<uint32_t>(s->d_Pp), P_<uint32_t>(s->d_zPi), P_<uint32_t>(s->d_P)));
+  const lsgk::PowLanes pw = pow_lanes(s->d_pwsig, (size_t)n, lsgk::POW_SIG_STATE);
   KL(s, "k_sig_decode", lsgk::sig_decode(S_(s), n, P_<uint8_t>(s->d_sig), P_<uint32_t>(s->d_siglen),
-                                         P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf), P_<int32_t>(s->d_seterr)));
+                                         P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf), P_<int32_t>(s->d_seterr), pw));
+  KL_POW(s, pw, n);
   if ((size_t)n <= slp_items_max())  // small packages: one program per set (0.3 ms, not 1.3)
     KL(s, "k_slp_subgroup", lsg_slp_g2_subgroup(S_(s), n, P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
                                                 P_<int32_t>(s->d_seterr)));
@@ -3579,8 +3612,10 @@ static int sig_decode_impl(lsg_ctx* c, const uint8_t* sigs, uint32_t sig_len, si
   LSG_RC(stage_sets(s, sp.data(), n, 0, false));
   LSG_RC(size_state(s, n, 0, 1, 0));
   const int nn = (int)n;
+  const lsgk::PowLanes pw = pow_lanes(s->d_pwsig, n, lsgk::POW_SIG_STATE);
   KL(s, "k_sig_decode", lsgk::sig_decode(S_(s), nn, P_<uint8_t>(s->d_sig), P_<uint32_t>(s->d_siglen),
-                                         P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf), P_<int32_t>(s->d_seterr)));
+                                         P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf), P_<int32_t>(s->d_seterr), pw));
+  KL_POW(s, pw, nn);
   if (validate) LSG_RC(launch_sig_subgroup(s, nn));
   return LSG_OK;
 }
@@ -3923,6 +3958,32 @@ int lsg_check_fp2_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out)
 int lsg_check_g2_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) { return check_lanes(c, in, n, out, true); }
 int lsg_check_mf_lanes(lsg_ctx* c, const uint32_t* in, size_t n, uint32_t* out) {
   return check_lanes(c, in, n, out, false, true);
+}
+
+// the fixed-exponent power hooks (k_fp_pow_lanes, k_check_pow_pair): n elements in, n out
+static int check_pow(lsg_ctx* c, int32_t id, const uint32_t* in, size_t n, uint32_t* out, bool lanes) {
+  if (!c || id < 0 || id > 2 || (n && (!in || !out)) || n > 0x7fffffffull / (4 * W_FP)) return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  if (n == 0) return LSG_OK;
+  Slot* s = &c->dev[0]->util;
+  timer_reset(s);
+  LSG_RC(ensure(s, s->d_aux, 4 * W_FP * n));
+  LSG_RC(ensure(s, s->d_Fb, 4 * W_FP * n));
+  LSG_HIP(s, hipMemcpyAsync(s->d_aux.p, in, 4 * W_FP * n, hipMemcpyHostToDevice, s->st[0]));
+  if (lanes)
+    KL(s, "k_fp_pow_lanes", lsgk::fp_pow_lanes(S_(s), (int)n, id, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  else
+    KL(s, "k_check_pow_pair", lsgk::check_pow_pair(S_(s), (int)n, id, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_Fb)));
+  LSG_HIP(s, hipMemcpyAsync(out, s->d_Fb.p, 4 * W_FP * n, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  keep_times(s);
+  return LSG_OK;
+}
+int lsg_check_pow_lanes(lsg_ctx* c, int32_t id, const uint32_t* in, size_t n, uint32_t* out) {
+  return check_pow(c, id, in, n, out, true);
+}
+int lsg_check_pow_pair(lsg_ctx* c, int32_t id, const uint32_t* in, size_t n, uint32_t* out) {
+  return check_pow(c, id, in, n, out, false);
 }
 
 // the field-edge hooks (k_check_canon, k_check_from_bytes, k_check_fp2_roots, batch_inv, launch_hash)

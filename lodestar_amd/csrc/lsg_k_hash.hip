@@ -173,6 +173,45 @@ __global__ void LSG_KERNEL_ATTR_W(LSG_H2C_WAVES) k_h2c_map(int n2, const uint32_
   if ((item & 1) == 0) lane_store(Hp, item >> 1, g2_add(q, o));
 }
 
+// The same map as three stages around the two powers of the SSWU square root, which
+// k_fp_pow_lanes (lsg_k_reduce.hip) runs between them with one element per lane: pa holds a
+// power's operand and pb its result, one fp_t per item (lsg_h2c.hpp sswu_stage_a / b / c).
+//   a  up to gx1, gx2; pa = N(gx1)                                          then pb = pa^((p+1)/4)
+//   b  sq1 and s2 from pb; the chosen x, gx (into the state's x1, gx1); pa = c   then pb = pa^((p-3)/4)
+//   c  the root from c = pa and t = pb, sgn0, the isogeny, Q0 + Q1, the store
+static_assert(lane_words<sswu_mid_t>() == lsgk::POW_MAP_STATE, "layout: map stage state");
+__global__ void LSG_KERNEL_ATTR_W(LSG_H2C_WAVES) k_h2c_map_a(int n2, const uint32_t* __restrict__ U, const uint32_t* __restrict__ ninv,
+                                                             uint32_t* __restrict__ state, uint32_t* __restrict__ pa) {
+  LANE_ITEM(n2);
+  (void)lead;
+  const sswu_mid_t m = sswu_stage_a(lane_load<fp2_t>(U, item), lane_load<fp_t>(ninv, item));
+  lane_store(state, item, m);
+  lane_store(pa, item, fp2_norm(m.gx1));
+}
+__global__ void LSG_KERNEL_ATTR_W(LSG_H2C_WAVES) k_h2c_map_b(int n2, const uint32_t* __restrict__ U, uint32_t* __restrict__ state,
+                                                             uint32_t* __restrict__ pa, const uint32_t* __restrict__ pb) {
+  LANE_ITEM(n2);
+  (void)lead;
+  sswu_mid_t m = lane_load<sswu_mid_t>(state, item);
+  fp2_t x, gx;
+  const fp_t c = sswu_stage_b(x, gx, m, lane_load<fp2_t>(U, item), lane_load<fp_t>(pa, item), lane_load<fp_t>(pb, item));
+  m.x1 = x;
+  m.gx1 = gx;
+  lane_store(state, item, m);
+  lane_store(pa, item, c);
+}
+__global__ void LSG_KERNEL_ATTR_W(LSG_H2C_WAVES) k_h2c_map_c(int n2, const uint32_t* __restrict__ U, const uint32_t* __restrict__ state,
+                                                             const uint32_t* __restrict__ pa, const uint32_t* __restrict__ pb,
+                                                             uint32_t* __restrict__ Hp) {
+  LANE_ITEM(n2);  // n2 is even (k_h2c_map)
+  (void)lead;
+  const sswu_mid_t m = lane_load<sswu_mid_t>(state, item);
+  const g2p_t q = iso_map3(sswu_stage_c(lane_load<fp2_t>(U, item), m.x1, m.gx1, lane_load<fp_t>(pa, item),
+                                        lane_load<fp_t>(pb, item)));
+  const g2p_t o = quad_swap_pairs(q);
+  if ((item & 1) == 0) lane_store(Hp, item >> 1, g2_add(q, o));
+}
+
 // stage 2b: clear_cofactor in place; zN_i = N(Z) (0 at infinity) for the batched inversion.
 // The [x] chains take their base point from an LDS slot per lane and the partial sum waits in
 // the item's own slot of Hp, so the chains hold only their accumulator.
@@ -353,8 +392,19 @@ hipError_t expand_msg(hipStream_t st, int n, const uint8_t* msg, const uint32_t*
 hipError_t h2c_prep(hipStream_t st, int n, const uint8_t* ub, uint32_t* U, uint32_t* norms) {
   LSG_LAUNCH_ITEMS(k_h2c_prep, n, st, n, ub, U, norms);
 }
-hipError_t h2c_map(hipStream_t st, int n, const uint32_t* U, const uint32_t* ninv, uint32_t* Hp) {
-  LSG_LAUNCH_ITEMS(k_h2c_map, 2 * n, st, 2 * n, U, ninv, Hp);
+hipError_t h2c_map(hipStream_t st, int n, const uint32_t* U, const uint32_t* ninv, uint32_t* Hp, const PowLanes& pw) {
+  if (n <= 0) return hipSuccess;
+  const int n2 = 2 * n;
+  if (!pw.on(n2)) LSG_LAUNCH_ITEMS(k_h2c_map, n2, st, n2, U, ninv, Hp);
+  const dim3 grid(lane_blocks((size_t)n2)), block(LSG_TPB);
+  hipLaunchKernelGGL(k_h2c_map_a, grid, block, 0, st, n2, U, ninv, pw.state, pw.pa);
+  hipError_t e = fp_pow_lanes(st, n2, LSG_POW_SQRT, pw.pa, pw.pb);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_h2c_map_b, grid, block, 0, st, n2, U, pw.state, pw.pa, pw.pb);
+  e = fp_pow_lanes(st, n2, LSG_POW_SQRT34, pw.pa, pw.pb);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_h2c_map_c, grid, block, 0, st, n2, U, pw.state, pw.pa, pw.pb, Hp);
+  return hipGetLastError();
 }
 hipError_t h2c_clear(hipStream_t st, int n, uint32_t* Hp, uint32_t* zN, uint8_t* hinf, bool pair_form) {
 #ifdef LSG_FP2_LANES

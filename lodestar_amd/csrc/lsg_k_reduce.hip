@@ -480,6 +480,28 @@ __global__ void LSG_KERNEL_ATTR k_check_fp2_roots(int n, const uint32_t* __restr
   o[56 + (lead ? 0 : 1)] = lead ? f : 0u;
 }
 
+// The fixed-exponent powers of the signature decompression and the SSWU map (lsg_k_sig.hip,
+// lsg_k_hash.hip: the stage kernels around them) with one Fp element per lane
+// (lsg_fp2_lanes.hpp fpl_t): out[i] = in[i]^e for the plan LSG_POW_PLANS[id], word for word
+// pair_pow_plan's.  in / out: fp_t arrays in the pair item-major layout (lane_store<fp_t>).  No
+// LDS, no barrier, no cross-lane step; lanes beyond n leave at once.
+#ifndef LSG_POW_LANES_WAVES
+#define LSG_POW_LANES_WAVES 2
+#endif
+__global__ void LSG_KERNEL_ATTR_W(LSG_POW_LANES_WAVES) k_fp_pow_lanes(int n, int id, const uint32_t* __restrict__ in,
+                                                                      uint32_t* __restrict__ out) {
+  const size_t i = gtid();
+  if (i >= (size_t)n) return;
+  id = __builtin_amdgcn_readfirstlane(id);
+  lanes_fp_store(out, i, lanes_pow_plan(lanes_fp_load(in, i), id));
+}
+// k_check_pow_pair: the pair form's pair_pow_plan on the same arrays (the device tests' reference)
+__global__ void LSG_KERNEL_ATTR k_check_pow_pair(int n, int id, const uint32_t* __restrict__ in, uint32_t* __restrict__ out) {
+  LANE_ITEM(n);
+  (void)lead;
+  lane_store(out, item, fp_pow_id(lane_load<fp_t>(in, item), id));
+}
+
 // roofline probe: 4 independent limb-parallel Montgomery chains per pair
 __global__ void LSG_KERNEL_ATTR k_probe_fp_mul(int n, int iters, uint32_t* __restrict__ io) {
   LANE_ITEM(n);
@@ -583,6 +605,17 @@ hipError_t check_from_bytes(hipStream_t st, int n, const uint8_t* in, uint32_t* 
 }
 hipError_t check_fp2_roots(hipStream_t st, int n, const uint32_t* in, uint32_t* out) {
   LSG_LAUNCH_ITEMS(k_check_fp2_roots, n, st, n, in, out);
+}
+hipError_t fp_pow_lanes(hipStream_t st, int n, int id, const uint32_t* in, uint32_t* out) {
+  if (n <= 0) return hipSuccess;
+  if (id < 0 || id > 2) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(k_fp_pow_lanes, dim3((unsigned)(((size_t)n + LSG_TPB - 1) / LSG_TPB)), dim3(LSG_TPB), 0, st, n, id,
+                     in, out);
+  return hipGetLastError();
+}
+hipError_t check_pow_pair(hipStream_t st, int n, int id, const uint32_t* in, uint32_t* out) {
+  if (id < 0 || id > 2) return hipErrorInvalidValue;
+  LSG_LAUNCH_ITEMS(k_check_pow_pair, n, st, n, id, in, out);
 }
 hipError_t probe_fp_mul(hipStream_t st, int items, int iters, uint32_t* io) {
   LSG_LAUNCH_ITEMS(k_probe_fp_mul, items, st, items, iters, io);

@@ -27,6 +27,86 @@ __global__ void LSG_KERNEL_ATTR k_sig_decode(int n, const uint8_t* __restrict__ 
   }
 }
 
+// The same decode as three stages around the two powers of the square root, which
+// k_fp_pow_lanes (lsg_k_reduce.hip) runs between them with one element per lane: pa holds a
+// power's operand and pb its result, one fp_t per item.
+//   a  parse; rhs = x^3 + b; pa = N(rhs)                                 then pb = pa^((p+1)/4)
+//   b  ok = (pb^2 == pa); pa = c (fp2_sqrt_root_c)                       then pb = pa^((p-3)/4)
+//   c  the root from c = pa and t = pb, the curve check, the sign, the store
+// Only a well-formed 96-byte encoding reaches the root (state word bit 0): every other item --
+// wrong size, flag errors, infinity, the 192-byte form -- is finished by stage a with the code and
+// precedence of k_sig_decode, sends 0 through the powers and is skipped by b and c.
+struct sigdec_state_t {
+  fp2_t x, rhs;
+  uint32_t w;  // bit 0: at the root, 1: the sign flag, 2: N(rhs) is a square (stage b)
+};
+static_assert(lane_words<sigdec_state_t>() == lsgk::POW_SIG_STATE, "layout: decode stage state");
+__global__ void LSG_KERNEL_ATTR k_sig_decode_a(int n, const uint8_t* __restrict__ sig, const uint32_t* __restrict__ sig_len,
+                                               uint32_t* __restrict__ sig_aff, uint8_t* __restrict__ inf,
+                                               int32_t* __restrict__ err, uint32_t* __restrict__ state,
+                                               uint32_t* __restrict__ pa) {
+  LANE_ITEM(n);
+  uint32_t len = sig_len[item];
+  g2a_t p;
+  p.x = fp2_zero();
+  p.y = fp2_zero();
+  sigdec_state_t s;
+  s.x = fp2_zero();
+  s.rhs = fp2_zero();
+  s.w = 0;
+  fp_t pw = fp_zero();
+  bool is_inf = false;
+  int e;
+  if (len == 96) {
+    bool want = false;
+    e = g2_uncompress_parse(p, is_inf, s.x, s.rhs, want, sig + 192 * item);
+    if (e == LSG_UNCOMPRESS_PENDING) {
+      s.w = 1u | (want ? 2u : 0u);
+      pw = fp2_norm(s.rhs);
+    }
+  } else if (len == 192)
+    e = g2_deserialize_uncompressed(p, is_inf, sig + 192 * item);
+  else
+    e = LSG_BLST_INVALID_SIZE;
+  lane_store(state, item, s);
+  lane_store(pa, item, pw);
+  if (e == LSG_UNCOMPRESS_PENDING) return;
+  lane_store(sig_aff, item, p);
+  if (lead) {
+    inf[item] = is_inf ? 1 : 0;
+    err[item] = e;
+  }
+}
+__global__ void LSG_KERNEL_ATTR k_sig_decode_b(int n, uint32_t* __restrict__ state, uint32_t* __restrict__ pa,
+                                               const uint32_t* __restrict__ pb) {
+  LANE_ITEM(n);
+  (void)lead;
+  sigdec_state_t s = lane_load<sigdec_state_t>(state, item);
+  if (!(s.w & 1u)) return;
+  const fp_t cand = lane_load<fp_t>(pb, item);
+  if (fp_is_root_of(cand, lane_load<fp_t>(pa, item))) s.w |= 4u;
+  lane_store(pa, item, fp2_sqrt_root_c(s.rhs, cand));
+  lane_store(state, item, s);
+}
+__global__ void LSG_KERNEL_ATTR k_sig_decode_c(int n, const uint32_t* __restrict__ state, const uint32_t* __restrict__ pa,
+                                               const uint32_t* __restrict__ pb, uint32_t* __restrict__ sig_aff,
+                                               uint8_t* __restrict__ inf, int32_t* __restrict__ err) {
+  LANE_ITEM(n);
+  const sigdec_state_t s = lane_load<sigdec_state_t>(state, item);
+  if (!(s.w & 1u)) return;
+  fp2_t y;
+  const bool root = fp2_sqrt_root_finish(y, s.rhs, lane_load<fp_t>(pa, item), lane_load<fp_t>(pb, item));
+  g2a_t p;
+  p.x = fp2_zero();
+  p.y = fp2_zero();
+  const int e = g2_uncompress_finish(p, s.x, y, (s.w & 4u) != 0 && root, (s.w & 2u) != 0);
+  lane_store(sig_aff, item, p);
+  if (lead) {
+    inf[item] = 0;
+    err[item] = e;
+  }
+}
+
 // psi(P) == [x]P (Jacobian doubling chain, complete additions); the chain's base point waits
 // in an LDS slot per lane, re-read at the five additions, instead of in spilled registers
 // F: the layout the chain runs in and the point is parked in (chain_fp2_t: one Fp2 component
@@ -208,8 +288,18 @@ __global__ void LSG_KERNEL_ATTR k_sign(int n, const uint8_t* __restrict__ sks, c
 
 namespace lsgk {
 hipError_t sig_decode(hipStream_t st, int n, const uint8_t* sig, const uint32_t* sig_len, uint32_t* sig_aff,
-                      uint8_t* inf, int32_t* err) {
-  LSG_LAUNCH_ITEMS(k_sig_decode, n, st, n, sig, sig_len, sig_aff, inf, err);
+                      uint8_t* inf, int32_t* err, const PowLanes& pw) {
+  if (n <= 0) return hipSuccess;
+  if (!pw.on(n)) LSG_LAUNCH_ITEMS(k_sig_decode, n, st, n, sig, sig_len, sig_aff, inf, err);
+  const dim3 grid(lane_blocks((size_t)n)), block(LSG_TPB);
+  hipLaunchKernelGGL(k_sig_decode_a, grid, block, 0, st, n, sig, sig_len, sig_aff, inf, err, pw.state, pw.pa);
+  hipError_t e = fp_pow_lanes(st, n, LSG_POW_SQRT, pw.pa, pw.pb);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_sig_decode_b, grid, block, 0, st, n, pw.state, pw.pa, pw.pb);
+  e = fp_pow_lanes(st, n, LSG_POW_SQRT34, pw.pa, pw.pb);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_sig_decode_c, grid, block, 0, st, n, pw.state, pw.pa, pw.pb, sig_aff, inf, err);
+  return hipGetLastError();
 }
 hipError_t sig_subgroup(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, int32_t* err, bool pair_form) {
 #ifdef LSG_FP2_LANES

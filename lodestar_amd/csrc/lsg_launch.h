@@ -12,11 +12,27 @@
 constexpr uint32_t LSG_MC_ROW = 0x80000000u;  // a message-cache source word that names an arena row
 
 namespace lsgk {
+// The one-element-per-lane powers of the signature decompression and the SSWU map (k_fp_pow_lanes,
+// lsg_k_reduce.hip; lsg_fp2_lanes.hpp): at `min_items` power operands or more (0: never) sig_decode and
+// h2c_map run as three pair-form stage kernels around two launches of the power kernel; below it
+// as their single kernels, whose latency a lone set or a small package keeps (a dependent
+// lane-form product is ~1.5 times the pair form's).  state / pa / pb: the caller's scratch of
+// POW_SIG_STATE (POW_MAP_STATE) words per item and W_FP words per item each for the powers'
+// operands and results.  sig_decode has n operands per power, h2c_map 2 n.
+struct PowLanes {
+  int min_items = 0;
+  uint32_t* state = nullptr;
+  uint32_t* pa = nullptr;
+  uint32_t* pb = nullptr;
+  bool on(int items) const { return min_items > 0 && items >= min_items && state && pa && pb; }
+};
+constexpr size_t POW_SIG_STATE = 4 * 14 + 2, POW_MAP_STATE = 10 * 14;  // words per item
 // ---- hash_to_G2 (lsg_k_hash.hip)                                      SURVEY 8a M3
 hipError_t expand_msg(hipStream_t st, int n, const uint8_t* msg, const uint32_t* off, const uint32_t* len,
                       const uint8_t* dst, uint32_t dst_len, uint8_t* ub);
 hipError_t h2c_prep(hipStream_t st, int n, const uint8_t* ub, uint32_t* U, uint32_t* norms);
-hipError_t h2c_map(hipStream_t st, int n, const uint32_t* U, const uint32_t* ninv, uint32_t* Hp);
+hipError_t h2c_map(hipStream_t st, int n, const uint32_t* U, const uint32_t* ninv, uint32_t* Hp,
+                   const PowLanes& pw = PowLanes());
 // pair_form: the kernel with its [x] chains in the pair layout (A/B; lsg_fp2_lanes.hpp)
 hipError_t h2c_clear(hipStream_t st, int n, uint32_t* Hp, uint32_t* zN, uint8_t* hinf, bool pair_form = false);
 hipError_t h2c_gather(hipStream_t st, int n, const uint32_t* mid, const uint32_t* Hm, const uint8_t* hinfm, uint32_t* H,
@@ -48,7 +64,7 @@ hipError_t msg_roots(hipStream_t st, int n, uint8_t* msg, const uint32_t* off, u
 
 // ---- signatures (lsg_k_sig.hip)                                       SURVEY 8a M2, M4
 hipError_t sig_decode(hipStream_t st, int n, const uint8_t* sig, const uint32_t* sig_len, uint32_t* sig_aff,
-                      uint8_t* inf, int32_t* err);
+                      uint8_t* inf, int32_t* err, const PowLanes& pw = PowLanes());
 hipError_t sig_subgroup(hipStream_t st, int n, const uint32_t* sig_aff, const uint8_t* inf, int32_t* err,
                         bool pair_form = false);
 // out[i] = the projective point set i adds to its group's RLC signature sum: the identity
@@ -177,6 +193,10 @@ hipError_t blobs_to_fp12(hipStream_t st, int n, const uint8_t* blobs, uint32_t* 
 hipError_t fp12_to_canon(hipStream_t st, int n, const uint32_t* in, uint8_t* out576);
 // out576 = in576^r (canonical Fp12 blobs, one item): an exported partial's RLC randomizer
 hipError_t fp12_pow_u64(hipStream_t st, const uint8_t* in576, uint64_t r, uint8_t* out576);
+// out[i] = in[i]^e, e = the fixed exponent `id` (0: p - 2, 1: (p + 1) / 4, 2: (p - 3) / 4), n fp_t in the pair
+// item-major layout: one element per lane (k_fp_pow_lanes) / the pair form's pair_pow_plan
+hipError_t fp_pow_lanes(hipStream_t st, int n, int id, const uint32_t* in, uint32_t* out);
+hipError_t check_pow_pair(hipStream_t st, int n, int id, const uint32_t* in, uint32_t* out);
 hipError_t probe_fp_mul(hipStream_t st, int items, int iters, uint32_t* io);
 hipError_t check_fp2_mul(hipStream_t st, int n, const uint32_t* in, uint32_t* out);
 hipError_t check_fp_sqr(hipStream_t st, int n, const uint32_t* in, uint32_t* out);

@@ -366,24 +366,34 @@ LSG_INL bool fp2_lexi_largest(const fp2_t& y) {
 //   c non-square:  root = (a1 t / 2, -c t)
 // Any square root s of n works (the two cases cover both signs).  Returns false when a is
 // not a square.  Callers fix the root's sign afterwards.
+// The two powers can run outside the function (k_fp_pow_lanes: one element per lane, the stage
+// kernels of lsg_k_sig.hip and lsg_k_hash.hip), so each stage is cut at its power: the pieces
+// composed here are the function the host build and the single kernels run.
 // Stage 1: the norm's candidate root s = n^((p+1)/4); *is_sq = (s^2 == n).
+LSG_INL bool fp_is_root_of(const fp_t& s, const fp_t& n) { return fp_eq(fp_sqr(s), n); }
 LSG_INL fp_t fp2_norm_sqrt_candidate(const fp2_t& a, bool* is_sq) {
   fp_t n = fp2_norm(a);
   fp_t s = fp_pow_id(n, LSG_POW_SQRT);
-  *is_sq = fp_eq(fp_sqr(s), n);
+  *is_sq = fp_is_root_of(s, n);
   return s;
 }
-// Stage 2: the root of a from a square root s of N(a).
-LSG_BIGFN bool fp2_sqrt_with_norm_root(fp2_t& out, fp2_t a, fp_t s) {
+// Stage 2: the root of a from a square root s of N(a): c, then t = c^((p-3)/4), then the root.
+LSG_INL fp_t fp2_sqrt_root_c(const fp2_t& a, const fp_t& s) {
   fp_t c = fp_mul(fp_add(a.c0, s), fp_t(FP_HALF));
-  c = fp_select(fp_is_zero(c), a.c0, c);
-  fp_t t = fp_pow_id(c, LSG_POW_SQRT34);
+  return fp_select(fp_is_zero(c), a.c0, c);
+}
+LSG_BIGFN bool fp2_sqrt_root_finish(fp2_t& out, fp2_t a, fp_t c, fp_t t) {
   fp_t ct = fp_mul(c, t);
   bool c_sq = fp_eq(fp_mul(ct, t), fp_one()) || fp_is_zero(c);
   fp_t h = fp_mul(fp_mul(a.c1, t), fp_t(FP_HALF));
   fp2_t r = c_sq ? fp2_t(ct, h) : fp2_t(h, fp_neg(ct));
   out = r;
   return fp2_eq(fp2_sqr(r), a);
+}
+LSG_BIGFN bool fp2_sqrt_with_norm_root(fp2_t& out, fp2_t a, fp_t s) {
+  fp_t c = fp2_sqrt_root_c(a, s);
+  fp_t t = fp_pow_id(c, LSG_POW_SQRT34);
+  return fp2_sqrt_root_finish(out, a, c, t);
 }
 LSG_BIGFN bool fp2_sqrt(fp2_t& out, fp2_t a) {
   bool ok;
