@@ -112,8 +112,10 @@ extern "C" {
 /* or'ed into lsg_set.msg_len: msg points at an SSZ-serialized object followed by its 32-byte
  * domain; the message signed is computeSigningRoot(object, domain)
  * (state-transition/src/util/signingRoot.ts:7-13), computed on the device as the package's first
- * stage (k_msg_roots).  The payload length msg_len & ~LSG_MSG_OBJECT selects the
- * kind:
+ * stage (k_msg_roots).  A marked msg_len is read in three fields: bit 31 the
+ * marker, bits 24..30 a kind tag (LSG_MSG_KIND_MASK), bits 0..23 the payload length (object +
+ * domain).  An unmarked length is a byte count in all its bits.  With tag 0 the payload length
+ * selects the kind:
  *    40  uint64 (Slot, Epoch: randao reveal, selection proof)
  *    48  two uint64 fields (phase0.VoluntaryExit; altair.SyncAggregatorSelectionData)
  *    64  Root (any object whose hashTreeRoot the caller has: block proposer, sync committee)
@@ -121,6 +123,20 @@ extern "C" {
  *   120  phase0.DepositMessage (pubkey 48, withdrawalCredentials 32, amount u64)
  *   144  phase0.BeaconBlockHeader (slot, proposerIndex, parentRoot, stateRoot, bodyRoot)
  *   160  phase0.AttestationData (slot, index, beaconBlockRoot, source, target)
+ *   296  altair.ContributionAndProof (aggregatorIndex u64, contribution 160, selectionProof 96)
+ * A non-zero tag names a variable-size kind, whose root k_msg_roots_var computes with one 64-lane
+ * workgroup per message:
+ *   LSG_MSG_KIND_AGG_PROOF          phase0.AggregateAndProof (Attestation with Bitlist[2048]):
+ *                                   object 337..593 bytes
+ *   LSG_MSG_KIND_AGG_PROOF_ELECTRA  EIP-7549's AggregateAndProof (Attestation {aggregation_bits:
+ *                                   Bitlist[131072], data, signature, committee_bits:
+ *                                   Bitvector[64]}): object 345..16,729 bytes
+ * serialized as aggregatorIndex [0,8), offset 108 [8,12), selectionProof [12,108), inner offset
+ * [108,112) (228, Electra 236), AttestationData [112,240), signature [240,336), Electra's
+ * committee_bits [336,344), then the bitlist with its delimiter bit (1..257 bytes, Electra
+ * 1..16,385).  Wrong offsets, a zero last byte, more bits than the limit, a length outside the
+ * range or another tag are caller bugs as a bad tag-0 length is.  These payloads exceed the
+ * message cache's 192 bytes and are counted as `bypassed`.
  * Such a set behaves exactly as the same set with msg = the 32-byte signing root and msg_len = 32:
  * verdicts, error codes and their precedence, the batch counters and the exported partial.
  * Honoured wherever sets are staged with a message -- lsg_submit_jobs / lsg_wait_jobs /
@@ -136,6 +152,10 @@ extern "C" {
  * lsg_reserve's max_msg_bytes.  A package with no marked set stages, allocates and launches
  * exactly what it did without the form. */
 #define LSG_MSG_OBJECT 0x80000000u
+#define LSG_MSG_KIND_SHIFT 24
+#define LSG_MSG_KIND_MASK 0x7f000000u
+#define LSG_MSG_KIND_AGG_PROOF 1u
+#define LSG_MSG_KIND_AGG_PROOF_ELECTRA 2u
 
 /* ---- job verdicts (WorkResult<boolean>, multithread/types.ts:21-24) */
 #define LSG_INVALID 0 /* {code: success, result: false} */
@@ -507,12 +527,18 @@ int lsg_attestation_signing_roots(lsg_ctx* ctx, const uint8_t* data128, size_t n
  * GENESIS_FORK_VERSION, ZERO_HASH) is one constant per network. */
 int lsg_deposit_signing_roots(lsg_ctx* ctx, const uint8_t* msgs88, size_t n, const uint8_t* domain32,
                               uint32_t domain_stride, uint8_t* out32);
-/* Any object kind of LSG_MSG_OBJECT by its serialized length: objs = n objects of obj_len bytes
- * each, obj_len one of 8, 16, 32, 76, 88, 112, 128 (another length: LSG_ERR_INVALID_ARG).  The
+/* Any tag-0 object kind of LSG_MSG_OBJECT by its serialized length: objs = n objects of obj_len
+ * bytes each, obj_len one of 8, 16, 32, 76, 88, 112, 128, 264 (another length: LSG_ERR_INVALID_ARG).  The
  * roots are those a package computes for marked sets (one dispatcher, lsg_ssz.hpp); for 32, 128
  * and 88 they equal the three calls above. */
 int lsg_object_signing_roots(lsg_ctx* ctx, const uint8_t* objs, uint32_t obj_len, size_t n, const uint8_t* domain32,
                              uint32_t domain_stride, uint8_t* out32);
+/* The variable-size kinds: n objects of one kind tag (LSG_MSG_KIND_AGG_PROOF*), object i the bytes
+ * objs[offsets[i] .. offsets[i + 1]) (offsets: n + 1 entries, offsets[0] = 0).  Runs k_msg_roots_var,
+ * the kernel a package runs for tagged sets.  Kind 0, an unknown kind or a malformed object:
+ * LSG_ERR_INVALID_ARG. */
+int lsg_object_signing_roots_var(lsg_ctx* ctx, uint32_t kind, const uint8_t* objs, const uint32_t* offsets, size_t n,
+                                 const uint8_t* domain32, uint32_t domain_stride, uint8_t* out32);
 
 /* processDeposit.ts:47-66 for n deposits in one device pass, synchronous, any n.  data184 = n
  * SSZ-serialized DepositData (184 bytes each: pubkey 48, withdrawalCredentials 32, amount u64,

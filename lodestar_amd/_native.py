@@ -43,6 +43,10 @@ LSG_PK_BITS = 8  # lsg_set.pk_len for keys named by committee id + participation
 LSG_PK_BITS_MULTI = 12  # lsg_set.pk_len for keys named by a committee list + one bitfield over them
 LSG_MAX_SET_COMMITTEES = 64
 LSG_MSG_OBJECT = 0x80000000  # or'ed into lsg_set.msg_len: msg is an SSZ object + its 32-byte domain
+LSG_MSG_KIND_SHIFT = 24  # bits 24..30 of a marked msg_len: the kind tag (0: the kind goes by the payload length)
+LSG_MSG_KIND_MASK = 0x7f000000
+LSG_MSG_KIND_AGG_PROOF = 1  # phase0.AggregateAndProof
+LSG_MSG_KIND_AGG_PROOF_ELECTRA = 2  # EIP-7549's AggregateAndProof
 
 
 def error_message(code):
@@ -137,12 +141,19 @@ class MsgObject:
     domain (lsg_set.msg_len | LSG_MSG_OBJECT): the signing root computeSigningRoot(obj, domain)
     is computed on the device as the package's first stage.  The object's length selects its
     kind: 8 (uint64), 16 (two uint64 fields), 32 (Root), 76 (BLSToExecutionChange), 88
-    (DepositMessage), 112 (BeaconBlockHeader), 128 (AttestationData); the library answers
-    another length with LSG_ERR_INVALID_ARG.  Accepted wherever a set's message goes."""
+    (DepositMessage), 112 (BeaconBlockHeader), 128 (AttestationData), 264
+    (ContributionAndProof); the library answers another length with LSG_ERR_INVALID_ARG.
+    `kind` names a variable-size kind instead (LSG_MSG_KIND_AGG_PROOF,
+    LSG_MSG_KIND_AGG_PROOF_ELECTRA: a serialized AggregateAndProof); it travels in bits 24..30
+    of the length word, and a malformed object is LSG_ERR_INVALID_ARG as well.  Accepted
+    wherever a set's message goes."""
 
-    def __init__(self, obj, domain):
+    def __init__(self, obj, domain, kind=0):
         self.obj = bytes(obj)
         self.domain = bytes(domain)
+        self.kind = int(kind)
+        if not 0 <= self.kind < 128:
+            raise ValueError("kind tag out of range")
 
     def __len__(self):
         return len(self.obj) + len(self.domain)
@@ -155,7 +166,9 @@ def _msg_form(msg):
     """(bytes, lsg_set.msg_len) of a set's message: plain bytes or a MsgObject"""
     if isinstance(msg, MsgObject):
         b = msg.tobytes()
-        return b, len(b) | LSG_MSG_OBJECT
+        if len(b) >> LSG_MSG_KIND_SHIFT:
+            raise ValueError("object payload too long")
+        return b, len(b) | LSG_MSG_OBJECT | (msg.kind << LSG_MSG_KIND_SHIFT)
     return msg, len(msg)
 
 
@@ -208,7 +221,7 @@ EXPORTS = [
     "lsg_check_batch_partial_rnd", "lsg_check_pow_lanes", "lsg_check_pow_pair",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
-    "lsg_object_signing_roots",
+    "lsg_object_signing_roots", "lsg_object_signing_roots_var",
     "lsg_submit_jobs_grouped", "lsg_wait_jobs_grouped",
     "lsg_msg_cache_set", "lsg_msg_cache_clear", "lsg_msg_cache_get_stats",
 ]
@@ -275,6 +288,8 @@ def load_library(path=LIB_PATH):
         lib.lsg_attestation_signing_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
         lib.lsg_deposit_signing_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
         lib.lsg_object_signing_roots.argtypes = [vp, ctypes.c_char_p, u32, sz, ctypes.c_char_p, u32, ctypes.c_char_p]
+        lib.lsg_object_signing_roots_var.argtypes = [vp, u32, ctypes.c_char_p, ctypes.POINTER(u32), sz, ctypes.c_char_p,
+                                                     u32, ctypes.c_char_p]
         lib.lsg_verify_deposits.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, u64, ctypes.c_char_p, pi32]
         lib.lsg_aggregate_signatures.argtypes = [vp, ctypes.c_char_p, u32, ctypes.POINTER(u32), sz,
                                                  ctypes.c_char_p, pi32]
@@ -729,7 +744,7 @@ class Context:
 
     def object_signing_roots(self, objs, domains):
         """computeSigningRoot of SSZ-serialized objects of one kind, selected by their common
-        length as for MsgObject (8, 16, 32, 76, 88, 112 or 128 bytes): the roots a package
+        length as for MsgObject (8, 16, 32, 76, 88, 112, 128 or 264 bytes): the roots a package
         computes for MsgObject messages.  `domains` is one 32-byte domain or a list."""
         n = len(objs)
         if n == 0:
@@ -745,6 +760,27 @@ class Context:
         out = ctypes.create_string_buffer(32 * n)
         self._check(self.lib.lsg_object_signing_roots(self.h, b"".join(objs), size, n, dom, stride, out),
                     "lsg_object_signing_roots")
+        raw = out.raw
+        return [raw[32 * i:32 * i + 32] for i in range(n)]
+
+    def object_signing_roots_var(self, kind, objs, domains):
+        """computeSigningRoot of serialized objects of one variable-size kind
+        (LSG_MSG_KIND_AGG_PROOF, LSG_MSG_KIND_AGG_PROOF_ELECTRA), each of its own length: the
+        roots a package computes for MsgObject(..., kind=kind) messages, by the same kernel
+        (k_msg_roots_var).  `domains` is one 32-byte domain or a list."""
+        n = len(objs)
+        if isinstance(domains, (bytes, bytearray)):
+            dom, stride = bytes(domains), 0
+        else:
+            assert len(domains) == n
+            dom, stride = b"".join(domains), 32
+        assert len(dom) == (32 if stride == 0 else 32 * n)
+        offs = (ctypes.c_uint32 * (n + 1))()
+        for i, o in enumerate(objs):
+            offs[i + 1] = offs[i] + len(o)
+        out = ctypes.create_string_buffer(32 * max(n, 1))
+        self._check(self.lib.lsg_object_signing_roots_var(self.h, kind, b"".join(objs), offs, n, dom, stride, out),
+                    "lsg_object_signing_roots_var")
         raw = out.raw
         return [raw[32 * i:32 * i + 32] for i in range(n)]
 

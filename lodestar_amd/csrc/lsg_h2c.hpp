@@ -8,7 +8,12 @@
 #include "lsg_curve.hpp"
 
 // SHA-256 (SHA_K, sha256_compress, be_words_to_bytes) and the SSZ signing roots built on it
+// (the variable-size kinds call their node hash instead of inlining it thirty times)
+#define LSG_SSZ_CALL __device__ __noinline__
 #include "lsg_ssz.hpp"
+#ifdef LSG_SSZ_CALL_DEFAULTED
+#error "lsg_ssz.hpp was included before lsg_h2c.hpp: its functions are the host program's, not the device's"
+#endif
 
 // Streaming SHA-256 over bytes (messages here are < 2^32 bits).
 struct sha256_ctx {

@@ -1268,6 +1268,9 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
       if (s->msg_objs)
         KL(s, "k_msg_roots", lsgk::msg_roots(S_(s), nx, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
                                              P_<uint32_t>(s->d_msglen)));
+      if (s->msg_vars)
+        KL(s, "k_msg_roots_var", lsgk::msg_roots_var(S_(s), nx, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
+                                                     P_<uint32_t>(s->d_msglen), nullptr));
       KL(s, "k_expand_msg", lsgk::expand_msg(S_(s), nx, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
                                              P_<uint32_t>(s->d_msglen), P_<uint8_t>(s->d_dst), DST_POP_LEN,
                                              P_<uint8_t>(s->d_ub)));
@@ -1289,6 +1292,9 @@ int launch_set_stages(Slot* s, const SegPlan* pkagg, const PhasePlan& Ph, uint32
     if (s->msg_objs)  // LSG_MSG_OBJECT messages: object + domain -> the 32-byte signing root, in place
       KL(s, "k_msg_roots", lsgk::msg_roots(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
                                            P_<uint32_t>(s->d_msglen)));
+    if (s->msg_vars)  // tagged messages (AggregateAndProof): one workgroup each, likewise in place
+      KL(s, "k_msg_roots_var", lsgk::msg_roots_var(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
+                                                   P_<uint32_t>(s->d_msglen), nullptr));
     KL(s, "k_expand_msg", lsgk::expand_msg(S_(s), nm, P_<uint8_t>(s->d_msg), P_<uint32_t>(s->d_msgoff),
                                            P_<uint32_t>(s->d_msglen), P_<uint8_t>(s->d_dst), DST_POP_LEN,
                                            P_<uint8_t>(s->d_ub)));
@@ -3745,6 +3751,53 @@ int lsg_deposit_signing_roots(lsg_ctx* c, const uint8_t* msgs88, size_t n, const
 int lsg_object_signing_roots(lsg_ctx* c, const uint8_t* objs, uint32_t obj_len, size_t n, const uint8_t* domain32,
                              uint32_t domain_stride, uint8_t* out32) {
   return signing_roots(c, 3, objs, n, domain32, domain_stride, out32, obj_len);
+}
+
+// The variable-size kinds through k_msg_roots_var, the kernel a package runs for tagged sets:
+// the payloads object || domain are laid out back to back as a package's messages are, with
+// their offsets and tagged length words; the roots come back in a list of their own.
+int lsg_object_signing_roots_var(lsg_ctx* c, uint32_t kind, const uint8_t* objs, const uint32_t* offsets, size_t n,
+                                 const uint8_t* domain, uint32_t dstride, uint8_t* out32) {
+  if (!c || !domain || (dstride != 0 && dstride != 32) || (n && (!objs || !offsets || !out32)) || n > 0x7fffffffull ||
+      (kind != LSG_MSG_KIND_AGG_PROOF && kind != LSG_MSG_KIND_AGG_PROOF_ELECTRA))
+    return LSG_ERR_INVALID_ARG;
+  if (n && offsets[0] != 0) return LSG_ERR_INVALID_ARG;
+  uint64_t total = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (offsets[i + 1] < offsets[i] || !msg_var_ok(kind, objs + offsets[i], offsets[i + 1] - offsets[i]))
+      return LSG_ERR_INVALID_ARG;
+    total += (uint64_t)(offsets[i + 1] - offsets[i]) + 32;
+  }
+  if (total > 0xffffffffull) return LSG_ERR_INVALID_ARG;  // (staged offsets are 32-bit)
+  LSG_ENTER(c);
+  Dev* d = c->dev[0];
+  Slot* s = &d->util;
+  timer_reset(s);
+  if (n == 0) return LSG_OK;
+  // host image: payloads (8-aligned size), then the offsets, then the length words
+  const size_t pay = ((size_t)total + 7) & ~(size_t)7;
+  std::vector<uint8_t> img(pay + 8 * n);
+  uint32_t* off = (uint32_t*)(img.data() + pay);
+  uint32_t* len = off + n;
+  size_t at = 0;
+  for (size_t i = 0; i < n; i++) {
+    const uint32_t ol = offsets[i + 1] - offsets[i];
+    off[i] = (uint32_t)at;
+    len[i] = LSG_MSG_OBJECT | (kind << LSG_MSG_KIND_SHIFT) | (ol + 32);
+    memcpy(img.data() + at, objs + offsets[i], ol);
+    memcpy(img.data() + at + ol, domain + (size_t)dstride * i, 32);
+    at += (size_t)ol + 32;
+  }
+  LSG_RC(ensure(s, s->d_aux, img.size()));
+  LSG_RC(ensure(s, s->d_Fb, 32 * n));
+  uint8_t* d_img = P_<uint8_t>(s->d_aux);
+  LSG_HIP(s, hipMemcpyAsync(d_img, img.data(), img.size(), hipMemcpyHostToDevice, s->st[0]));
+  KL(s, "k_msg_roots_var", lsgk::msg_roots_var(S_(s), (int)n, d_img, (const uint32_t*)(d_img + pay),
+                                               (uint32_t*)(d_img + pay) + n, P_<uint8_t>(s->d_Fb)));
+  LSG_HIP(s, hipMemcpyAsync(out32, s->d_Fb.p, 32 * n, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  keep_times(s);
+  return LSG_OK;
 }
 
 // processDeposit.ts:47-66 for n deposits: signing roots on the device, then one single-set

@@ -356,10 +356,49 @@ __global__ void __launch_bounds__(64) k_msg_roots(int n, uint8_t* msg, const uin
   size_t i = gtid();
   if (i >= (size_t)n) return;
   const uint32_t l = msg_len[i];
-  if (!(l & LSG_MSG_OBJECT)) return;
+  if (!(l & LSG_MSG_OBJECT) || (l & LSG_MSG_KIND_MASK)) return;  // (tagged messages: k_msg_roots_var)
   const uint32_t obj_len = (l & ~LSG_MSG_OBJECT) - 32u;
   uint8_t* p = msg + msg_off[i];
   msg_len[i] = ssz_object_signing_root(obj_len, p, p + obj_len, p) ? 32u : 0u;
+}
+
+// The variable-size kinds (a non-zero kind tag in the staged length word: AggregateAndProof,
+// DESIGN.md 5j), one 64-lane workgroup per staged message; a workgroup whose message carries no
+// tag leaves at once.  The lanes run the phases of lsg_ssz.hpp's ssz_var_step -- pairs of one
+// tree level side by side, the fixed part's subtrees on lanes of their own -- with the
+// intermediate nodes in LDS (12,384 bytes) and a barrier after each phase, so an object costs
+// about depth + chunks / 128 dependent node hashes, not one per chunk.  Payloads have no
+// alignment: byte loads.  out32 == null (a package): the root goes over the start of the
+// payload, stored by lane 0 in the last phase, after every read, and the length word becomes
+// 32 as in k_msg_roots.  out32 != null (lsg_object_signing_roots_var): root m at out32 + 32 m,
+// the payload and its length word left alone.  The stager admits only well-formed objects
+// (lsgp::msg_var_ok); a length that would leave the node buffer leaves an empty message.
+__global__ void __launch_bounds__(SSZ_VAR_LANES) k_msg_roots_var(int n, uint8_t* msg, const uint32_t* __restrict__ msg_off,
+                                                                 uint32_t* msg_len, uint8_t* out32) {
+  __shared__ uint32_t nodes[SSZ_VAR_NODE_WORDS];
+  const uint32_t m = blockIdx.x, lane = threadIdx.x;
+  if (m >= (uint32_t)n) return;
+  const uint32_t l = msg_len[m];
+  const uint32_t kind = (l & LSG_MSG_KIND_MASK) >> LSG_MSG_KIND_SHIFT;
+  if (!(l & LSG_MSG_OBJECT) || kind == 0) return;
+  const uint32_t payload = l & ~(LSG_MSG_OBJECT | LSG_MSG_KIND_MASK);
+  uint8_t* p = msg + msg_off[m];
+  uint8_t* out = out32 ? out32 + 32 * (size_t)m : p;
+  const bool in_range = kind <= 2 && payload > 32 + ssz_var_bits_off(kind) &&
+                        payload <= 32 + ssz_var_bits_off(kind) + ssz_var_max_bits(kind) / 8 + 1;
+  const uint32_t obj_len = payload - 32;
+  const SszVar v = ssz_var_shape(kind, in_range ? obj_len : ssz_var_bits_off(kind) + 1, in_range ? p[obj_len - 1] : 1);
+  if (!in_range || v.n_bits > ssz_var_max_bits(kind)) {  // (uniform over the workgroup)
+    __syncthreads();  // every lane has read the length word
+    if (lane == 0 && !out32) msg_len[m] = 0;
+    return;
+  }
+  const uint32_t phases = ssz_var_phases(v);
+  for (uint32_t ph = 0; ph < phases; ph++) {
+    ssz_var_step(v, ph, lane, p, p + obj_len, nodes, out);
+    __syncthreads();
+  }
+  if (lane == 0 && !out32) msg_len[m] = 32;
 }
 
 namespace lsgk {
@@ -380,6 +419,11 @@ hipError_t object_signing_root(hipStream_t st, int n, const uint8_t* objs, uint3
 hipError_t msg_roots(hipStream_t st, int n, uint8_t* msg, const uint32_t* off, uint32_t* len) {
   if (n <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_msg_roots, dim3((n + 63) / 64), dim3(64), 0, st, n, msg, off, len);
+  return hipGetLastError();
+}
+hipError_t msg_roots_var(hipStream_t st, int n, uint8_t* msg, const uint32_t* off, uint32_t* len, uint8_t* out32) {
+  if (n <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_msg_roots_var, dim3(n), dim3(SSZ_VAR_LANES), 0, st, n, msg, off, len, out32);
   return hipGetLastError();
 }
 hipError_t expand_msg(hipStream_t st, int n, const uint8_t* msg, const uint32_t* off, const uint32_t* len,

@@ -61,6 +61,10 @@ hipError_t object_signing_root(hipStream_t st, int n, const uint8_t* objs, uint3
 // the staged messages marked LSG_MSG_OBJECT (len[m] & marker) become their 32-byte signing roots
 // in place, len[m] = 32; the others are left alone
 hipError_t msg_roots(hipStream_t st, int n, uint8_t* msg, const uint32_t* off, uint32_t* len);
+// likewise the staged messages whose length word carries a kind tag (the variable-size kinds,
+// which msg_roots leaves alone), one 64-lane workgroup per message.  out32 != null: root m goes
+// to out32 + 32 m instead and neither msg nor len is written.
+hipError_t msg_roots_var(hipStream_t st, int n, uint8_t* msg, const uint32_t* off, uint32_t* len, uint8_t* out32);
 
 // ---- signatures (lsg_k_sig.hip)                                       SURVEY 8a M2, M4
 hipError_t sig_decode(hipStream_t st, int n, const uint8_t* sig, const uint32_t* sig_len, uint32_t* sig_aff,

@@ -21,6 +21,7 @@
 
 #include "../../include/lodestar_bls.h"
 #include "lsg_bits.h"
+#include "lsg_ssz.hpp"
 
 namespace lsgp {
 
@@ -387,14 +388,24 @@ inline void plan_phase(std::vector<int32_t>& A, const std::vector<uint64_t>& rnd
 }
 
 // ---- messages given as an SSZ object + domain (LSG_MSG_OBJECT)
-// the bytes behind lsg_set.msg: msg_len without the marker
-inline uint32_t msg_bytes(uint32_t msg_len) { return msg_len & ~LSG_MSG_OBJECT; }
+// A marked length word is marker (bit 31), kind tag (bits 24..30), payload length (bits 0..23);
+// an unmarked one is a byte count in all its bits.
 inline bool msg_marked(uint32_t msg_len) { return (msg_len & LSG_MSG_OBJECT) != 0; }
+// the bytes behind lsg_set.msg
+inline uint32_t msg_bytes(uint32_t msg_len) {
+  return msg_marked(msg_len) ? msg_len & ~(LSG_MSG_OBJECT | LSG_MSG_KIND_MASK) : msg_len;
+}
+// the kind tag of a marked length (0: the kind is selected by the payload length, or unmarked)
+inline uint32_t msg_kind_tag(uint32_t msg_len) {
+  return msg_marked(msg_len) ? (msg_len & LSG_MSG_KIND_MASK) >> LSG_MSG_KIND_SHIFT : 0;
+}
+// marked with tag 0: one of the fixed-size kinds, k_msg_roots' work
+inline bool msg_fixed_object(uint32_t msg_len) { return msg_marked(msg_len) && !msg_kind_tag(msg_len); }
 // The object's serialized length (the kind, as ssz_object_signing_root of lsg_ssz.hpp takes it)
-// that a marked msg_len selects by its payload length, object + 32-byte domain; 0: none -- an
-// unmarked length, or a payload length outside the table.
+// that a marked msg_len with tag 0 selects by its payload length, object + 32-byte domain; 0:
+// none -- an unmarked length, a tagged one, or a payload length outside the table.
 inline uint32_t msg_object_kind(uint32_t msg_len) {
-  if (!msg_marked(msg_len)) return 0;
+  if (!msg_marked(msg_len) || msg_kind_tag(msg_len)) return 0;
   switch (msg_bytes(msg_len)) {
     case 40: return 8;     // uint64
     case 48: return 16;    // two uint64 fields
@@ -403,12 +414,35 @@ inline uint32_t msg_object_kind(uint32_t msg_len) {
     case 120: return 88;   // phase0.DepositMessage
     case 144: return 112;  // phase0.BeaconBlockHeader
     case 160: return 128;  // phase0.AttestationData
+    case 296: return 264;  // altair.ContributionAndProof
     default: return 0;
   }
 }
-// A marked set must select a kind and carry its bytes: anything else is a caller bug, answered
-// with LSG_ERR_INVALID_ARG before a slot is taken.  Unmarked sets pass as they are.
-inline bool msg_set_ok(const lsg_set& t) { return !msg_marked(t.msg_len) || (t.msg && msg_object_kind(t.msg_len)); }
+// The structure of a variable-size object (kind tag 1: phase0.AggregateAndProof, 2: EIP-7549's;
+// the layout is lsg_ssz.hpp's, whose device text assumes what is checked here): the length in
+// range, both offsets as the fixed parts dictate, a delimiter bit in the last byte, and no more
+// bits than the list's limit.  obj: obj_len readable bytes.
+inline bool msg_var_ok(uint32_t kind, const uint8_t* obj, size_t obj_len) {
+  if ((kind != LSG_MSG_KIND_AGG_PROOF && kind != LSG_MSG_KIND_AGG_PROOF_ELECTRA) || !obj) return false;
+  const uint32_t off = ssz_var_bits_off(kind), max_bits = ssz_var_max_bits(kind);
+  if (obj_len <= off || obj_len > off + max_bits / 8 + 1) return false;
+  uint32_t o1, o2;
+  memcpy(&o1, obj + 8, 4);  // (little-endian hosts, as the rest of the staging)
+  memcpy(&o2, obj + 108, 4);
+  if (o1 != 108 || o2 != off - 108) return false;
+  const uint8_t last = obj[obj_len - 1];
+  return last != 0 && ssz_var_shape(kind, (uint32_t)obj_len, last).n_bits <= max_bits;
+}
+// A marked set must select a kind and carry its bytes, a tagged one well-formed: anything else
+// is a caller bug, answered with LSG_ERR_INVALID_ARG before a slot is taken.  Unmarked sets
+// pass as they are.
+inline bool msg_set_ok(const lsg_set& t) {
+  if (!msg_marked(t.msg_len)) return true;
+  if (!t.msg) return false;
+  const uint32_t tag = msg_kind_tag(t.msg_len), mb = msg_bytes(t.msg_len);
+  if (!tag) return msg_object_kind(t.msg_len) != 0;
+  return mb > 32 && msg_var_ok(tag, t.msg, mb - 32);
+}
 // Likewise a multi-committee set (LSG_PK_BITS_MULTI) without a blob, or listing more than
 // LSG_MAX_SET_COMMITTEES committees.  multi_k: the blob's leading count.
 inline uint32_t multi_k(const lsg_set& t) {

@@ -146,7 +146,8 @@ struct StageSizes {
   size_t bit_words = 0;  // words of the bit arena the bits and multi sets may take
   bool all_index = true;  // every key names a table row: 4-byte key slots (a block body's
                           // ~3.7M signers cross PCIe as 15 MB instead of 355 MB)
-  bool any_obj = false;   // a message is an SSZ object + domain (LSG_MSG_OBJECT): k_msg_roots runs
+  bool any_obj = false;   // a message is an SSZ object + domain (LSG_MSG_OBJECT, tag 0): k_msg_roots runs
+  bool any_var = false;   // a message is a tagged, variable-size object: k_msg_roots_var runs
   size_t pk_stride() const { return all_index ? 4 : 96; }
 };
 inline bool stage_is_bits(const lsg_set& t, bool bits_ok) { return bits_ok && t.pk_len == LSG_PK_BITS; }
@@ -158,7 +159,8 @@ inline StageSizes stage_measure(const lsg_set* const* sets, size_t n, bool bits_
   for (size_t i = 0; i < n; i++) {
     const lsg_set& t = *sets[i];
     z.msg_total += msg_bytes(t.msg_len);
-    z.any_obj = z.any_obj || msg_marked(t.msg_len);
+    z.any_obj = z.any_obj || msg_fixed_object(t.msg_len);
+    z.any_var = z.any_var || msg_kind_tag(t.msg_len) != 0;
     if (stage_is_bits(t, bits_ok)) {
       z.n_bits_sets++;
       z.bit_words += bits_words(t.n_pks);
@@ -242,7 +244,8 @@ struct Staged {
   // msg_dedup when some sets share one (a committee's attestations sign one AttestationData)
   size_t n_msgs = 0;
   bool msg_dedup = false;
-  bool msg_objs = false;  // a staged message is an SSZ object + domain (LSG_MSG_OBJECT)
+  bool msg_objs = false;  // a staged message is an SSZ object + domain (LSG_MSG_OBJECT, tag 0)
+  bool msg_vars = false;  // a staged message is a tagged, variable-size object
   std::vector<uint32_t> msg_id;  // host copy of the set -> message map (msg_dedup)
   size_t msg_used = 0;           // message bytes staged (each distinct message / miss once)
   // the message cache.  mc_on: the package was staged through it -- n_miss of the
@@ -323,7 +326,7 @@ inline int stage_fill(uint8_t* A, const StageLayout& L, uint32_t* cbits, const l
   out.mc_pins.clear();
   out.mc_pend.clear();
   out.mc_store.clear();
-  bool miss_obj = false;
+  bool miss_obj = false, miss_var = false;
   if (mc) {
     out.mc_epoch = mc->epoch();
     out.mc_src_off = plan.size();
@@ -373,12 +376,13 @@ inline int stage_fill(uint8_t* A, const StageLayout& L, uint32_t* cbits, const l
             out.mc_store.push_back((int32_t)row);
           }
           plan[out.mc_src_off + nm] = (int32_t)k;
-          miss_obj = miss_obj || msg_marked(q->msg_len);
+          miss_obj = miss_obj || msg_fixed_object(q->msg_len);
+          miss_var = miss_var || msg_kind_tag(q->msg_len) != 0;
         }
       }
       if (staged) {
         msgoff[k] = (uint32_t)mo;
-        msglen[k] = q->msg_len;  // (with its marker: k_msg_roots turns the payload into a 32-byte message)
+        msglen[k] = q->msg_len;  // (with its marker and tag: k_msg_roots / k_msg_roots_var turn the payload into a 32-byte message)
         if (mb) memcpy(A + L.msg + mo, q->msg, mb);
         mo += mb;
       }
@@ -447,6 +451,7 @@ inline int stage_fill(uint8_t* A, const StageLayout& L, uint32_t* cbits, const l
   out.msg_used = mo;
   out.bit_words = bw;
   out.msg_objs = mc ? miss_obj : z.any_obj;
+  out.msg_vars = mc ? miss_var : z.any_var;
   if (mc) {  // the source words of the nm distinct messages stay; the store's pairs follow them
     plan.resize(out.mc_src_off + nm);
     out.mc_st_off = plan.size();

@@ -141,7 +141,10 @@ function serializeSet(set) {
     const message = new Uint8Array(set.signingObject.length + 32);
     message.set(set.signingObject, 0);
     message.set(set.domain, set.signingObject.length);
-    return {...serializeSet({...set, signingObject: undefined, signingRoot: message}), messageObject: true};
+    const kind = msgObjectKind(set);
+    const out = {...serializeSet({...set, signingObject: undefined, signingObjectKind: undefined, signingRoot: message}), messageObject: true};
+    if (kind !== 0) out.messageKind = kind;
+    return out;
   }
   // signers named by a committee loaded with loadCommittees() plus participation bits (8f(5))
   if (set.committee !== undefined) {
@@ -370,12 +373,37 @@ function loadAddon() {
  * ({signingObject, domain} instead of signingRoot; LSG_MSG_OBJECT, SURVEY.md 8f(6)): the
  * signing root is computed on the GPU as the package's first stage.  The object's length
  * selects its kind: uint64, two uint64 fields, Root, BLSToExecutionChange, DepositMessage,
- * BeaconBlockHeader, AttestationData. */
+ * BeaconBlockHeader, AttestationData, ContributionAndProof.  A variable-size object names its
+ * kind beside it (signingObjectKind: "AggregateAndProof" | "AggregateAndProofElectra"): the kind
+ * tag travels in bits 24..30 of the length word (LSG_MSG_KIND_*), and the object's structure --
+ * both offsets, the bitlist's delimiter bit and limit, the length -- is checked here, at call
+ * time, as the library checks it at its entry points. */
 const MSG_OBJECT = 0x80000000; // LSG_MSG_OBJECT
-const MSG_OBJECT_LENGTHS = [8, 16, 32, 76, 88, 112, 128];
+const MSG_KIND_SHIFT = 24; // LSG_MSG_KIND_SHIFT
+const MSG_OBJECT_LENGTHS = [8, 16, 32, 76, 88, 112, 128, 264];
+// signingObjectKind -> {tag, where the bitlist starts, its limit in bits}
+const MSG_OBJECT_KINDS = {
+  AggregateAndProof: {tag: 1, bitsOff: 336, maxBits: 2048},
+  AggregateAndProofElectra: {tag: 2, bitsOff: 344, maxBits: 131072},
+};
+function msgObjectKind(set) {
+  return set.signingObjectKind === undefined ? 0 : MSG_OBJECT_KINDS[set.signingObjectKind].tag;
+}
 function checkMsgObject(set) {
   const obj = set.signingObject;
-  if (!(obj instanceof Uint8Array) || !MSG_OBJECT_LENGTHS.includes(obj.length)) {
+  if (set.signingObjectKind !== undefined) {
+    const kind = Object.prototype.hasOwnProperty.call(MSG_OBJECT_KINDS, set.signingObjectKind) ? MSG_OBJECT_KINDS[set.signingObjectKind] : null;
+    if (kind === null) throw Error(`signingObjectKind must be one of ${Object.keys(MSG_OBJECT_KINDS).join(", ")}`);
+    const {bitsOff, maxBits} = kind;
+    if (!(obj instanceof Uint8Array) || obj.length <= bitsOff || obj.length > bitsOff + maxBits / 8 + 1) {
+      throw Error(`signingObject of kind ${set.signingObjectKind} must be a Uint8Array of ${bitsOff + 1} to ${bitsOff + maxBits / 8 + 1} bytes`);
+    }
+    const u32 = (at) => (obj[at] | (obj[at + 1] << 8) | (obj[at + 2] << 16) | (obj[at + 3] << 24)) >>> 0;
+    if (u32(8) !== 108 || u32(108) !== bitsOff - 108) throw Error(`signingObject is not a serialized ${set.signingObjectKind}: offsets`);
+    const last = obj[obj.length - 1];
+    if (last === 0) throw Error("signingObject's aggregation bits have no delimiter bit");
+    if (8 * (obj.length - bitsOff - 1) + (31 - Math.clz32(last)) > maxBits) throw Error(`signingObject's aggregation bits exceed ${maxBits}`);
+  } else if (!(obj instanceof Uint8Array) || !MSG_OBJECT_LENGTHS.includes(obj.length)) {
     throw Error(`signingObject must be a Uint8Array of ${MSG_OBJECT_LENGTHS.join(", ")} bytes`);
   }
   if (!(set.domain instanceof Uint8Array) || set.domain.length !== 32) {
@@ -567,7 +595,7 @@ function packJobs(ranges, nSigs, into, minSigs = 0, grouped = false) {
     groupTags[k] = set.aggregateTag;
   };
   // 224 bytes per set: one raw key, a 32-byte root, a signature.  Sets that carry more (aggregate
-  // keys, signingObject + domain: up to 160 message bytes) grow the arena in put(); the grown
+  // keys, signingObject + domain: up to 16,761 message bytes) grow the arena in put(); the grown
   // buffer comes back as arenaBuf, so a verifier's later packages of that kind reuse it
   let cap = Math.max(nSigs, minSigs) * 224 + 256;
   let arena = into && into.arenaBuf.length >= cap ? into.arenaBuf : new Uint8Array(cap);
@@ -616,7 +644,7 @@ function packJobs(ranges, nSigs, into, minSigs = 0, grouped = false) {
           const dom = set.signingObject === undefined ? null : set.domain;
           if (dom !== null) checkMsgObject(set);
           const root = dom === null ? set.signingRoot : set.signingObject;
-          const msgWord = dom === null ? root.length : MSG_OBJECT + root.length + 32;
+          const msgWord = dom === null ? root.length : MSG_OBJECT + msgObjectKind(set) * (1 << MSG_KIND_SHIFT) + root.length + 32;
           const sig = set.signature;
           const msgBytes = dom === null ? root.length : root.length + 32;
           if (grouped) groupOf(set, k);
@@ -823,7 +851,8 @@ class BlsGpuVerifier {
       // preallocate every pipeline slot for packages of up to reserveSets sets (lsg_reserve)
       const pks = options.reservePubkeys || options.reserveSets;
       // message bytes: 32 per set for signing roots; signingObject sets stage object + domain
-      // (up to 160 bytes, an AttestationData): callers that send them say so (reserveMsgBytes)
+      // (up to 160 bytes for an AttestationData, 296 for a ContributionAndProof, 16,761 for an
+      // Electra AggregateAndProof): callers that send them say so (reserveMsgBytes)
       const msgBytes = options.reserveMsgBytes || 32 * options.reserveSets;
       this.addon.reserve(this.ctx, options.reserveSets, pks, msgBytes, this.poolSize);
     }

@@ -47,13 +47,16 @@
  *       or pk_len 12 = LSG_PK_BITS_MULTI: count k, k committee ids, bits over their concatenation)
  *   objectSigningRoots(ctx, objs: n x objLen B, objLen, domain: 32 B | n x 32 B) -> Uint8Array(n x 32)
  *                                                                      lsg_object_signing_roots
+ *   objectSigningRootsVar(ctx, kind, objs, offsets: Uint32Array(n + 1), domain) -> Uint8Array(n x 32)
+ *                                                                      lsg_object_signing_roots_var
  *   msgCacheSet(ctx, rows)                                             lsg_msg_cache_set
  *   msgCacheStats(ctx) -> {lookups, hits, pending, inserts, evictions, bypassed, full, entries, capacity}
  *                                                                      lsg_msg_cache_get_stats
  *       (these seven throw "does not support" when the loaded library lacks the entry point)
  *   A set's message may be an SSZ object followed by its 32-byte domain (LSG_MSG_OBJECT): the
  *   descriptor's msgLen word of verifyPacked carries 0x80000000 | length; a set of verifySets
- *   carries messageObject: true beside message.
+ *   carries messageObject: true beside message, and messageKind (a kind tag, LSG_MSG_KIND_*) for a
+ *   variable-size kind.
  * Failures of the library itself (not verdicts) throw an Error carrying lsg_last_error().
  */
 #include <node_api.h>
@@ -75,6 +78,9 @@ extern int lsg_committees_set(lsg_ctx* ctx, uint32_t first_id, const uint32_t* i
 extern int lsg_committees_clear(lsg_ctx* ctx, uint32_t first_id, size_t n) __attribute__((weak));
 extern int lsg_object_signing_roots(lsg_ctx* ctx, const uint8_t* objs, uint32_t obj_len, size_t n,
                                     const uint8_t* domain32, uint32_t domain_stride, uint8_t* out32)
+    __attribute__((weak));
+extern int lsg_object_signing_roots_var(lsg_ctx* ctx, uint32_t kind, const uint8_t* objs, const uint32_t* offsets, size_t n,
+                                        const uint8_t* domain32, uint32_t domain_stride, uint8_t* out32)
     __attribute__((weak));
 extern int lsg_submit_jobs_grouped(lsg_ctx* ctx, const lsg_job* jobs, size_t n_jobs, uint64_t seed,
                                    const uint32_t* set_group, size_t n_groups, lsg_ticket* ticket) __attribute__((weak));
@@ -192,11 +198,21 @@ static int view_sets(napi_env env, napi_value arr, set_view* out) {
     if (!m || get_bytes(env, m, &d, &len) || len >= LSG_MSG_OBJECT) goto bad;
     q->msg = d;
     q->msg_len = (uint32_t)len;
-    /* messageObject: true -- message is an SSZ object followed by its 32-byte domain (LSG_MSG_OBJECT) */
+    /* messageObject: true -- message is an SSZ object followed by its 32-byte domain (LSG_MSG_OBJECT);
+     * messageKind: its kind tag (LSG_MSG_KIND_*, 0 or absent: the kind goes by the length), which
+     * travels in bits 24..30 of the length word, so the payload must fit bits 0..23 */
     napi_value mo = get_prop(env, s, "messageObject");
     bool is_obj = false;
     if (mo && napi_coerce_to_bool(env, mo, &mo) == napi_ok) napi_get_value_bool(env, mo, &is_obj);
-    if (is_obj) q->msg_len |= LSG_MSG_OBJECT;
+    if (is_obj) {
+      uint32_t kind = 0;
+      napi_value mk = get_prop(env, s, "messageKind");
+      napi_valuetype mkt = napi_undefined;
+      if (mk) napi_typeof(env, mk, &mkt);
+      if (mkt == napi_number && napi_get_value_uint32(env, mk, &kind) != napi_ok) goto bad;
+      if (kind > (LSG_MSG_KIND_MASK >> LSG_MSG_KIND_SHIFT) || len > 0x00ffffffu) goto bad;
+      q->msg_len |= LSG_MSG_OBJECT | (kind << LSG_MSG_KIND_SHIFT);
+    }
     if (!g || get_bytes(env, g, &d, &len)) goto bad;
     q->sig = d;
     q->sig_len = (uint32_t)len;
@@ -426,8 +442,9 @@ static int build_jobs(pkg_req* r, lsg_set** sets_out, lsg_job** jobs_out) {
       memcpy(&k, r->arena + d[0], 4);
       pk_bytes = 4 + 4 * (uint64_t)k + (((uint64_t)d[2] + 7) >> 3);
     }
-    /* the length word of a message may carry LSG_MSG_OBJECT: its bytes are the masked length */
-    const uint64_t msg_bytes = d[4] & ~LSG_MSG_OBJECT;
+    /* a marked length word is marker, kind tag (bits 24..30) and payload length (bits 0..23); an
+     * unmarked one is a byte count in all its bits */
+    const uint64_t msg_bytes = (d[4] & LSG_MSG_OBJECT) ? (d[4] & ~(LSG_MSG_OBJECT | LSG_MSG_KIND_MASK)) : d[4];
     if ((uint64_t)d[0] + pk_bytes > L || (uint64_t)d[3] + msg_bytes > L || (uint64_t)d[5] + d[6] > L) {
       free(sets);
       free(jobs);
@@ -997,7 +1014,7 @@ static napi_value js_attestation_signing_roots(napi_env env, napi_callback_info 
 
 /* objectSigningRoots(ctx, objs: Uint8Array (n x objLen B), objLen, domain: Uint8Array (32 B shared,
  * or n x 32 B)) -> Uint8Array(n x 32): computeSigningRoot for n objects of the kind objLen selects
- * (8, 16, 32, 76, 88, 112, 128; 8f(6), lsg_object_signing_roots) */
+ * (8, 16, 32, 76, 88, 112, 128, 264; 8f(6), lsg_object_signing_roots) */
 static napi_value js_object_signing_roots(napi_env env, napi_callback_info info) {
   size_t argc = 4;
   napi_value argv[4];
@@ -1025,6 +1042,43 @@ static napi_value js_object_signing_roots(napi_env env, napi_callback_info info)
   uint32_t stride = doml == 32 ? 0 : 32;
   int rc = n ? lsg_object_signing_roots(ctx, d, ol, n, dom, stride, (uint8_t*)outp) : LSG_OK;
   if (rc) return throw_lsg(env, ctx, "lsg_object_signing_roots", rc);
+  return out;
+}
+
+/* objectSigningRootsVar(ctx, kind, objs: Uint8Array (the objects back to back), offsets: Uint32Array
+ * (n + 1 entries, offsets[0] = 0, offsets[n] = objs.length), domain: Uint8Array (32 B shared, or
+ * n x 32 B)) -> Uint8Array(n x 32): computeSigningRoot for n objects of one variable-size kind
+ * (LSG_MSG_KIND_AGG_PROOF 1, LSG_MSG_KIND_AGG_PROOF_ELECTRA 2; lsg_object_signing_roots_var) */
+static napi_value js_object_signing_roots_var(napi_env env, napi_callback_info info) {
+  size_t argc = 5;
+  napi_value argv[5];
+  NAPI_CALL(env, napi_get_cb_info(env, info, &argc, argv, NULL, NULL));
+  lsg_ctx* ctx = get_ctx(env, argv[0]);
+  if (!ctx) return NULL;
+  const uint8_t *d, *dom;
+  const uint32_t* offs;
+  size_t dl, doml, no;
+  uint32_t kind = 0;
+  if (argc < 5 || napi_get_value_uint32(env, argv[1], &kind) != napi_ok || get_bytes(env, argv[2], &d, &dl) ||
+      get_u32s(env, argv[3], &offs, &no) || no == 0 || get_bytes(env, argv[4], &dom, &doml) || offs[0] != 0 ||
+      offs[no - 1] != dl || (doml != 32 && doml != 32 * (no - 1))) {
+    napi_throw_type_error(env, NULL,
+                          "lsg_napi: objectSigningRootsVar(ctx, kind, objs, offsets: Uint32Array(n + 1), domain: 32 B | n x 32 B)");
+    return NULL;
+  }
+  if (!lsg_object_signing_roots_var) {
+    napi_throw_error(env, NULL,
+                     "lsg_napi: the loaded library does not support objectSigningRootsVar (no lsg_object_signing_roots_var)");
+    return NULL;
+  }
+  const size_t n = no - 1;
+  void* outp;
+  napi_value ab, out;
+  NAPI_CALL(env, napi_create_arraybuffer(env, 32 * n, &outp, &ab));
+  NAPI_CALL(env, napi_create_typedarray(env, napi_uint8_array, 32 * n, ab, 0, &out));
+  uint32_t stride = doml == 32 ? 0 : 32;
+  int rc = n ? lsg_object_signing_roots_var(ctx, kind, d, offs, n, dom, stride, (uint8_t*)outp) : LSG_OK;
+  if (rc) return throw_lsg(env, ctx, "lsg_object_signing_roots_var", rc);
   return out;
 }
 
@@ -1270,6 +1324,7 @@ static napi_value init(napi_env env, napi_value exports) {
       {"aggregateSignatures", NULL, js_aggregate_signatures, NULL, NULL, NULL, napi_enumerable, NULL},
       {"attestationSigningRoots", NULL, js_attestation_signing_roots, NULL, NULL, NULL, napi_enumerable, NULL},
       {"objectSigningRoots", NULL, js_object_signing_roots, NULL, NULL, NULL, napi_enumerable, NULL},
+      {"objectSigningRootsVar", NULL, js_object_signing_roots_var, NULL, NULL, NULL, napi_enumerable, NULL},
       {"verifyDeposits", NULL, js_verify_deposits, NULL, NULL, NULL, napi_enumerable, NULL},
       {"pubkeyValidate", NULL, js_pubkey_validate, NULL, NULL, NULL, napi_enumerable, NULL},
       {"committeesSet", NULL, js_committees_set, NULL, NULL, NULL, napi_enumerable, NULL},

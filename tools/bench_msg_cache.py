@@ -210,11 +210,12 @@ def main():
 def _set_of(pj, i):
     """set i of a PreparedJobs as a (pks, msg, sig) tuple again"""
     import ctypes
-    from lodestar_amd._native import LSG_MSG_OBJECT, MsgObject
+    from lodestar_amd._native import LSG_MSG_KIND_MASK, LSG_MSG_KIND_SHIFT, LSG_MSG_OBJECT, MsgObject
     s = pj.sets[i]
-    n = s.msg_len & ~LSG_MSG_OBJECT
+    marked = bool(s.msg_len & LSG_MSG_OBJECT)  # a marked word: marker, kind tag, payload length
+    n = s.msg_len & ~(LSG_MSG_OBJECT | LSG_MSG_KIND_MASK) if marked else s.msg_len
     raw = ctypes.string_at(s.msg, n)
-    msg = MsgObject(raw[:n - 32], raw[n - 32:]) if s.msg_len & LSG_MSG_OBJECT else raw
+    msg = MsgObject(raw[:n - 32], raw[n - 32:], (s.msg_len & LSG_MSG_KIND_MASK) >> LSG_MSG_KIND_SHIFT) if marked else raw
     return ([ctypes.string_at(s.pks, s.pk_len)], msg, ctypes.string_at(s.sig, s.sig_len))
 
 
