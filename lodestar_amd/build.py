@@ -15,18 +15,18 @@ OUT = os.path.join(HERE, "liblodestar_bls.so")
 # kernel translation units compile in parallel; lsg_host.hip is the orchestration + C ABI
 SOURCES = ["lsg_k_hash.hip", "lsg_k_sig.hip", "lsg_k_pk.hip", "lsg_k_miller.hip", "lsg_k_reduce.hip", "lsg_slp.hip",
            "lsg_host.hip"]
-HEADERS = ["lsg_types.hpp", "lsg_fp_lane.hpp", "lsg_fp_elem.hpp", "lsg_tower.hpp", "lsg_curve.hpp", "lsg_h2c.hpp",
+HEADERS = ["lsg_types.hpp", "lsg_fp_elem.hpp", "lsg_tower.hpp", "lsg_curve.hpp", "lsg_h2c.hpp",
            "lsg_pairing.hpp", "lsg_constants.hpp", "lsg_fp_pair.hpp", "lsg_constants_r29.hpp", "lsg_io.hpp",
-           "lsg_serial.h", "lsg_kcommon.hpp", "lsg_launch.h", "lsg_layout.h", "lsg_slp_progs.h", "lsg_slp_exec.hpp", "lsg_inv.hpp",
+           "lsg_slp.h", "lsg_kcommon.hpp", "lsg_launch.h", "lsg_layout.h", "lsg_slp_progs.h", "lsg_slp_exec.hpp", "lsg_inv.hpp",
            "lsg_ab.h", "lsg_plan.hpp", "lsg_bits.h", "lsg_ssz.hpp", "lsg_fp2_lanes.hpp",
            "lsg_msg_cache.hpp", "lsg_stage.hpp"]
 OBJ = os.path.join(HERE, "_obj")
 # The A/B and test build (lsg_ab.h): the orchestration compiled with -DLSG_AB (its switches read
-# from the environment) plus the row-backend serial kernels (LSG_SERIAL=row); every other
-# translation unit is the shipped library's own object.  Tests that compare two forms of a
-# stage load it beside the shipped library (lodestar_amd._native.load_library(AB_OUT)).
+# from the environment); every other translation unit is the shipped library's own object.
+# Tests that compare two forms of a stage load it beside the shipped library
+# (lodestar_amd._native.load_library(AB_OUT)).
 AB_OUT = os.path.join(HERE, "liblodestar_bls_ab.so")
-AB_SOURCES = ["lsg_host.hip", "lsg_serial.hip", "lsg_serial_wide.hip"]
+AB_SOURCES = ["lsg_host.hip"]
 AB_FLAGS = ["-DLSG_AB=1"]
 
 

@@ -5,7 +5,6 @@
 // them from the environment per call, so one process can compare both forms.
 #pragma once
 #include <stdlib.h>
-#include <string.h>
 
 // The square roots of sig_decode and h2c_map run their powers with one element per lane
 // (k_fp_pow_lanes) from this many power operands per launch on: one per signature, two per
@@ -20,11 +19,6 @@ static inline long lsg_ab_long(const char* name, long dflt) {
   const char* e = getenv(name);
   return e ? atol(e) : dflt;
 }
-static inline bool lsg_ab_str_is(const char* name, const char* v) {
-  const char* e = getenv(name);
-  return e && strcmp(e, v) == 0;
-}
 #else
 #define lsg_ab_long(name, dflt) ((long)(dflt))
-#define lsg_ab_str_is(name, v) false
 #endif

@@ -34,8 +34,6 @@
 // throughout.  This is the mid-loop carry of the one-lane build of pair_sop2_n / pair_mont_mul_n.
 // tests/test_fp2_lanes_model.py checks value, the m sequence and the bound at every step on
 // Python integers; tests/native/fp2lanecheck.cpp runs the passes below under UBSan.
-//
-// -DLSG_NO_FP2_LANES: the two kernels stay on the pair form (the code before this header).
 #pragma once
 
 constexpr int LSG_VL = 14;  // limbs per lane
@@ -244,7 +242,7 @@ LSG_PFN void lanes_sqr_operand(uint32_t& V, uint32_t& s, uint32_t own, uint32_t 
 }
 LSG_PFN uint32_t lanes_xi_operand(uint32_t own, uint32_t partner, bool odd) { return odd ? own + partner : own - partner; }
 
-#if LSG_PAIR_G == 2 && !defined(LSG_NO_FP2_LANES)
+#if LSG_PAIR_G == 2
 #define LSG_FP2_LANES 1
 // ------------------------------------------------------------------ the type and its leaves
 struct fp2v_t {
@@ -510,4 +508,4 @@ LSG_PFN fp2vs_t<3, 3> fp6_kar_s1(const fp2v_t& v0, const fp2v_t& v1, const fp2v_
 LSG_PFN fp2vs_t<2, 2> fp6_kar_s2(const fp2v_t& v0, const fp2v_t& v1, const fp2v_t& v2, const fp2v_t& m2) {
   return (fsum(m2) - v0 - v2) + v1;
 }
-#endif  // LSG_PAIR_G == 2 && !LSG_NO_FP2_LANES
+#endif  // LSG_PAIR_G == 2

@@ -1,7 +1,7 @@
 // Element backend: one thread holds a whole Fp element (12 x u32 Montgomery limbs).
 // Used by the host build of the math (tests/native/hostcheck.hip) so that every stage of the
 // generic tower / curve / pairing code can be checked against the oracle on a CPU; the
-// product kernels use the limb-parallel backend (lsg_fp_lane.hpp) instead.
+// kernels use the pair backend (lsg_fp_pair.hpp) instead.
 #pragma once
 #include "lsg_constants.hpp"
 

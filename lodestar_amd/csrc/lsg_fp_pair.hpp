@@ -50,38 +50,19 @@ LSG_PFN uint32_t pbcast(uint32_t x) {
   return S == 0 ? pdpp<0xA0>(x) : pdpp<0xF5>(x);
 }
 LSG_PFN uint32_t pswap(uint32_t x) { return pdpp<0xB1>(x); }  // the other lane of the pair
-LSG_PFN uint32_t pdown(uint32_t x) {                           // lane 0 <- lane 1, lane 1 <- 0
-  const uint32_t v = pdpp<0xF5>(x);
-  return pair_h() ? 0u : v;
-}
-#ifndef LSG_LEAF_DPP_AND  // A/B builds: 0 = the round-2 moves (DPP move, then and / select)
-#define LSG_LEAF_DPP_AND 1
-#endif
-#if LSG_LEAF_DPP_AND
 LSG_PFN uint32_t pup(uint32_t x) {  // lane 1 <- lane 0, lane 0 <- 0: one v_and_b32 with a DPP source
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xA0, 0xf, 0xf, true) & (0u - pair_h());
 }
-#else
-LSG_PFN uint32_t pup(uint32_t x) {
-  const uint32_t v = pdpp<0xA0>(x);
-  return pair_h() ? v : 0u;
-}
-#endif
-// pdown(x & M29) and pbcast<0>(x) & M29 as ONE v_and_b32 each: the DPP move folds into the and
-// (GCNDPPCombine) when the mask is a register operand -- lmask = M29 on lane 0 and 0 on lane 1
-// also does pdown's zeroing of lane 1, so the retire step loses an and and a cndmask and the m
-// broadcast an and
-#if LSG_LEAF_DPP_AND
+// lane 0 <- lane 1's x & M29, lane 1 <- 0, and pbcast<0>(x) & M29, as ONE v_and_b32 each: the DPP
+// move folds into the and (GCNDPPCombine) when the mask is a register operand -- lmask = M29 on
+// lane 0 and 0 on lane 1 also zeroes lane 1, so against a DPP move followed by an and / select
+// the retire step loses an and and a cndmask and the m broadcast an and
 LSG_PFN uint32_t pdown_and(uint32_t x, uint32_t lmask) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xF5, 0xf, 0xf, true) & lmask;
 }
 LSG_PFN uint32_t pbcast0_and(uint32_t x, uint32_t m29) {
   return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0xA0, 0xf, 0xf, true) & m29;
 }
-#else
-LSG_PFN uint32_t pdown_and(uint32_t x, uint32_t) { return pdown(x & LSG_M29); }
-LSG_PFN uint32_t pbcast0_and(uint32_t x, uint32_t) { return pbcast<0>(x & LSG_M29); }
-#endif
 #else
 #define LSG_PFN LSG_INL
 #define LSG_PLEAF LSG_NOINL
@@ -91,7 +72,6 @@ LSG_PFN uint32_t pbcast(uint32_t x) {
   return x;
 }
 LSG_PFN uint32_t pswap(uint32_t x) { return x; }
-LSG_PFN uint32_t pdown(uint32_t) { return 0u; }
 LSG_PFN uint32_t pup(uint32_t) { return 0u; }
 LSG_PFN uint32_t pdown_and(uint32_t, uint32_t) { return 0u; }
 LSG_PFN uint32_t pbcast0_and(uint32_t x, uint32_t m29) { return x & m29; }
@@ -314,9 +294,6 @@ LSG_PFN void pair_mont_mul_n(fp_t* r, const fp_t* a, const fp_t* b) {
 // per lane; for limbs in [-8, 2^29 + 8] and the doubled operand below 2^30 + 16 that is
 // |t| < 7 (2^59.1 + 2^58) < 2^62.3 plus the carries of < 2^34 that stay behind.  The one-lane
 // host build holds a column for 14 steps and carries once at mid-loop, as pair_sop2_n does.
-#ifndef LSG_SQR_STEP_FENCE  // A/B builds: 0 = the steps of a squaring scheduled freely
-#define LSG_SQR_STEP_FENCE 1
-#endif
 template <int N>
 LSG_PFN void pair_mont_sqr_n(fp_t* r, const fp_t* a) {
   const bool top = pair_top();
@@ -358,7 +335,7 @@ LSG_PFN void pair_mont_sqr_n(fp_t* r, const fp_t* a) {
       t[n][0] += c;
       t[n][LSG_PL - 1] = (int64_t)mv;
     }
-#if LSG_PAIR_G == 2 && LSG_SQR_STEP_FENCE
+#if LSG_PAIR_G == 2
     // no step's work moved into another: without it pair_pow_plan and the kernels around it
     // need two VGPRs more than with the product (195 against 193), with it 180
     __builtin_amdgcn_sched_barrier(0);
@@ -378,9 +355,6 @@ LSG_PFN void pair_mont_sqr_n(fp_t* r, const fp_t* a) {
 #pragma unroll
   for (int n = 0; n < N; n++) pair_redc_tail(t[n], r[n], top);
 }
-#ifndef LSG_SOP_STEP_FENCE
-#define LSG_SOP_STEP_FENCE 0
-#endif
 // ---- sums of two products with one Montgomery reduction (fp_sop)
 //   r_n = REDC(xa_n ya_n + xb_n yb_n)
 // ONE CIOS pass with two partial products per step.  The Fp2 product is two of them,
@@ -437,9 +411,6 @@ LSG_PFN void pair_sop2_n(fp_t* r, const fp_t* xa, const fp_t* ya, const fp_t* xb
       t[n][0] += c;
       t[n][LSG_PL - 1] = (int64_t)mv;
     }
-#if LSG_PAIR_G == 2 && LSG_SOP_STEP_FENCE
-    __builtin_amdgcn_sched_barrier(0);  // no step's broadcasts hoisted into an earlier one
-#endif
 #if LSG_PAIR_G == 1
     if (i == 6) {  // one lane holds every column for 14 steps: carry once (value-preserving)
 #pragma unroll
@@ -488,9 +459,7 @@ LSG_PLEAF fp_t pair_mont_mul(fp_t a, fp_t b) {
   pair_mont_mul_n<1>(&r, &a, &b);
   return r;
 }
-#ifndef LSG_NO_SQR_LEAF  // (A/B builds: -DLSG_NO_SQR_LEAF squares with the product leaf)
-#define LSG_SQR_LEAF 1   // fp_sqr and the power leaves call the squaring pass
-#endif
+#define LSG_SQR_LEAF 1  // fp_sqr and the power leaves call the squaring pass
 LSG_PLEAF fp_t pair_mont_sqr(fp_t a) {
   LSG_COUNT_MUL();
   LSG_AUDIT_CARRIED(a, "squaring operand");
@@ -500,16 +469,9 @@ LSG_PLEAF fp_t pair_mont_sqr(fp_t a) {
 }
 // Multi-product leaves.  Operands cross the call as 8-word vectors: the gfx950 call ABI
 // passes vector arguments in VGPRs (up to 32), but only the first two 7-word structs; the
-// rest went byval through scratch at every call site.
-// LSG_LEAF_MODE (A/B builds): 0 = one product per call everywhere, 1 = the multi-product
-// leaves below with their products one after another (default), 2 = interleaved
-#ifndef LSG_LEAF_MODE
-#define LSG_LEAF_MODE 1
-#endif
-#ifndef LSG_FP2_SOP  // A/B builds: 0 = the Karatsuba Fp2 leaf (three full products)
-#define LSG_FP2_SOP 1
-#endif
-#if LSG_PAIR_G == 2 && LSG_LEAF_MODE == 1
+// rest went byval through scratch at every call site.  A leaf runs its products one after
+// another, with a scheduling fence between them.
+#if LSG_PAIR_G == 2
 #define LSG_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 #else
 #define LSG_SCHED_FENCE() ((void)0)
@@ -572,19 +534,15 @@ LSG_PLEAF fp_duo pair_mont_mul2_v(fp_arg_t a0, fp_arg_t b0, fp_arg_t a1, LSG_TAI
     LSG_AUDIT_CARRIED(x[n], "product operand");
     LSG_AUDIT_CARRIED(y[n], "product operand");
   }
-#if LSG_LEAF_MODE == 2
-  pair_mont_mul_n<2>(r, x, y);
-#else
   pair_mont_mul_n<1>(&r[0], &x[0], &y[0]);
   LSG_SCHED_FENCE();
   pair_mont_mul_n<1>(&r[1], &x[1], &y[1]);
-#endif
   return fp_duo{r[0], r[1]};
 }
 LSG_PFN fp_duo pair_mont_mul2(const fp_t& a0, const fp_t& b0, const fp_t& a1, const fp_t& b1) {
   return pair_mont_mul2_v(fp_pack(a0), fp_pack(b0), fp_pack(a1), LSG_TAIL_ARGS(b1));
 }
-// Karatsuba Fp2 product (a0 + a1 u)(b0 + b1 u), u^2 = -1: its three Fp products in one call
+// Fp2 product (a0 + a1 u)(b0 + b1 u), u^2 = -1: its two sums of products in one call
 LSG_PLEAF fp_duo pair_fp2_mul_v(fp_arg_t a0, fp_arg_t a1, fp_arg_t b0, LSG_TAIL_PARAMS(b1));
 // Fp2 square (a0 + a1)(a0 - a1), 2 a0 a1: its two Fp products in one call
 LSG_PLEAF fp_duo pair_fp2_sqr_v(fp_arg_t a0, fp_arg_t a1);
@@ -592,9 +550,7 @@ LSG_PFN fp_duo pair_fp2_mul(const fp_t& a0, const fp_t& a1, const fp_t& b0, cons
   return pair_fp2_mul_v(fp_pack(a0), fp_pack(a1), fp_pack(b0), LSG_TAIL_ARGS(b1));
 }
 LSG_PFN fp_duo pair_fp2_sqr(const fp_t& a0, const fp_t& a1) { return pair_fp2_sqr_v(fp_pack(a0), fp_pack(a1)); }
-#if LSG_LEAF_MODE != 0
 #define LSG_FP2_LEAF 1  // lsg_tower.hpp's fp2_mul / fp2_sqr call the two leaves above
-#endif
 
 // ------------------------------------------------------------------ Fp API
 LSG_PFN fp_t fp_zero() {
@@ -790,21 +746,6 @@ LSG_PFN fps_t<K * P, K * N> fps_mulk(const fps_t<P, N>& a) {
 #endif  // !LSG_EAGER_SUMS
 
 LSG_PFN fp_t fp_mul(const fp_t& a, const fp_t& b) { return pair_mont_mul(a, b); }
-#if LSG_LEAF_MODE == 0
-LSG_PFN void fp_mul2(fp_t& r0, fp_t& r1, const fp_t& a0, const fp_t& b0, const fp_t& a1, const fp_t& b1) {
-  fp_t t = pair_mont_mul(a0, b0);
-  r1 = pair_mont_mul(a1, b1);
-  r0 = t;
-}
-LSG_PFN void fp_mul3(fp_t& r0, fp_t& r1, fp_t& r2, const fp_t& a0, const fp_t& b0, const fp_t& a1, const fp_t& b1,
-                     const fp_t& a2, const fp_t& b2) {
-  fp_t t0 = pair_mont_mul(a0, b0);
-  fp_t t1 = pair_mont_mul(a1, b1);
-  r2 = pair_mont_mul(a2, b2);
-  r0 = t0;
-  r1 = t1;
-}
-#else
 LSG_PFN void fp_mul2(fp_t& r0, fp_t& r1, const fp_t& a0, const fp_t& b0, const fp_t& a1, const fp_t& b1) {
   const fp_duo d = pair_mont_mul2(a0, b0, a1, b1);
   r0 = d.x;
@@ -817,7 +758,6 @@ LSG_PFN void fp_mul3(fp_t& r0, fp_t& r1, fp_t& r2, const fp_t& a0, const fp_t& b
   r0 = d.x;
   r1 = d.y;
 }
-#endif
 LSG_PFN void fp_mul9(fp_t* r, const fp_t* a, const fp_t* b) {
 #pragma unroll
   for (int g = 0; g < 9; g += 3) fp_mul3(r[g], r[g + 1], r[g + 2], a[g], b[g], a[g + 1], b[g + 1], a[g + 2], b[g + 2]);
@@ -833,26 +773,9 @@ LSG_PLEAF fp_duo pair_fp2_mul_v(fp_arg_t va0, fp_arg_t va1, fp_arg_t vb0, LSG_TA
   LSG_AUDIT_CARRIED(a1, "Fp2 product operand");
   LSG_AUDIT_CARRIED(b0, "Fp2 product operand");
   LSG_AUDIT_CARRIED(b1, "Fp2 product operand");
-#if LSG_FP2_SOP
   fp_duo d;
   pair_fp2_mul_sop(d.x, d.y, a0, a1, b0, b1);
   return d;
-#endif
-  // the three products run one after another (sched_barrier): interleaved, the leaf needed
-  // ~180 VGPRs, and every caller had to spill around it what the call clobbers
-  fp_t t[3];
-#if LSG_LEAF_MODE == 2
-  const fp_t a[3] = {a0, a1, fp_add(a0, a1)}, b[3] = {b0, b1, fp_add(b0, b1)};
-  pair_mont_mul_n<3>(t, a, b);
-#else
-  pair_mont_mul_n<1>(&t[0], &a0, &b0);
-  LSG_SCHED_FENCE();
-  pair_mont_mul_n<1>(&t[1], &a1, &b1);
-  LSG_SCHED_FENCE();
-  const fp_t s0 = fp_add(a0, a1), s1 = fp_add(b0, b1);
-  pair_mont_mul_n<1>(&t[2], &s0, &s1);
-#endif
-  return fp_duo{fp_sub(t[0], t[1]), fp_sub(fp_sub(t[2], t[0]), t[1])};
 }
 LSG_PLEAF fp_duo pair_fp2_sqr_v(fp_arg_t va0, fp_arg_t va1) {
   LSG_COUNT_MUL();
@@ -875,84 +798,20 @@ LSG_PLEAF fp_duo pair_fp2_sqr_v(fp_arg_t va0, fp_arg_t va1) {
     e.l[k] = a1.l[k] + a1.l[k];
   }
   fp_t t[2];
-#if LSG_LEAF_MODE == 2
-  const fp_t a[2] = {s, a0}, b[2] = {d, e};
-  pair_mont_mul_n<2>(t, a, b);
-#else
   pair_mont_mul_n<1>(&t[0], &s, &d);
   LSG_SCHED_FENCE();
   pair_mont_mul_n<1>(&t[1], &a0, &e);
-#endif
   return fp_duo{t[0], t[1]};
 }
 
-// a^e for a fixed public exponent e (12 little-endian words) in one call: the same sliding
-// window of width 4 as lsg_tower.hpp's generic fp_pow_fixed, with its ~455 products inline
-// (one call, one load of p, no per-product argument moves) -- the square roots of signature
-// decompression and SSWU and the batched inversions' roots are chains of these
-LSG_PLEAF fp_t pair_pow_fixed(fp_t a, const uint32_t* __restrict__ e) {
-  auto mul = [](const fp_t& x, const fp_t& y) {
-    LSG_COUNT_MUL();
-    fp_t r;
-    pair_mont_mul_n<1>(&r, &x, &y);
-    return r;
-  };
-  auto sq = [](const fp_t& x) {  // x^2 (-DLSG_NO_SQR_LEAF: as the product x x)
-    LSG_COUNT_MUL();
-    fp_t r;
-#ifdef LSG_SQR_LEAF
-    pair_mont_sqr_n<1>(&r, &x);
-#else
-    pair_mont_mul_n<1>(&r, &x, &x);
-#endif
-    return r;
-  };
-  // T[k] = a^(2k+1), written out: a table loop the compiler declines to unroll would put T
-  // in scratch with indexed access
-  fp_t T[8];
-  const fp_t a2 = sq(a);
-  T[0] = a;
-  T[1] = mul(T[0], a2);
-  T[2] = mul(T[1], a2);
-  T[3] = mul(T[2], a2);
-  T[4] = mul(T[3], a2);
-  T[5] = mul(T[4], a2);
-  T[6] = mul(T[5], a2);
-  T[7] = mul(T[6], a2);
-  int i = 383;
-  while (i >= 0 && !((e[i >> 5] >> (i & 31)) & 1u)) i--;
-  fp_t r = T[0];
-  bool started = false;
-  while (i >= 0) {
-    if (!((e[i >> 5] >> (i & 31)) & 1u)) {
-      r = sq(r);
-      i--;
-      continue;
-    }
-    int j = i - 3 < 0 ? 0 : i - 3;
-    while (!((e[j >> 5] >> (j & 31)) & 1u)) j++;
-    uint32_t v = 0;
-    for (int t = i; t >= j; t--) v = (v << 1) | ((e[t >> 5] >> (t & 31)) & 1u);
-    if (started)
-      for (int t = i; t >= j; t--) r = sq(r);
-    fp_t tv = T[0];
-#pragma unroll
-    for (int k = 1; k < 8; k++) tv = fp_select(v == (uint32_t)(2 * k + 1), T[k], tv);
-    r = started ? mul(r, tv) : tv;
-    started = true;
-    i = j - 1;
-  }
-  return r;
-}
-#if LSG_LEAF_MODE != 0 && !defined(LSG_NO_POW_LEAF)  // (A/B builds: -DLSG_NO_POW_LEAF)
-#define LSG_POW_LEAF 1  // lsg_tower.hpp's fp_pow_fixed calls pair_pow_fixed
-#endif
-
-// The same sliding window, planned at compile time.  pair_pow_fixed walks the exponent bit by
-// bit through a pointer argument: every bit test is a vector load and a wait (the pointer is
-// not known to be uniform inside the leaf), ~7 dependent loads per window against ~5
-// products.  Here the plan of each of the three fixed exponents is a constant table read with
-// scalar loads at a wave-uniform index, and the control flow is scalar.
+// a^e for the three fixed public exponents in one call, with its ~455 products inline (one
+// call, one load of p, no per-product argument moves) -- the square roots of signature
+// decompression and SSWU and the batched inversions' roots are chains of these.  The sliding
+// window of width 4 of lsg_tower.hpp's generic fp_pow_fixed, planned at compile time: walking
+// the exponent bit by bit through a pointer argument made every bit test a vector load and a
+// wait (the pointer is not known to be uniform inside the leaf), ~7 dependent loads per window
+// against ~5 products.  Here the plan of each exponent is a constant table read with scalar
+// loads at a wave-uniform index, and the control flow is scalar.
 //   step[0] = k:             r = a^(2k+1)
 //   step[w] = (s << 8) | k:  r = r^(2^s) * a^(2k+1)
 //   then `tail` squarings
@@ -1025,14 +884,10 @@ LSG_PLEAF fp_t pair_pow_plan(fp_t a, int id) {
     pair_mont_mul_n<1>(&r, &x, &y);
     return r;
   };
-  auto sq = [](const fp_t& x) {  // x^2 (-DLSG_NO_SQR_LEAF: as the product x x)
+  auto sq = [](const fp_t& x) {
     LSG_COUNT_MUL();
     fp_t r;
-#ifdef LSG_SQR_LEAF
     pair_mont_sqr_n<1>(&r, &x);
-#else
-    pair_mont_mul_n<1>(&r, &x, &x);
-#endif
     return r;
   };
   auto pick = [](const fp_t* T, uint32_t k) {
@@ -1041,7 +896,9 @@ LSG_PLEAF fp_t pair_pow_plan(fp_t a, int id) {
     for (uint32_t q = 1; q < 8; q++) tv = fp_select(k == q, T[q], tv);
     return tv;
   };
-  fp_t T[8];  // T[k] = a^(2k+1), written out as in pair_pow_fixed
+  // T[k] = a^(2k+1), written out: a table loop the compiler declines to unroll would put T
+  // in scratch with indexed access
+  fp_t T[8];
   const fp_t a2 = sq(a);
   T[0] = a;
   T[1] = mul(T[0], a2);
@@ -1076,9 +933,7 @@ LSG_PLEAF fp_t pair_pow_plan(fp_t a, int id) {
   for (int b = P.tail; b; b--) r = sqr(r);
   return r;
 }
-#if defined(LSG_POW_LEAF) && !defined(LSG_NO_POW_PLAN)  // (A/B builds: -DLSG_NO_POW_PLAN)
 #define LSG_POW_PLAN 1  // lsg_tower.hpp's fp_pow_id calls pair_pow_plan
-#endif
 
 // ---- canonical values
 // v in (-p, 2p) -> the representative in [0, p), fully normalised

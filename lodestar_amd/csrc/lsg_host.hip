@@ -1,6 +1,6 @@
 // lsg_host.hip -- host orchestration and the C ABI (include/lodestar_bls.h) of the MI355X
 // BLS12-381 signature-set verifier.  No kernels live here (they are in lsg_k_*.hip and
-// lsg_serial.hip, reached through lsg_launch.h / lsg_serial.h).
+// lsg_slp.hip, reached through lsg_launch.h / lsg_slp.h).
 //
 // Reference path replaced (file:line under /root/reference):
 //   packages/beacon-node/src/chain/bls/multithread/worker.ts:30-114  verifyManySignatureSets,
@@ -56,7 +56,7 @@
 #include "../../include/lodestar_bls.h"
 #include "lsg_launch.h"
 #include "lsg_layout.h"
-#include "lsg_serial.h"
+#include "lsg_slp.h"
 #include "lsg_ab.h"
 #include "lsg_msg_cache.hpp"
 #include "lsg_plan.hpp"
@@ -986,7 +986,7 @@ int batch_inv(Slot* s, int ws, const char* name, const uint32_t* v, size_t n, ui
 
 size_t slp_items_max() {
   const long v = lsg_ab_long("LSG_SLP_ITEMS", 2048);
-  return lsg_serial_mode() == LSG_SERIAL_SLP && v > 0 ? (size_t)v : 0;
+  return v > 0 ? (size_t)v : 0;
 }
 
 // hash_to_G2 of the slot's n expanded messages (d_ub) into H / hinf on the current stream
@@ -1120,10 +1120,6 @@ int launch_accum(Slot* s, size_t n_items, size_t item_off, uint32_t* fall, bool 
   return LSG_OK;
 }
 
-// kernel-time label of a serial stage: the straight-line program that runs it (slp_*), or the
-// row kernel with LSG_SERIAL=row in the A/B build (k_row_*)
-#define SERIAL_LABEL(name) (lsg_serial_mode() == LSG_SERIAL_SLP ? "slp_" #name : "k_row_" #name)
-
 // side stream: signature sums -> ML(-G1, S_g) -> fall slots; main stream: products, export, FE
 // rs: the scaled points [r_i] sig_i the plain groups sum; rs_msm: the unscaled points the
 // bucket MSM groups read (phase A: one buffer holds both kinds, by set)
@@ -1139,16 +1135,16 @@ int launch_phase(Slot* s, const PhasePlan& Ph, const uint32_t* rs, uint32_t* fal
     LSG_RC(run_seg(s, 1, "msm_bits", Ph.bits, P_<uint32_t>(s->d_bkt), P_<uint32_t>(s->d_bits)));
     KL(s, "k_g2p_to_canon", lsgk::g2p_to_canon(S_(s), (int)(MSM_BITS * Ph.n_msm), P_<uint32_t>(s->d_bits),
                                                P_<uint8_t>(s->d_Sb)));
-    KL(s, SERIAL_LABEL(horner_miller),
-       lsg_row_horner_miller(S_(s), (int)Ph.n_msm, P_<uint8_t>(s->d_Sb), P_<uint8_t>(s->d_fgb)));
+    KL(s, "slp_horner_miller",
+       lsg_slp_horner_miller(S_(s), (int)Ph.n_msm, P_<uint8_t>(s->d_Sb), P_<uint8_t>(s->d_fgb)));
   }
   if (Ph.n_msm < ng) {
     const int nsm = (int)(ng - Ph.n_msm);
     LSG_RC(run_seg(s, 1, "sig_sums", Ph.sums, rs, P_<uint32_t>(s->d_S)));
     uint8_t* sb = P_<uint8_t>(s->d_Sb) + (size_t)288 * MSM_BITS * Ph.n_msm;
     KL(s, "k_g2p_to_canon", lsgk::g2p_to_canon(S_(s), nsm, P_<uint32_t>(s->d_S) + W_G2P * Ph.n_msm, sb));
-    KL(s, SERIAL_LABEL(miller_neg_g1),
-       lsg_row_miller_neg_g1(S_(s), nsm, sb, P_<uint8_t>(s->d_fgb) + 576 * Ph.n_msm));
+    KL(s, "slp_miller_neg_g1",
+       lsg_slp_miller_neg_g1(S_(s), nsm, sb, P_<uint8_t>(s->d_fgb) + 576 * Ph.n_msm));
   }
   KL(s, "k_blobs_to_fp12", lsgk::blobs_to_fp12(S_(s), (int)ng, P_<uint8_t>(s->d_fgb), fall + W_F12 * Ph.term_base));
   LSG_HIP(s, hipEventRecord(s->ev_grp, s->st[1]));
@@ -1166,8 +1162,8 @@ int launch_fe_range(Slot* s, size_t g0, size_t g1) {
   if (g1 <= g0) return LSG_OK;
   s->cur = 0;
   const size_t ng = g1 - g0;
-  KL(s, SERIAL_LABEL(final_exp),
-     lsg_row_final_exp(S_(s), (int)ng, P_<uint8_t>(s->d_Fb) + 576 * g0, P_<int32_t>(s->d_verdict) + g0));
+  KL(s, "slp_final_exp",
+     lsg_slp_final_exp(S_(s), (int)ng, P_<uint8_t>(s->d_Fb) + 576 * g0, P_<int32_t>(s->d_verdict) + g0));
   LSG_HIP(s, hipMemcpyAsync(H_<int32_t>(s->h_verdict) + g0, P_<int32_t>(s->d_verdict) + g0, 4 * ng,
                             hipMemcpyDeviceToHost, s->st[0]));
   return LSG_OK;
@@ -1697,7 +1693,7 @@ int pkg_node_check(Slot* s, int n) {
   LSG_RC(run_seg(s, 2, "fp12_product", s->phA_node, nf, P_<uint32_t>(s->d_nodeF) + W_F12 * (size_t)n));
   uint8_t* blob = P_<uint8_t>(s->d_gath) + 576 * (size_t)(LSG_MAX_DEVICES + 1);
   KL(s, "k_fp12_to_canon", lsgk::fp12_to_canon(S_(s), 1, P_<uint32_t>(s->d_nodeF) + W_F12 * (size_t)n, blob));
-  KL(s, SERIAL_LABEL(final_exp), lsg_row_final_exp(S_(s), 1, blob, P_<int32_t>(s->d_nodeV)));
+  KL(s, "slp_final_exp", lsg_slp_final_exp(S_(s), 1, blob, P_<int32_t>(s->d_nodeV)));
   LSG_HIP(s, hipMemcpyAsync(s->h_nodeV.p, s->d_nodeV.p, 4, hipMemcpyDeviceToHost, s->st[0]));
   LSG_HIP(s, hipEventRecord(s->ev_node, s->st[0]));
   return LSG_OK;
@@ -2506,7 +2502,7 @@ int submit_final(Slot* s, const uint8_t* partials576, size_t ng, size_t pg, bool
     KL(s, "k_blobs_to_fp12", lsgk::blobs_to_fp12(S, (int)n, P_<uint8_t>(s->d_Fb), P_<uint32_t>(s->d_aux)));
     LSG_RC(run_seg(s, 2, "fp12_product", P, P_<uint32_t>(s->d_aux), P_<uint32_t>(s->d_F)));
     KL(s, "k_fp12_to_canon", lsgk::fp12_to_canon(S, (int)ng, P_<uint32_t>(s->d_F), P_<uint8_t>(s->d_Fb)));
-    KL(s, SERIAL_LABEL(final_exp), lsg_row_final_exp(S, (int)ng, P_<uint8_t>(s->d_Fb), P_<int32_t>(s->d_verdict)));
+    KL(s, "slp_final_exp", lsg_slp_final_exp(S, (int)ng, P_<uint8_t>(s->d_Fb), P_<int32_t>(s->d_verdict)));
     LSG_HIP(s, hipMemcpyAsync(s->h_verdict.p, s->d_verdict.p, 4 * ng, hipMemcpyDeviceToHost, S));
   } else {
     s->n_sets = 0;

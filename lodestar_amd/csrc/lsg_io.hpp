@@ -1,12 +1,12 @@
-// Canonical (big-endian, non-Montgomery) byte forms of tower and curve values, shared by the
-// translation units of the two Fp backends (lsg_bls.hip: quad, lsg_serial.hip: row).  These
-// 576/288-byte blobs are the hand-off format between backends and across GPUs (the Fp12
-// Miller partial of SURVEY.md 8e).
+// Canonical (big-endian, non-Montgomery) byte forms of tower and curve values.  These
+// 576/288-byte blobs are the hand-off format between the per-set kernels and the
+// straight-line programs (lsg_slp.hip) and across GPUs (the Fp12 Miller partial of
+// SURVEY.md 8e).
 #pragma once
 #include "lsg_pairing.hpp"
 
 // The conversions to and from Montgomery form are issued as one batch of independent
-// products (fp_mul_list): the row backend splits a batch over the rows that share an item.
+// products (fp_mul_list).
 template <int N>
 LSG_DEVI void fps_from_canon_bytes(fp_t* v, const uint8_t* b) {
   fp_t x[N], r2[N];

@@ -244,7 +244,7 @@ __global__ void LSG_KERNEL_ATTR k_g2p_compress(int n, const uint32_t* __restrict
   g2_compress(out96 + 96 * item, a, is_inf);
 }
 
-// projective G2 (lane form) -> canonical 288-byte blobs for the row-backend group stages
+// projective G2 (lane form) -> canonical 288-byte blobs for the per-group programs (lsg_slp.hip)
 __global__ void LSG_KERNEL_ATTR k_g2p_to_canon(int n, const uint32_t* __restrict__ in, uint8_t* __restrict__ out) {
   LANE_ITEM(n);
   (void)lead;

@@ -2,8 +2,8 @@
 //
 // Every per-set kernel runs the pair backend (lsg_fp_pair.hpp): one field element per lane
 // pair, so one work item (a set, a pubkey, a Miller item) is one pair and a wave64 carries
-// 32 items.  The math headers sit in an anonymous namespace: lsg_serial.hip instantiates the
-// same generic code over the row backend and the two fp_t must never meet at link time.
+// 32 items.  The math headers sit in an anonymous namespace: every translation unit has its
+// own copy of their non-inline functions, and the copies must never meet at link time.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

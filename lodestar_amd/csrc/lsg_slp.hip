@@ -9,13 +9,12 @@
 //   gather its operand forms (up to 7 slots each, 64-bit accumulation of coef * limb, one
 //   carry round), then LIN: store their sum; MUL: store the Montgomery product; LOADMUL:
 //   the product of the item's input Fp #j (read from global memory) with its B form.
-// A dependency chain of ~10^4 products thus runs in ~10^3 steps of one product each, where
-// the row kernels (lsg_serial.hip) spend ~2 us per dependent product.  Inputs and outputs are
-// the canonical byte blobs of lsg_io.hpp, exactly as for the row kernels.
+// A dependency chain of ~10^4 products thus runs in ~10^3 steps of one product each.  Inputs
+// and outputs are the canonical byte blobs of lsg_io.hpp.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "lsg_serial.h"
+#include "lsg_slp.h"
 #include "../../include/lodestar_bls.h"
 
 namespace {
@@ -68,9 +67,6 @@ LSG_SLP_PROG(SLP_G2_SCALE, g2_scale, G2_SCALE)
 // flight while the current step computes (the program lives in global memory / L2)
 template <class PR>
 __device__ __forceinline__ void slp_steps(uint32_t* lds, const uint8_t* inp, uint32_t q, uint32_t h) {
-#if LSG_SLP_PRIO  // A/B builds: issue priority of the programs' waves over co-resident kernels'
-  __builtin_amdgcn_s_setprio(LSG_SLP_PRIO);
-#endif
   const uint32_t* ops = PR::ops();
   const uint32_t* steps = PR::steps();
   uint32_t d = steps[0];

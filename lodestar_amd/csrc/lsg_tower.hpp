@@ -1,4 +1,4 @@
-// BLS12-381 extension tower, generic over the Fp backend (include lsg_fp_lane.hpp or
+// BLS12-381 extension tower, generic over the Fp backend (include lsg_fp_pair.hpp or
 // lsg_fp_elem.hpp first).
 //
 // Replaces the field layer of supranational blst (un-vendored; reached through
@@ -35,9 +35,6 @@ LSG_INL fp_t fp_from_be48(const uint8_t* b) { return fp_from_be_bytes(b, 12); }
 // wave takes the same branches; the table entry is picked with selects (no indexed
 // register access).
 LSG_BIGFN fp_t fp_pow_fixed(fp_t a, const uint32_t* e) {
-#ifdef LSG_POW_LEAF
-  return pair_pow_fixed(a, e);
-#else
   fp_t T[8];  // T[k] = a^(2k+1)
   T[0] = a;
   const fp_t a2 = fp_sqr(a);
@@ -67,7 +64,6 @@ LSG_BIGFN fp_t fp_pow_fixed(fp_t a, const uint32_t* e) {
     i = j - 1;
   }
   return r;
-#endif
 }
 
 // a^e for the three fixed exponents by id (LSG_POW_INV p-2, LSG_POW_SQRT (p+1)/4,
@@ -270,15 +266,6 @@ LSG_INL fp2_t fp2_mul_fp(const fp2_t& a, const fp_t& k) {
 // (fp_mul9 is one call with nine dependency chains in flight; the tail uses mul3/mul2/mul)
 template <int N>
 LSG_INL void fp_mul_list(fp_t* r, const fp_t* x, const fp_t* y) {
-#ifdef LSG_ROW_SPLIT
-#ifndef LSG_SPLIT_MIN
-#define LSG_SPLIT_MIN 4
-#endif
-  if (N >= LSG_SPLIT_MIN) {  // the rows (lane pairs) of a wave share one item: split the batch
-    fp_mul_list_rows<N>(r, x, y);
-    return;
-  }
-#endif
 #pragma unroll
   for (int g = 0; g + 9 <= N; g += 9) fp_mul9(r + g, x + g, y + g);
   constexpr int T = N % 9, B = N - T;

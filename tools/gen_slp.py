@@ -717,12 +717,14 @@ def proj_to_aff(E, p):
 
 
 def ml_neg_g1(E, S):
-    """ML(-G1, S) for S projective (lsg_serial.hip:44); the caller substitutes 1 when S = O"""
+    """ML(-G1, S) for S projective: the Miller loop at the negated G1 generator and S made
+    affine; the caller substitutes 1 when S = O"""
     return miller_loop(E, (E.const(G1X), E.const(P - G1Y)), proj_to_aff(E, S))
 
 
 def horner(Cs):
-    """S = sum_k 2^k C_k by Horner over the 64 per-bit sums (lsg_serial.hip:63)"""
+    """S = sum_k 2^k C_k by Horner over the 64 per-bit sums: from C_63 down, one complete
+    doubling and one complete addition per bit"""
     s = Cs[63]
     for k in range(62, -1, -1):
         s = g2_add(g2_dbl(s), Cs[k])
