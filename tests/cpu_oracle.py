@@ -30,6 +30,9 @@ def lib():
                                         ctypes.c_int, ctypes.c_int, ctypes.c_uint64, ctypes.POINTER(ctypes.c_int)]
         L.cpu_verify_sets.restype = ctypes.c_int
         L.cpu_verify_sets.argtypes = [ctypes.c_char_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint64]
+        L.cpu_hash_to_g2.restype = None
+        L.cpu_hash_to_g2.argtypes = [ctypes.c_char_p, ctypes.c_size_t, ctypes.c_char_p, ctypes.c_size_t,
+                                     ctypes.c_char_p]
         _lib = L
     return _lib
 
@@ -39,6 +42,14 @@ def threads():
     if env and env.isdigit() and int(env) > 0:
         return min(int(env), 32)
     return max(1, min(len(os.sched_getaffinity(0)), 32))
+
+
+def hash_to_g2(msg, dst):
+    """The 192 bytes of hash_to_G2(msg) under dst (any lengths; tests/test_msg_lengths_host.py
+    pins this against the Python oracle and hashlib over tests/msglens.py's cases)."""
+    out = ctypes.create_string_buffer(192)
+    lib().cpu_hash_to_g2(msg, len(msg), dst, len(dst), out)
+    return out.raw
 
 
 def verify_each(pks96, msgs, sigs):

@@ -576,6 +576,31 @@ def test_the_sample_rule(driver):
     assert exp[3]["res"][3:5] == [298, 1]
 
 
+def test_messages_that_differ_only_in_length(driver):
+    """m, m || 0x00, m || 0x00 0x00, m[:-1] and the empty message are five messages to the table and
+    to the cache (a hit on m and on m || 0x00 leaves the other two siblings misses); staged back
+    to back at 33, 34, 35 and 32 bytes, every later message starts at an odd offset; the cache
+    takes 191 and 192 bytes and lets 193 pass"""
+    m, long_msg = rbytes(33), rbytes(193)
+    sib = [m, m + b"\0", m + b"\0\0", m[:-1], b""]
+    sets = [keys_set(sib[i % 5]) for i in range(20)]
+    edge = [keys_set(long_msg[:191]), keys_set(long_msg[:192]), keys_set(long_msg), keys_set(long_msg[:192] + b"\xff"),
+            keys_set(long_msg[:191])]
+    k = lambda x: msg_key(x, len(x))  # noqa: E731
+    primed = [("lookup", k(sib[0]), sib[0], False), ("allot", k(sib[0]), sib[0], False), ("publish", [0]),
+              ("lookup", k(sib[1]), sib[1], False), ("allot", k(sib[1]), sib[1], False), ("publish", [1])]
+    exp = check(driver, [Case(sets, dedup=True), Case(sets, dedup=False), Case(sets + edge, dedup=True, cache=16),
+                         Case(sets + edge, dedup=True, cache=16, cache_ops=primed)])
+    assert exp[0]["msg_id"] == [i % 5 for i in range(20)] and exp[0]["res"][3:5] == [5, 1]
+    assert exp[1]["res"][3:5] == [20, 0]
+    # the 191-byte message repeats; lookups: the four siblings with bytes, 191 and 192; the empty
+    # message and the two of 193 bytes bypass
+    assert exp[2]["msg_id"][20:] == [5, 6, 7, 8, 5] and exp[2]["res"][3] == 9 and exp[2]["res"][8:11] == [1, 9, 0]
+    assert exp[2]["mcstats"][:6] == [6, 0, 0, 6, 0, 3]
+    assert exp[3]["res"][8:11] == [1, 7, 2] and exp[3]["pins"] == [0, 1]
+    assert exp[3]["mcstats"][:6] == [8, 2, 0, 6, 0, 3]
+
+
 # ---------------------------------------------------------------- the message cache
 def test_cache_hit_miss_pending_full_and_bypass(driver):
     m = msgs(8)
