@@ -163,25 +163,26 @@ LSG_INL proj_t<F> proj_add_mixed(const proj_t<F>& p, const aff_t<F>& q) {
   return r;
 }
 
-// RCB 2016 algorithm 9 (doubling, a = 0)
+// RCB 2016 algorithm 9 (doubling, a = 0): the same X3, Y3, Z3 from 3 products and 5 squares
+// instead of 6 and 3.  With B = Y^2, C = Z^2, E = 3b C:
+//   2YZ = (Y + Z)^2 - B - C,   Z3 = 8 B YZ = 4B 2YZ,   X3 = 2 (B - 3E) XY,
+//   Y3 = (B - 3E)(B + E) + 8 B E = (B + 3E)^2 - 12 E^2.
+// Complete as algorithm 9 is: these are its field elements, not another scaling.
+// Every sum is a lazy sum whose carry is checked by the static_asserts of carry() and
+// carry_mul<K>() (lsg_fp_pair.hpp, lsg_fp2_lanes.hpp): (1, 3) for B - 3E, (2, 1) for 2B - s0,
+// (1, 2) for the cross term, and 4 x, 12 x, 2 x of one carried value.
 template <class F>
 LSG_INL proj_t<F> proj_dbl(const proj_t<F>& p) {
-  F t0 = fsqr(p.Y);
-  F Z3 = fmulk<8>(t0);
-  F t1 = fmul(p.Y, p.Z);
-  F t2 = fmul_b3(fsqr(p.Z));
-  F X3 = fmul(t2, Z3);
-  F Y3 = fadd(t0, t2);
-  Z3 = fmul(t1, Z3);
-  t0 = fsub(t0, fmulk<3>(t2));  // (as one lazy sum t0 - 3 t2, k_sign's scratch grew: 912 -> 944 B)
-  Y3 = fmul(t0, Y3);
-  Y3 = fadd(X3, Y3);
-  t1 = fmul(p.X, p.Y);
-  X3 = fmulk<2>(fmul(t0, t1));
+  const F B = fsqr(p.Y);
+  const F C = fsqr(p.Z);
+  const F yz2 = fsub2(fsqr(fadd(p.Y, p.Z)), B, C);
+  const F E = fmul_b3(C);
   proj_t<F> r;
-  r.X = X3;
-  r.Y = Y3;
-  r.Z = Z3;
+  r.Z = fmul(fmulk<4>(B), yz2);
+  const F s0 = (fsum(B) - fsum_mulk<3>(fsum(E))).carry();  // B - 3E
+  const F s1 = (fsum_mulk<2>(fsum(B)) - s0).carry();        // B + 3E = 2B - (B - 3E)
+  r.Y = fsub(fsqr(s1), fmulk<12>(fsqr(E)));
+  r.X = fmulk<2>(fmul(s0, fmul(p.X, p.Y)));
   return r;
 }
 
@@ -197,12 +198,17 @@ LSG_INL g1p_t gadd(const g1p_t& p, const g1p_t& q) { return g1_add(p, q); }
 LSG_INL g2p_t gadd(const g2p_t& p, const g2p_t& q) { return g2_add(p, q); }
 LSG_INL g1p_t gdbl(const g1p_t& p) { return g1_dbl(p); }
 LSG_INL g2p_t gdbl(const g2p_t& p) { return g2_dbl(p); }
+// an affine (finite) second operand takes the mixed addition: algorithm 7's values with Z = 1
+LSG_INL g1p_t gadd(const g1p_t& p, const g1a_t& q) { return g1_add_mixed(p, q); }
+LSG_INL g2p_t gadd(const g2p_t& p, const g2a_t& q) { return g2_add_mixed(p, q); }
 #ifdef LSG_FP2_LANES
 // G2 points with their coordinates in the component-per-lane layout: the same formulas
 typedef aff_t<fp2v_t> g2va_t;
 typedef proj_t<fp2v_t> g2vp_t;
 LSG_BIGFN g2vp_t g2v_add(g2vp_t p, g2vp_t q) { return proj_add(p, q); }
+LSG_BIGFN g2vp_t g2v_add_mixed(g2vp_t p, g2va_t q) { return proj_add_mixed(p, q); }
 LSG_INL g2vp_t gadd(const g2vp_t& p, const g2vp_t& q) { return g2v_add(p, q); }
+LSG_INL g2vp_t gadd(const g2vp_t& p, const g2va_t& q) { return g2v_add_mixed(p, q); }
 LSG_INL g2va_t g2v_from_pair(const g2a_t& a) { return g2va_t{fp2v_from_pair(a.x), fp2v_from_pair(a.y)}; }
 LSG_INL g2vp_t g2v_from_pair(const g2p_t& p) {
   return g2vp_t{fp2v_from_pair(p.X), fp2v_from_pair(p.Y), fp2v_from_pair(p.Z)};
@@ -287,11 +293,14 @@ LSG_BIGFN jac_t<fp2_t> jac_dbl(jac_t<fp2_t> p) { return jac_dbl_t(p); }
 LSG_BIGFN jac_t<fp2v_t> jac_dbl(jac_t<fp2v_t> p) { return jac_dbl_t(p); }
 #endif
 
-// acc (Jacobian) + q (homogeneous) through the complete RCB addition
-template <class F>
-LSG_INL jac_t<F> jac_add_proj(const jac_t<F>& acc, const proj_t<F>& q) {
+// acc (Jacobian) + q (homogeneous, or affine and finite) through the complete RCB addition
+template <class F, class Q>
+LSG_INL jac_t<F> jac_add_proj(const jac_t<F>& acc, const Q& q) {
   return jac_from_proj(gadd(jac_to_proj(acc), q));
 }
+// the base point of a chain as a homogeneous point, whichever form its getter returns
+template <class F> LSG_INL const proj_t<F>& proj_of(const proj_t<F>& p) { return p; }
+template <class F> LSG_INL proj_t<F> proj_of(const aff_t<F>& a) { return proj_from_aff(a); }
 
 // [k]P for a 64-bit scalar k (per lane), 4-bit fixed windows: 60 Jacobian doublings and 16
 // complete additions of a table entry T[d] = [d]P (T[0] = O), selected per row.
@@ -319,7 +328,7 @@ LSG_INL proj_t<F> proj_mul_u64(const proj_t<F>& p, uint64_t k) {
 
 // [k]P for a 64-bit scalar k, signed 3-bit windows: k = sum_{i<22} d_i 8^i with d_i in
 // [-4, 3] (d_21 in [0, 2]), table T[1..4] = [1..4]P held in registers and picked with selects
-// (a per-lane indexed table lives in scratch).  63 Jacobian doublings and 21 complete
+// (a per-lane indexed table lives in scratch).  63 doublings and 21 complete
 // additions, plus 2 doublings and 1 addition for the table (the 4-bit form: 61 + 29).
 template <class F>
 LSG_INL proj_t<F> proj_pick_signed(const proj_t<F>& T1, const proj_t<F>& T2, const proj_t<F>& T3,
@@ -338,6 +347,12 @@ LSG_INL proj_t<F> proj_pick_signed(const proj_t<F>& T1, const proj_t<F>& T2, con
   r.Y = fselect(d < 0, fneg(r.Y), r.Y);
   return r;
 }
+// Over Fp (k_pk_scale) the chain stays homogeneous.  Over Fp2 (k_sig_scale3, the window table
+// in 512 registers at one wave per SIMD) the homogeneous loop took 80 B of scratch per lane where
+// the Jacobian doublings with conversions around each addition take none: it keeps those
+// (DESIGN section 5 has the compiler's report).
+template <class F> struct s3_homogeneous { static constexpr bool value = false; };
+template <> struct s3_homogeneous<fp_t> { static constexpr bool value = true; };
 template <class F>
 LSG_INL proj_t<F> proj_mul_u64_s3(const proj_t<F>& p, uint64_t k) {
   const proj_t<F> T2 = gdbl(p);
@@ -353,25 +368,40 @@ LSG_INL proj_t<F> proj_mul_u64_s3(const proj_t<F>& p, uint64_t k) {
   auto digit = [&](int i) {
     return (int)((k >> (3 * i)) & 7u) + (int)((cm >> i) & 1u) - (i < 21 ? 8 * (int)((cm >> (i + 1)) & 1u) : 0);
   };
-  jac_t<F> acc = jac_from_proj(proj_pick_signed(p, T2, T3, T4, digit(21)));
+  if constexpr (s3_homogeneous<F>::value) {
+    // three doublings of one product more each than the Jacobian ones cost less than the two
+    // conversions around the addition (4 products and 2 squares): no Jacobian form at all
+    proj_t<F> acc = proj_pick_signed(p, T2, T3, T4, digit(21));
 #pragma unroll 1
-  for (int i = 20; i >= 0; i--) {
-    acc = jac_dbl(acc);
-    acc = jac_dbl(acc);
-    acc = jac_dbl(acc);
-    acc = jac_add_proj(acc, proj_pick_signed(p, T2, T3, T4, digit(i)));
+    for (int i = 20; i >= 0; i--) {
+      acc = gdbl(acc);
+      acc = gdbl(acc);
+      acc = gdbl(acc);
+      acc = gadd(acc, proj_pick_signed(p, T2, T3, T4, digit(i)));
+    }
+    return acc;
+  } else {
+    jac_t<F> acc = jac_from_proj(proj_pick_signed(p, T2, T3, T4, digit(21)));
+#pragma unroll 1
+    for (int i = 20; i >= 0; i--) {
+      acc = jac_dbl(acc);
+      acc = jac_dbl(acc);
+      acc = jac_dbl(acc);
+      acc = jac_add_proj(acc, proj_pick_signed(p, T2, T3, T4, digit(i)));
+    }
+    return jac_to_proj(acc);
   }
-  return jac_to_proj(acc);
 }
 
 // [|x|]P for the BLS parameter |x| = 0xd201000000010000 (public, uniform branch):
 // 63 Jacobian doublings, 5 complete additions
 // The base point comes from get() at each addition: a per-set kernel keeps it in LDS
 // (lsg_kcommon.hpp lds_park) so that the doubling chain holds one point in registers.
+// get() may return the base point affine (and finite): the additions are then the mixed ones.
 template <class F, class G>
 LSG_INL proj_t<F> proj_mul_xabs_get(const G& get) {
   const uint64_t xa = ((uint64_t)LSG_X_ABS_HI << 32) | LSG_X_ABS_LO;
-  jac_t<F> acc = jac_from_proj(get());
+  jac_t<F> acc = jac_from_proj(proj_of<F>(get()));
 #pragma unroll 1
   for (int b = 62; b >= 0; b--) {
     acc = jac_dbl(acc);
@@ -448,9 +478,9 @@ LSG_INL g2p_t g2_psi2(const g2p_t& p) {
 // (F: the layout the chain runs in, get()'s coordinates; the comparison is in the pair form)
 template <class F = fp2_t, class G>
 LSG_INL bool g2_in_group_get(const G& get) {
-  if (proj_is_inf(get())) return true;
+  if (proj_is_inf(proj_of<F>(get()))) return true;
   const proj_t<F> xp = proj_neg(proj_mul_xabs_get<F>(get));
-  return proj_eq(g2_psi(g2_to_pair(get())), g2_to_pair(xp));
+  return proj_eq(g2_psi(g2_to_pair(proj_of<F>(get()))), g2_to_pair(xp));
 }
 LSG_BIGFN bool g2_in_group(g2p_t p) {
   return g2_in_group_get([&]() { return p; });

@@ -366,13 +366,14 @@ LSG_DEVI void mf_mul_pair(uint32_t* lds, int w, int k) {
   __syncthreads();
 }
 
-// L phase steps with their values staged through LDS: ml_dbl_step_raw / ml_add_step_raw +
-// line_eval (lsg_pairing.hpp), the same formulas in the same order, but each line
-// coefficient is evaluated at P and written to its slot as soon as it exists, and T's
-// coordinates go back to their slots as soon as they are final.  Computed first and written
-// last (ml_dbl_step_raw + line_eval, the split kernels' steps, once an alternative here), the
-// line's three Fp2 values were live across the remaining point products and went to scratch
-// (176 B per lane).
+// L phase steps with their values staged through LDS: the values of ml_dbl_step_raw /
+// ml_add_step_raw + line_eval (lsg_pairing.hpp), but each line coefficient is evaluated at P and
+// written to its slot as soon as it exists, and T's coordinates go back to their slots as soon
+// as they are final.  Computed first and written last (ml_dbl_step_raw + line_eval, the split
+// kernels' steps, once an alternative here), the line's three Fp2 values were live across the
+// remaining point products and went to scratch (176 B per lane).  The addition step keeps
+// ml_add_step_raw's formulas in their order; the doubling step is ml_dbl_line_sq
+// (lsg_pairing.hpp): the same field elements from 2 products and 7 squares.
 template <class F>
 LSG_DEVI void mf_put_line(uint32_t* lds, int wl, bool use, const F& l00, const F& l01P, const F& l11P) {
   mf_put2(lds, MF_LC(wl, 0), fselect(use, l00, mf_layout<F>::one()));
@@ -382,27 +383,15 @@ LSG_DEVI void mf_put_line(uint32_t* lds, int wl, bool use, const F& l00, const F
 template <class F>
 LSG_DEVI void mf_dbl_line(uint32_t* lds, int wl, bool use, const uint32_t* __restrict__ P, size_t sl) {
   const int tb = MF_T + 6 * wl;
-  F t0, t1, t2, v1;
-  {
-    const F X = mf_get2<F>(lds, tb), Y = mf_get2<F>(lds, tb + 2), Z = mf_get2<F>(lds, tb + 4);
-    t0 = fsqr(Y);
-    t1 = fmul(Y, Z);
-    t2 = fmul_b3(fsqr(Z));
-    const F XX = fsqr(X);
-    v1 = fmul(X, Y);
-    const g1a_t Pk = lane_load<g1a_t>(P, sl);
-    mf_put_line(lds, wl, use, fsub(t2, t0), fmul_fp(fmulk<3>(XX), mf_layout<F>::fp_in(Pk.x)),
-                fmul_fp((-fsum(t1)).template carry_mul<2>(), mf_layout<F>::fp_in(Pk.y)));
-  }
-  F Z3 = fmulk<8>(t0);
-  F X3 = fmul(t2, Z3);
-  F Y3 = fadd(t0, t2);
-  mf_put2(lds, tb + 4, fmul(t1, Z3));
-  const F s0 = (fsum(t0) - fsum_mulk<3>(fsum(t2))).carry();  // t0 - 3 t2
-  Y3 = fmul(s0, Y3);
-  mf_put2(lds, tb + 2, fadd(X3, Y3));
-  X3 = fmul(s0, v1);
-  mf_put2(lds, tb, fmulk<2>(X3));
+  ml_dbl_line_sq<F>(
+      [&]() { return proj_t<F>{mf_get2<F>(lds, tb), mf_get2<F>(lds, tb + 2), mf_get2<F>(lds, tb + 4)}; },
+      [&]() { return lane_load<g1a_t>(P, sl); }, [](const fp_t& a) { return mf_layout<F>::fp_in(a); },
+      [&](int slot, const F& v) {
+        if (slot < 3)  // a line coefficient: the identity line (1, 0, 0) for a pair that does not contribute
+          mf_put2(lds, MF_LC(wl, slot), fselect(use, v, slot == 0 ? mf_layout<F>::one() : fzero<F>()));
+        else
+          mf_put2(lds, tb + 2 * (slot - 3), v);
+      });
 }
 template <class F>
 LSG_DEVI void mf_add_line(uint32_t* lds, int wl, bool use, const uint32_t* __restrict__ P, const uint32_t* __restrict__ H,

@@ -117,7 +117,8 @@ LSG_DEVI void sig_subgroup_item(uint32_t* park, int n, const uint32_t* __restric
   LANE_ITEM(n);
   if (err[item] != 0 || inf[item]) return;
   lds_park(park, g2_layout<F>::in(lane_load<g2a_t>(sig_aff, item)));
-  bool ok = g2_in_group_get<F>([&]() { return proj_from_aff(lds_unpark<aff_t<F>>(park)); });
+  // the parked point is affine and finite: the chain's five additions are mixed ones
+  bool ok = g2_in_group_get<F>([&]() { return lds_unpark<aff_t<F>>(park); });
   if (lead && !ok) err[item] = LSG_BLST_POINT_NOT_IN_GROUP;
 }
 __global__ void LSG_KERNEL_ATTR k_sig_subgroup(int n, const uint32_t* __restrict__ sig_aff,

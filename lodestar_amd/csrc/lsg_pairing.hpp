@@ -69,6 +69,38 @@ LSG_INL line_t line_eval(line_t L, const fp_t& xP, const fp_t& yP) {
   return L;
 }
 
+// The doubling step of the fused Miller kernel (lsg_k_miller.hip mf_dbl_line): the field elements
+// of ml_dbl_step_raw + line_eval from 2 products and 7 squares (there: 6 and 3), over either Fp2
+// layout F.  With B = Y^2, C = Z^2, J = X^2, E = 3b' C:
+//   2YZ = (Y + Z)^2 - B - C,   2XY = (X + Y)^2 - J - B,
+//   X3 = (B - 3E) 2XY,   Z3 = 4B 2YZ,   Y3 = (B + 3E)^2 - 12 E^2  (= (B - 3E)(B + E) + 8 B E);
+//   the line at P is (E - B, 3J xP, 2YZ (-yP)), the sign of its last coefficient taken on yP.
+// getT() gives T, getP() the G1 point (read late: after the squares), fp_in(a) an Fp value in the
+// form F's product by Fp takes.  put(slot, v) receives each value as soon as it exists: slots
+// 0..2 the line's coefficients, 3..5 the new X, Y, Z -- in the order Z, X, Y.
+template <class F, class GetT, class GetP, class FpIn, class Put>
+LSG_INL void ml_dbl_line_sq(const GetT& getT, const GetP& getP, const FpIn& fp_in, const Put& put) {
+  F B, E, yz2, xy2;
+  {
+    const proj_t<F> T = getT();
+    B = fsqr(T.Y);
+    const F C = fsqr(T.Z);
+    yz2 = fsub2(fsqr(fadd(T.Y, T.Z)), B, C);
+    E = fmul_b3(C);
+    const F J = fsqr(T.X);
+    xy2 = fsub2(fsqr(fadd(T.X, T.Y)), J, B);
+    const g1a_t Pk = getP();
+    put(0, fsub(E, B));
+    put(1, fmul_fp(fmulk<3>(J), fp_in(Pk.x)));
+    put(2, fmul_fp(yz2, fp_in(fp_neg(Pk.y))));
+  }
+  put(5, fmul(fmulk<4>(B), yz2));
+  const F s0 = (fsum(B) - fsum_mulk<3>(fsum(E))).carry();  // B - 3E
+  put(3, fmul(s0, xy2));
+  const F s1 = (fsum_mulk<2>(fsum(B)) - s0).carry();  // B + 3E = 2B - (B - 3E)
+  put(4, fsub(fsqr(s1), fmulk<12>(fsqr(E))));
+}
+
 // ---- Output combinations of the fused Miller kernel's phases (lsg_k_miller.hip: mf_sqr,
 // mf_pair_lines, mf_mul_pair), as functions of the phase's Fp2 products V(p).  Each output
 // coefficient is one linear combination of up to 11 products and their xi multiples; written
