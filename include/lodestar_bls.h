@@ -618,6 +618,22 @@ int lsg_check_mf_lanes(lsg_ctx* ctx, const uint32_t* in, size_t n, uint32_t* out
  * word.  LSG_ERR_INVALID_ARG for another id.  Tests only. */
 int lsg_check_pow_lanes(lsg_ctx* ctx, int32_t id, const uint32_t* in, size_t n, uint32_t* out);
 int lsg_check_pow_pair(lsg_ctx* ctx, int32_t id, const uint32_t* in, size_t n, uint32_t* out);
+/* lsg_check_msm_buckets: the bucket pass of the signature MSM on the caller's points, flags, index
+ * list and chunk triples.  sigs96: n compressed G2 points, decoded without the subgroup check
+ * (every one must decode); err / inf / pinf: the n per-point flags the pass sees in place of the
+ * decode's own (a point with any of them set adds nothing); idx: the list of n_idx point numbers;
+ * chunks: n_chunks triples {off, len, out} of the first pass, 2^ips_log2 lane pairs each
+ * (ips_log2 <= 5), summing idx[off .. off + len) into output `out` >= 0 or into partial sum
+ * -out - 1 < n_tmp; chunks2 (n_chunks2 may be 0): the triples of a second pass over the partial
+ * sums off .. off + len, outputs only.  Every partial sum and every one of the n_out outputs must
+ * be written exactly once.  mode 0: k_msm_bucket_seg (the fold with one Fp2 component per lane),
+ * 1: its pair-form twin, 2: projective copies (k_sig_proj) summed by k_seg_reduce<1>.  out96: the
+ * n_out sums, compressed (projective representatives differ between the modes).
+ * LSG_ERR_INVALID_ARG for anything out of range.  Tests only. */
+int lsg_check_msm_buckets(lsg_ctx* ctx, int32_t mode, const uint8_t* sigs96, size_t n, const int32_t* err,
+                          const uint8_t* inf, const uint8_t* pinf, const int32_t* idx, size_t n_idx,
+                          const int32_t* chunks, size_t n_chunks, int32_t ips_log2, const int32_t* chunks2,
+                          size_t n_chunks2, int32_t ips_log2_2, size_t n_tmp, size_t n_out, uint8_t* out96);
 /* Parity hooks of the layer between the products and the accept / reject rules (tests only;
  * none is on the verification path).  Elements travel in the pair layout above: 14 words, limb
  * L at word 2 (L mod 7) + L / 7.  Each returns LSG_ERR_INVALID_ARG for a null pointer with a

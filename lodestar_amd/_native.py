@@ -218,7 +218,7 @@ EXPORTS = [
     "lsg_set_coalesce", "lsg_aggregate_pubkeys_multi", "lsg_check_fp2_mul",
     "lsg_check_fp_sqr", "lsg_check_fp2_sqr", "lsg_check_sums", "lsg_check_fp2_lanes", "lsg_check_g2_lanes", "lsg_check_mf_lanes",
     "lsg_check_canon", "lsg_check_fp2_roots", "lsg_check_batch_inv", "lsg_check_map_uniform",
-    "lsg_check_batch_partial_rnd", "lsg_check_pow_lanes", "lsg_check_pow_pair",
+    "lsg_check_batch_partial_rnd", "lsg_check_pow_lanes", "lsg_check_pow_pair", "lsg_check_msm_buckets",
     "lsg_deposit_signing_roots", "lsg_verify_deposits",
     "lsg_committees_set", "lsg_committees_clear", "lsg_committee_count",
     "lsg_object_signing_roots", "lsg_object_signing_roots_var",
@@ -306,6 +306,9 @@ def load_library(path=LIB_PATH):
         lib.lsg_check_mf_lanes.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_pow_lanes.argtypes = [vp, i32, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_pow_pair.argtypes = [vp, i32, ctypes.c_char_p, sz, ctypes.c_char_p]
+        lib.lsg_check_msm_buckets.argtypes = [vp, i32, ctypes.c_char_p, sz, ctypes.c_char_p, ctypes.c_char_p,
+                                              ctypes.c_char_p, ctypes.c_char_p, sz, ctypes.c_char_p, sz, i32,
+                                              ctypes.c_char_p, sz, i32, sz, sz, ctypes.c_char_p]
         lib.lsg_check_canon.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p, sz, ctypes.c_char_p, ctypes.c_char_p]
         lib.lsg_check_fp2_roots.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
         lib.lsg_check_batch_inv.argtypes = [vp, ctypes.c_char_p, sz, ctypes.c_char_p]
@@ -956,6 +959,24 @@ class Context:
         src = struct.pack(f"<{len(words)}I", *words)
         self._check(getattr(self.lib, fn)(self.h, pow_id, src, n, out), fn)
         return list(struct.unpack(f"<{14 * n}I", out.raw[:4 * 14 * n]))
+
+    def check_msm_buckets(self, mode, sigs, err, inf, pinf, idx, chunks, ips_log2, n_out, chunks2=(), ips_log2_2=0,
+                          n_tmp=0):
+        """lsg_check_msm_buckets: `sigs` = compressed G2 points, err / inf / pinf = their flags, idx =
+        the index list, chunks / chunks2 = (off, len, out) triples of the two passes; returns the
+        n_out bucket sums, 96 bytes each.  mode 0 / 1: the fold kernel in the lane / pair layout,
+        2: projective copies and the segmented reduction."""
+        n = len(sigs)
+        assert len(err) == len(inf) == len(pinf) == n and all(len(b) == 96 for b in sigs)
+        flat = [v for t in chunks for v in t]
+        flat2 = [v for t in chunks2 for v in t]
+        out = ctypes.create_string_buffer(96 * max(n_out, 1))
+        rc = self.lib.lsg_check_msm_buckets(
+            self.h, mode, b"".join(sigs), n, struct.pack(f"<{n}i", *err), bytes(inf), bytes(pinf),
+            struct.pack(f"<{len(idx)}i", *idx), len(idx), struct.pack(f"<{len(flat)}i", *flat), len(chunks), ips_log2,
+            struct.pack(f"<{len(flat2)}i", *flat2), len(chunks2), ips_log2_2, n_tmp, n_out, out)
+        self._check(rc, "lsg_check_msm_buckets")
+        return [out.raw[96 * k:96 * k + 96] for k in range(n_out)]
 
     def check_canon(self, words, strings=()):
         """lsg_check_canon: `words` = 14 u32 per raw element, `strings` = 48-byte strings.  Returns

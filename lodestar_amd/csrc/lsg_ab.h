@@ -13,6 +13,13 @@
 #define LSG_POW_LANES_DEFAULT 1
 #define LSG_POW_LANES_MIN_DEFAULT 65536
 
+// The bucket pass of the signature MSM (lsg_host.hip run_msm_buckets, lsg_plan.hpp plan_buckets):
+// LSG_MSM_FOLD=0 in the A/B build runs it as k_sig_proj + k_seg_reduce<1> on plan_seg's plan instead
+// of k_msm_bucket_seg on plan_buckets'; LSG_MSM_IPS=<0..5> forces the latter's lane pairs per bucket
+// (log2) for sweeps (profiles/r21_msmfold_ips_sweep.jsonl)
+#define LSG_MSM_FOLD_DEFAULT 1
+#define LSG_MSM_IPS_DEFAULT (-1)
+
 #ifdef LSG_AB
 // integer switch `name`, `dflt` when unset
 static inline long lsg_ab_long(const char* name, long dflt) {

@@ -236,6 +236,34 @@ typedef fp2v_t chain_fp2_t;  // the layout of k_sig_subgroup's [x] chain
 typedef fp2_t chain_fp2_t;
 #endif
 
+// One lane pair's share of a segmented G2 sum over affine points (the bucket pass of the
+// signature MSM, k_msm_bucket_seg): members first, first + step, ... below len, folded in the
+// layout F.  fetch(k, a) reads member k in the pair form and says whether it takes part; the
+// next member's fetch is issued before this one is added.  The first member that takes part
+// enters as (x : y : 1), every later one by the mixed addition, which is complete in its
+// projective operand: a sum that came back to the identity goes on from there.
+template <class F, class FETCH>
+LSG_INL proj_t<F> g2_fold_mixed(int first, int step, int len, FETCH&& fetch) {
+  proj_t<F> acc = proj_inf<F>();
+  bool any = false, use = false;
+  g2a_t a;
+  a.x = fzero<fp2_t>();
+  a.y = fzero<fp2_t>();
+  if (first < len) use = fetch(first, a);
+#pragma unroll 1
+  for (int k = first; k < len; k += step) {
+    const g2a_t cur = a;
+    const bool cur_use = use;
+    if (k + step < len) use = fetch(k + step, a);
+    if (cur_use) {
+      const aff_t<F> q = g2_layout<F>::in(cur);
+      acc = any ? gadd(acc, q) : proj_from_aff(q);
+      any = true;
+    }
+  }
+  return acc;
+}
+
 // ---- Jacobian doubling chains.  A doubling in Jacobian coordinates (x = X/Z^2, y = Y/Z^3;
 // dbl-2009-l, a = 0: 1M + 5S) costs 13 Fp multiplications over Fp2 against 22 for the
 // complete RCB doubling, and it is exact for every input of these curves: the point at

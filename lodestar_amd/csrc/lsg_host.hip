@@ -227,7 +227,7 @@ struct Slot : Staged {
   DevBuf d_lines;
   bool rs2_ready = false;
   std::vector<uint8_t> rs2_scaled;  // per set: [r_i] sig_i is in d_rs2 (fallback phases share it)
-  std::vector<uint8_t> rs_raw;      // per set: d_rs holds the unscaled point (a phase-A MSM group's)
+  std::vector<uint8_t> rs_raw;      // per set: it was in a phase-A MSM group (LSG_MSM_FOLD=0: d_rs holds its unscaled point)
   // groups
   DevBuf d_S, d_F, d_verdict, d_Sb, d_fgb, d_Fb, d_bkt, d_bits, d_aux, d_gath, d_nodeF, d_nodeV;
   DevBuf seg_tmp[3][2];  // reduction scratch per use: [0] pubkeys, [1] signature sums, [2] Fp12 products
@@ -668,6 +668,8 @@ Switches read_switches() {
   w.b0_run = (size_t)std::max(2L, lsg_ab_long("LSG_B0_RUN", 4));
   w.seg_fold_wide = (int)lsg_ab_long("LSG_SEG_FOLD_WIDE", SEG_FOLD_WIDE);
   w.slp_items = slp_items_max();
+  w.msm_fold = lsg_ab_long("LSG_MSM_FOLD", LSG_MSM_FOLD_DEFAULT) != 0;
+  w.msm_ips = (int)std::max(-1L, std::min(lsg_ab_long("LSG_MSM_IPS", LSG_MSM_IPS_DEFAULT), 5L));
   return w;
 }
 // plan_seg for a slot's plan arena
@@ -1120,9 +1122,32 @@ int launch_accum(Slot* s, size_t n_items, size_t item_off, uint32_t* fall, bool 
   return LSG_OK;
 }
 
+// The bucket sums of the phase's MSM groups: the first pass folds the resident affine signatures
+// themselves (lsg_k_sig.hip k_msm_bucket_seg on plan_buckets' plan), buckets longer than a chunk
+// finish through k_seg_reduce<1>; compare run_pk_seg.  LSG_MSM_FOLD=0 (A/B build): the passes of
+// plan_seg over the projective copies in rs_msm (k_sig_proj).
+int run_msm_buckets(Slot* s, const SegPlan& P, const uint32_t* rs_msm, uint32_t* dst) {
+  if (!s->sw.msm_fold) return run_seg(s, 1, "msm_buckets", P, rs_msm, dst);
+  LSG_RC(size_seg(s, 1, P));
+  uint32_t* tmp[3] = {nullptr, P_<uint32_t>(s->seg_tmp[1][0]), P_<uint32_t>(s->seg_tmp[1][1])};
+  for (size_t k = 0; k < P.passes.size(); k++) {
+    const SegPass& q = P.passes[k];
+    if (k == 0)
+      KL(s, "msm_buckets", lsgk::msm_bucket_seg(S_(s), q.n_chunks, q.ips_log2, PL(s, q.chunk_off), PL(s, P.idx_off),
+                                                P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
+                                                P_<int32_t>(s->d_seterr), P_<uint8_t>(s->d_pinf), dst, tmp[q.tmp_out],
+                                                !fp2_lanes_on()));
+    else
+      KL(s, "msm_buckets", lsgk::seg_reduce(S_(s), 1, q.n_chunks, q.ips_log2, PL(s, q.chunk_off), nullptr, tmp[q.src],
+                                            dst, tmp[q.tmp_out]));
+  }
+  return LSG_OK;
+}
+
 // side stream: signature sums -> ML(-G1, S_g) -> fall slots; main stream: products, export, FE
 // rs: the scaled points [r_i] sig_i the plain groups sum; rs_msm: the unscaled points the
-// bucket MSM groups read (phase A: one buffer holds both kinds, by set)
+// bucket MSM groups read where their bucket pass reads projective copies (LSG_MSM_FOLD=0; phase
+// A: one buffer holds both kinds, by set) -- the shipped bucket pass reads d_sigaff itself
 int launch_phase(Slot* s, const PhasePlan& Ph, const uint32_t* rs, uint32_t* fall, bool export_blobs,
                  const uint32_t* rs_msm = nullptr) {
   if (!rs_msm) rs_msm = rs;
@@ -1131,7 +1156,7 @@ int launch_phase(Slot* s, const PhasePlan& Ph, const uint32_t* rs, uint32_t* fal
   LSG_RC(size_state(s, s->n_sets, s->n_pks, ng, Ph.n_msm, 2));
   s->cur = 1;
   if (Ph.n_msm) {
-    LSG_RC(run_seg(s, 1, "msm_buckets", Ph.buckets, rs_msm, P_<uint32_t>(s->d_bkt)));
+    LSG_RC(run_msm_buckets(s, Ph.buckets, rs_msm, P_<uint32_t>(s->d_bkt)));
     LSG_RC(run_seg(s, 1, "msm_bits", Ph.bits, P_<uint32_t>(s->d_bkt), P_<uint32_t>(s->d_bits)));
     KL(s, "k_g2p_to_canon", lsgk::g2p_to_canon(S_(s), (int)(MSM_BITS * Ph.n_msm), P_<uint32_t>(s->d_bits),
                                                P_<uint8_t>(s->d_Sb)));
@@ -1607,7 +1632,9 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
   const uint64_t th2 = trace_host() ? now_ns() : 0;
   LSG_RC(launch_set_stages(s, &s->pkagg, A, P_<uint32_t>(s->d_fall)));
   const uint64_t th3 = trace_host() ? now_ns() : 0;
-  // signature points: unscaled for MSM groups, [r_i] sig_i for the rest
+  // signature points: [r_i] sig_i for the groups that sum scaled points; the MSM groups' bucket
+  // pass reads the affine signatures, so a package of MSM groups alone prepares none (rs_raw: the
+  // set was in an MSM group here, so a fallback group of such sets may run its own bucket MSM)
   s->rs_raw.assign(s->n_sets, 0);
   for (size_t g = 0; g < A.n_msm; g++) memset(s->rs_raw.data() + A.groups[g].first, 1, A.groups[g].len);
   if (!A.groups.empty()) {
@@ -1618,7 +1645,8 @@ int pkg_part1(Slot* s, const lsg_job* jobs, const std::vector<size_t>& ids, uint
       for (size_t g = A.n_msm; g < A.groups.size(); g++)
         memset(mode.data() + A.groups[g].first, 1, A.groups[g].len);
     }
-    LSG_RC(launch_sig_prep(s, any_small, mode.empty() ? nullptr : &mode, P_<uint32_t>(s->d_rs)));
+    if (any_small || !s->sw.msm_fold)
+      LSG_RC(launch_sig_prep(s, any_small, mode.empty() ? nullptr : &mode, P_<uint32_t>(s->d_rs)));
   }
   LSG_RC(launch_phase(s, A, P_<uint32_t>(s->d_rs), P_<uint32_t>(s->d_fall), true));
   if (A.groups.empty() || s->gp.big_g < 0) {  // no package group: the partial is the identity
@@ -1730,9 +1758,10 @@ int run_fallback_phase(Slot* s, CtxLock* lk, const std::vector<Grp>& groups,
   v.assign(groups.size(), 0);
   if (groups.empty()) return LSG_OK;
   const uint64_t tf0 = trace_host() ? now_ns() : 0;
-  // Signature sums: a group whose sets' unscaled points are resident (they were in a phase-A
-  // bucket-MSM group: d_rs) and that is large enough sums them by its own bucket MSM (no
-  // per-set scaling); the others sum [r_i] sig_i (d_rs2, scaled below).  MSM groups go first
+  // Signature sums: a group whose sets were all in a phase-A bucket-MSM group (rs_raw) and that
+  // is large enough sums them by its own bucket MSM (no per-set scaling): its bucket pass reads
+  // the resident affine signatures (LSG_MSM_FOLD=0: their unscaled copies in d_rs, which only
+  // such sets have); the others sum [r_i] sig_i (d_rs2, scaled below).  MSM groups go first
   // (plan_phase); `order` maps the phase's group k to the caller's.
   std::vector<size_t> order;
   std::vector<uint8_t> gm(groups.size(), 0);
@@ -1774,7 +1803,7 @@ int run_fallback_phase(Slot* s, CtxLock* lk, const std::vector<Grp>& groups,
   std::vector<uint8_t> mode(s->n_sets, 0);
   bool any = false;
   for (size_t g = 0; g < groups.size(); g++) {
-    if (gm[g]) continue;  // (its MSM reads the unscaled points)
+    if (gm[g]) continue;  // (its MSM scales by buckets)
     for (size_t i = groups[g].first; i < groups[g].first + groups[g].len; i++)
       if (!s->rs2_scaled[i]) {
         mode[i] = s->rs2_scaled[i] = 1;
@@ -4033,6 +4062,78 @@ int lsg_check_pow_lanes(lsg_ctx* c, int32_t id, const uint32_t* in, size_t n, ui
 }
 int lsg_check_pow_pair(lsg_ctx* c, int32_t id, const uint32_t* in, size_t n, uint32_t* out) {
   return check_pow(c, id, in, n, out, false);
+}
+
+// the bucket-pass hook (k_msm_bucket_seg and its pair-form twin; mode 2: k_sig_proj + k_seg_reduce<1>)
+int lsg_check_msm_buckets(lsg_ctx* c, int32_t mode, const uint8_t* sigs96, size_t n, const int32_t* err,
+                          const uint8_t* inf, const uint8_t* pinf, const int32_t* idx, size_t n_idx,
+                          const int32_t* chunks, size_t n_chunks, int32_t ips_log2, const int32_t* chunks2,
+                          size_t n_chunks2, int32_t ips_log2_2, size_t n_tmp, size_t n_out, uint8_t* out96) {
+  const size_t lim = (size_t)1 << 20;
+  if (!c || mode < 0 || mode > 2 || !sigs96 || !err || !inf || !pinf || !chunks || !out96 || (n_idx && !idx) ||
+      (n_chunks2 && !chunks2) || n == 0 || n > lim || n_idx > lim || n_chunks == 0 || n_chunks > lim || n_chunks2 > lim ||
+      n_tmp > lim || n_out == 0 || n_out > lim || ips_log2 < 0 || ips_log2 > 5 || ips_log2_2 < 0 || ips_log2_2 > 5)
+    return LSG_ERR_INVALID_ARG;
+  // every index the kernels follow is checked here: list entries name a point, a chunk lies
+  // inside its list, every tmp slot and every output is written exactly once
+  for (size_t k = 0; k < n_idx; k++)
+    if (idx[k] < 0 || (size_t)idx[k] >= n) return LSG_ERR_INVALID_ARG;
+  std::vector<uint8_t> tmp_set(n_tmp, 0), out_set(n_out, 0);
+  auto mark = [&](int32_t out, bool tmp_ok) {
+    std::vector<uint8_t>& v = out >= 0 ? out_set : tmp_set;
+    const size_t o = out >= 0 ? (size_t)out : (size_t)(-(int64_t)out - 1);
+    if ((out < 0 && !tmp_ok) || o >= v.size() || v[o]) return false;
+    v[o] = 1;
+    return true;
+  };
+  for (size_t k = 0; k < n_chunks; k++) {
+    const int32_t off = chunks[3 * k], len = chunks[3 * k + 1];
+    if (off < 0 || len < 0 || (size_t)off + (size_t)len > n_idx || !mark(chunks[3 * k + 2], true)) return LSG_ERR_INVALID_ARG;
+  }
+  for (size_t k = 0; k < n_chunks2; k++) {
+    const int32_t off = chunks2[3 * k], len = chunks2[3 * k + 1];
+    if (off < 0 || len < 0 || (size_t)off + (size_t)len > n_tmp || !mark(chunks2[3 * k + 2], false)) return LSG_ERR_INVALID_ARG;
+  }
+  for (uint8_t v : tmp_set)
+    if (!v) return LSG_ERR_INVALID_ARG;
+  for (uint8_t v : out_set)
+    if (!v) return LSG_ERR_INVALID_ARG;
+  LSG_ENTER(c);
+  timer_reset(&c->dev[0]->util);
+  Slot* s;
+  LSG_RC(sig_decode_impl(c, sigs96, 96, n, false, &s));
+  LSG_HIP(s, hipMemcpyAsync(s->d_seterr.p, err, 4 * n, hipMemcpyHostToDevice, s->st[0]));
+  LSG_HIP(s, hipMemcpyAsync(s->d_siginf.p, inf, n, hipMemcpyHostToDevice, s->st[0]));
+  LSG_HIP(s, hipMemcpyAsync(s->d_pinf.p, pinf, n, hipMemcpyHostToDevice, s->st[0]));
+  s->plan.assign(idx, idx + n_idx);
+  const size_t c1 = s->plan.size();
+  s->plan.insert(s->plan.end(), chunks, chunks + 3 * n_chunks);
+  const size_t c2 = s->plan.size();
+  if (n_chunks2) s->plan.insert(s->plan.end(), chunks2, chunks2 + 3 * n_chunks2);
+  LSG_RC(upload_plan(s));
+  LSG_RC(ensure(s, s->d_bkt, 4 * W_G2P * n_out));
+  LSG_RC(ensure(s, s->seg_tmp[1][0], 4 * W_G2P * std::max(n_tmp, (size_t)1)));
+  LSG_RC(ensure(s, s->d_aux, 96 * n_out));
+  uint32_t* dst = P_<uint32_t>(s->d_bkt);
+  uint32_t* tmp = P_<uint32_t>(s->seg_tmp[1][0]);
+  if (mode == 2) {
+    KL(s, "k_sig_prep", lsgk::sig_prep(S_(s), (int)n, P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
+                                       P_<int32_t>(s->d_seterr), P_<uint8_t>(s->d_pinf), nullptr, nullptr,
+                                       P_<uint32_t>(s->d_rs)));
+    KL(s, "msm_buckets", lsgk::seg_reduce(S_(s), 1, (int)n_chunks, ips_log2, PL(s, c1), PL(s, 0), P_<uint32_t>(s->d_rs),
+                                          dst, tmp));
+  } else {
+    KL(s, "msm_buckets", lsgk::msm_bucket_seg(S_(s), (int)n_chunks, ips_log2, PL(s, c1), PL(s, 0),
+                                              P_<uint32_t>(s->d_sigaff), P_<uint8_t>(s->d_siginf),
+                                              P_<int32_t>(s->d_seterr), P_<uint8_t>(s->d_pinf), dst, tmp, mode == 1));
+  }
+  if (n_chunks2)
+    KL(s, "msm_buckets", lsgk::seg_reduce(S_(s), 1, (int)n_chunks2, ips_log2_2, PL(s, c2), nullptr, tmp, dst, nullptr));
+  KL(s, "k_g2p_compress", lsgk::g2p_compress(S_(s), (int)n_out, dst, P_<uint8_t>(s->d_aux)));
+  LSG_HIP(s, hipMemcpyAsync(out96, s->d_aux.p, 96 * n_out, hipMemcpyDeviceToHost, s->st[0]));
+  LSG_HIP(s, hipStreamSynchronize(s->st[0]));
+  keep_times(s);
+  return LSG_OK;
 }
 
 // the field-edge hooks (k_check_canon, k_check_from_bytes, k_check_fp2_roots, batch_inv, launch_hash)

@@ -222,6 +222,64 @@ __global__ void LSG_KERNEL_ATTR k_sig_agg_seg(int n_chunks, int ips_log2, const 
   }
 }
 
+// The bucket pass of the signature MSM (plan_phase / plan_buckets, lsg_plan.hpp): bucket (w, d) =
+// the sum of the sets whose w-th digit of r_i is d, over the resident affine signatures -- the
+// gather of k_sig_agg_seg with the skip rule of k_sig_proj (sig_usable: an unusable set adds
+// nothing), so no projective copy of every signature is written and read back once per window.
+// Each lane pair folds its members serially with mixed additions (g2_fold_mixed, lsg_curve.hpp)
+// in the layout F -- one Fp2 component per lane, or the pair form -- and the chunk's pairs are
+// combined in the pair form by the butterfly of complete additions.  The plan gives a chunk few
+// pairs (the pass is work-bound: a butterfly level costs every pair one addition, of which half,
+// three quarters, ... are thrown away), so most of the work is the fold.
+template <class F>
+LSG_DEVI void msm_bucket_item(int n_chunks, int ips_log2, const int32_t* __restrict__ chunks,
+                              const int32_t* __restrict__ gather, const uint32_t* __restrict__ sig_aff,
+                              const uint8_t* __restrict__ inf, const int32_t* __restrict__ err,
+                              const uint8_t* __restrict__ pinf, uint32_t* __restrict__ dst, uint32_t* __restrict__ tmp) {
+  lsg_lane_setup();
+  const size_t item = gtid() / LSG_GROUP;
+  const size_t c = item >> ips_log2;
+  const int ips = 1 << ips_log2, j = (int)(item & (size_t)(ips - 1));
+  const bool active = c < (size_t)n_chunks;
+  g2p_t acc = proj_inf<fp2_t>();
+  int out = 0;
+  if (active) {
+    const int off = chunks[3 * c], len = chunks[3 * c + 1];
+    out = chunks[3 * c + 2];
+    acc = g2_to_pair(g2_fold_mixed<F>(j, ips, len, [&](int k, g2a_t& a) {
+      const size_t i = (size_t)gather[off + k];
+      a = lane_load<g2a_t>(sig_aff, i);
+      return sig_usable(i, inf, err, pinf);
+    }));
+  }
+  // every lane runs the butterfly: a chunk never straddles a wave (ips <= 32 pairs)
+#pragma unroll 1
+  for (int o = ips >> 1; o >= 1; o >>= 1) acc = g2_add(acc, shfl_xor_t(acc, LSG_GROUP * o));
+  if (active && j == 0) {
+    if (out >= 0)
+      lane_store(dst, (size_t)out, acc);
+    else
+      lane_store(tmp, (size_t)(-out - 1), acc);
+  }
+}
+__global__ void LSG_KERNEL_ATTR k_msm_bucket_seg(int n_chunks, int ips_log2, const int32_t* __restrict__ chunks,
+                                                 const int32_t* __restrict__ gather, const uint32_t* __restrict__ sig_aff,
+                                                 const uint8_t* __restrict__ inf, const int32_t* __restrict__ err,
+                                                 const uint8_t* __restrict__ pinf, uint32_t* __restrict__ dst,
+                                                 uint32_t* __restrict__ tmp) {
+  msm_bucket_item<chain_fp2_t>(n_chunks, ips_log2, chunks, gather, sig_aff, inf, err, pinf, dst, tmp);
+}
+#ifdef LSG_FP2_LANES
+// the same kernel with its fold in the pair form: the A/B library's LSG_FP2_LANES=0 and the device tests
+__global__ void LSG_KERNEL_ATTR k_msm_bucket_seg_pair(int n_chunks, int ips_log2, const int32_t* __restrict__ chunks,
+                                                      const int32_t* __restrict__ gather,
+                                                      const uint32_t* __restrict__ sig_aff, const uint8_t* __restrict__ inf,
+                                                      const int32_t* __restrict__ err, const uint8_t* __restrict__ pinf,
+                                                      uint32_t* __restrict__ dst, uint32_t* __restrict__ tmp) {
+  msm_bucket_item<fp2_t>(n_chunks, ips_log2, chunks, gather, sig_aff, inf, err, pinf, dst, tmp);
+}
+#endif
+
 __global__ void LSG_KERNEL_ATTR k_g2a_to_bytes(int n, const uint32_t* __restrict__ pts, const uint8_t* __restrict__ inf,
                                                uint8_t* __restrict__ out) {
   LANE_ITEM(n);
@@ -327,6 +385,18 @@ hipError_t sig_agg_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t
                        const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err, uint32_t* dst, uint32_t* tmp) {
   LSG_LAUNCH_ITEMS(k_sig_agg_seg, (size_t)n_chunks << ips_log2, st, n_chunks, ips_log2, chunks, gather, sig_aff, inf, err,
                    dst, tmp);
+}
+hipError_t msm_bucket_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t* chunks, const int32_t* gather,
+                          const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err, const uint8_t* pinf,
+                          uint32_t* dst, uint32_t* tmp, bool pair_form) {
+#ifdef LSG_FP2_LANES
+  if (pair_form)
+    LSG_LAUNCH_ITEMS(k_msm_bucket_seg_pair, (size_t)n_chunks << ips_log2, st, n_chunks, ips_log2, chunks, gather, sig_aff,
+                     inf, err, pinf, dst, tmp);
+#endif
+  (void)pair_form;
+  LSG_LAUNCH_ITEMS(k_msm_bucket_seg, (size_t)n_chunks << ips_log2, st, n_chunks, ips_log2, chunks, gather, sig_aff, inf,
+                   err, pinf, dst, tmp);
 }
 hipError_t g2a_to_bytes(hipStream_t st, int n, const uint32_t* pts, const uint8_t* inf, uint8_t* out192) {
   LSG_LAUNCH_ITEMS(k_g2a_to_bytes, n, st, n, pts, inf, out192);

@@ -86,6 +86,13 @@ hipError_t sig_scale_only(hipStream_t st, int n, const uint32_t* sig_aff, const 
 // folded with mixed additions unless err[set] != 0 or inf[set]
 hipError_t sig_agg_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t* chunks, const int32_t* gather,
                        const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err, uint32_t* dst, uint32_t* tmp);
+// the first pass of the signature MSM's bucket sums (plan_buckets chunks; later passes: seg_reduce
+// op 1 over tmp): element k of the list is set gather[k], folded with mixed additions unless
+// err[set] != 0, inf[set] or pinf[set] (pinf may be null); pair_form: the fold in the pair form
+// (k_msm_bucket_seg_pair) instead of one Fp2 component per lane
+hipError_t msm_bucket_seg(hipStream_t st, int n_chunks, int ips_log2, const int32_t* chunks, const int32_t* gather,
+                          const uint32_t* sig_aff, const uint8_t* inf, const int32_t* err, const uint8_t* pinf,
+                          uint32_t* dst, uint32_t* tmp, bool pair_form = false);
 hipError_t g2a_to_bytes(hipStream_t st, int n, const uint32_t* pts, const uint8_t* inf, uint8_t* out192);
 hipError_t g2p_compress(hipStream_t st, int n, const uint32_t* pts, uint8_t* out96);
 hipError_t g2p_to_canon(hipStream_t st, int n, const uint32_t* pts, uint8_t* out288);

@@ -96,6 +96,10 @@ struct Switches {
   size_t b0_run = 4;           // LSG_B0_RUN: consecutive chunks per phase-B0 group
   int seg_fold_wide = SEG_FOLD_WIDE;  // LSG_SEG_FOLD_WIDE
   size_t slp_items = 2048;     // LSG_SLP_ITEMS as in force (0: the serial programs are off)
+  // LSG_MSM_FOLD=0: the MSM's bucket pass as k_sig_proj + k_seg_reduce<1> on plan_seg's plan
+  // instead of k_msm_bucket_seg on plan_buckets'; LSG_MSM_IPS >= 0 forces the latter's ips_log2
+  bool msm_fold = true;
+  int msm_ips = -1;
 };
 
 // lane pairs per chunk (log2): enough that the longest segment fits one chunk of SEG_FOLD
@@ -107,11 +111,30 @@ inline int ips_for(double avg, int32_t max_len, int fold) {
   return l;
 }
 
+// a pass's chunk triples by descending length (stable): chunk order is free, every chunk carries
+// its output, and a wave whose chunks are alike finishes its serial folds together
+inline void sort_chunks_desc(int32_t* chunks, size_t n) {
+  struct Tri {
+    int32_t off, len, out;
+  };
+  std::vector<Tri> v(n);
+  for (size_t c = 0; c < n; c++) v[c] = {chunks[3 * c], chunks[3 * c + 1], chunks[3 * c + 2]};
+  std::stable_sort(v.begin(), v.end(), [](const Tri& a, const Tri& b) { return a.len > b.len; });
+  for (size_t c = 0; c < n; c++) {
+    chunks[3 * c] = v[c].off;
+    chunks[3 * c + 1] = v[c].len;
+    chunks[3 * c + 2] = v[c].out;
+  }
+}
+
 // Segments s = 0..ns-1: elements [seg_off[s], seg_off[s] + seg_len[s]) of the idx list (at
 // idx_off in the arena; has_idx) or of the input itself; result s goes to dst[dst_base + s].
+// first_ips >= 0 (plan_buckets only): the first pass takes that many lane pairs per chunk (log2),
+// folds up to max(SEG_FOLD, fold_wide) members per pair and lists its chunks by descending
+// length; later passes, and every pass of every other caller, are planned as ever.
 inline SegPlan plan_seg(std::vector<int32_t>& A, int op, const std::vector<int32_t>& seg_off,
                         const std::vector<int32_t>& seg_len, bool has_idx, size_t idx_off, int32_t dst_base,
-                        int fold_wide) {
+                        int fold_wide, int first_ips = -1) {
   SegPlan P;
   P.op = op;
   P.has_idx = has_idx;
@@ -143,6 +166,11 @@ inline SegPlan plan_seg(std::vector<int32_t>& A, int op, const std::vector<int32
       pass.ips_log2 = l;
       fold = fold_wide;
     }
+    const bool first_given = first_ips >= 0 && P.passes.empty();
+    if (first_given) {
+      pass.ips_log2 = std::min(first_ips, 5);
+      fold = std::max(SEG_FOLD, fold_wide);
+    }
     pass.src = src;
     pass.tmp_out = tmp_out;
     const int32_t cap = (int32_t)((1 << pass.ips_log2) * fold);
@@ -169,6 +197,7 @@ inline SegPlan plan_seg(std::vector<int32_t>& A, int op, const std::vector<int32
         nxt_total += (size_t)(t - first);
       }
     }
+    if (first_given) sort_chunks_desc(A.data() + pass.chunk_off, (size_t)pass.n_chunks);
     P.tmp_items = std::max(P.tmp_items, (size_t)t);
     P.passes.push_back(pass);
     avg = nxt.empty() ? 1.0 : (double)nxt_total / (double)nxt.size();
@@ -177,6 +206,125 @@ inline SegPlan plan_seg(std::vector<int32_t>& A, int op, const std::vector<int32
     tmp_out = tmp_out == 1 ? 2 : 1;
   }
   return P;
+}
+
+// ---- the bucket pass of the signature MSM (k_msm_bucket_seg): work-bound by construction.
+// A pass costs every lane pair of a wave the wave's longest serial fold plus one complete
+// addition per butterfly level, whether the pair's result is kept or not, so the model counts a
+// pass in lane-pair additions: chunks laid out 32 >> ips_log2 per wave in launch order, a wave
+// costing 32 x (its longest fold + ips_log2), a fold of m members m - 1 additions.
+// bucket_cost: that count from the bucket lengths alone (sorted by descending length), for the
+// plan plan_seg(..., first_ips) would make -- its choice of pairs and fold per pass restated --
+// without making it; first_ips < 0: plan_seg's own plan (chunks in bucket order: `lens` as given).
+struct SegCost {
+  size_t adds = 0, waves = 0;  // waves: of the first pass
+  int chain = 0;               // the longest dependent run of additions, summed over the passes
+  int passes = 0;
+};
+inline SegCost bucket_cost(const std::vector<int32_t>& lens, int first_ips, int fold_wide) {
+  SegCost c;
+  std::vector<int32_t> split, nxt;
+  const std::vector<int32_t>* cur = &lens;
+  size_t total = 0;
+  for (int32_t l : lens) total += (size_t)l;
+  double avg = lens.empty() ? 1.0 : (double)total / (double)lens.size();
+  while (!cur->empty()) {
+    int32_t max_len = 0;
+    for (int32_t l : *cur) max_len = std::max(max_len, l);
+    int fold = SEG_FOLD, l2 = ips_for(avg, max_len, fold);
+    if ((cur->size() << 5) >= SEG_WIDE_PAIRS) {
+      int l = 0;
+      while (l < l2 && (int32_t)(fold_wide << l) < max_len) l++;
+      l2 = l;
+      fold = fold_wide;
+    }
+    const bool given = first_ips >= 0 && c.passes == 0;
+    if (given) {
+      l2 = std::min(first_ips, 5);
+      fold = std::max(SEG_FOLD, fold_wide);
+    }
+    const int32_t cap = (int32_t)(fold << l2), ips = 1 << l2;
+    const std::vector<int32_t>* chunks = cur;
+    std::vector<int32_t> pieces;
+    if (max_len > cap) {  // (rare: a bucket longer than a chunk)
+      split.clear();
+      size_t nt = 0;
+      for (int32_t l : *cur) {
+        if (l <= cap) {
+          split.push_back(l);
+          continue;
+        }
+        for (int32_t o = 0; o < l; o += cap) split.push_back(std::min(cap, l - o));
+        pieces.push_back((l + cap - 1) / cap);
+        nt += (size_t)pieces.back();
+      }
+      if (given) std::sort(split.begin(), split.end(), std::greater<int32_t>());
+      chunks = &split;
+      avg = pieces.empty() ? 1.0 : (double)nt / (double)pieces.size();
+    }
+    const size_t per_wave = (size_t)32 >> l2, n = chunks->size();
+    int pass_chain = 0;
+    size_t waves = 0;
+    for (size_t w = 0; w < n; w += per_wave, waves++) {
+      int32_t longest = (*chunks)[w];
+      if (!given || chunks != &lens)  // (not known to be sorted: look at the whole wave)
+        for (size_t k = w; k < std::min(n, w + per_wave); k++) longest = std::max(longest, (*chunks)[k]);
+      const int cost = (longest > 0 ? (int)((longest + ips - 1) / ips) - 1 : 0) + l2;
+      c.adds += (size_t)32 * (size_t)cost;
+      pass_chain = std::max(pass_chain, cost);
+    }
+    if (c.passes == 0) c.waves = waves;
+    c.chain += pass_chain;
+    c.passes++;
+    nxt.swap(pieces);
+    cur = &nxt;
+    if (nxt.empty()) break;
+  }
+  return c;
+}
+// The first pass takes the candidate ips_log2 in 0..5 with the most lane pairs whose modelled cost
+// is within BUCKET_COST_TOL of the cheapest candidate's: more pairs per bucket shorten the chain
+// of dependent additions, and the tolerance is what that may cost in instructions.  A candidate
+// that takes more passes than plan_seg's own plan -- a pass is a launch and a round trip through
+// memory -- is none; 32 pairs per bucket never does.  A pass that is both narrow and long -- fewer
+// than BUCKET_MIN_WAVES waves, more than the SEG_FOLD dependent additions plan_seg allows any
+// pass -- is latency-bound however little it costs, so it widens while the passes stay the same.
+// The constants come from the sweep in DESIGN.md section 5l.  The tolerance is bracketed there by
+// two workloads; the floor rests on one (committees at 255 waves, inside a wide spread), and it
+// does not act on chains of SEG_FOLD or fewer, so it is weakly supported.
+// Where no bucket holds more than SEG_FOLD members (a group of a few hundred sets: about one
+// member per bucket) there is no butterfly to save and nothing to price: the pass keeps
+// plan_seg's plan as it is, and such a group costs the host nothing new.
+constexpr double BUCKET_COST_TOL = 1.25;
+constexpr size_t BUCKET_MIN_WAVES = 256;
+// force_ips >= 0 (the A/B library's LSG_MSM_IPS): that candidate, whatever the model says
+inline int bucket_ips(const std::vector<int32_t>& seg_len, int fold_wide) {
+  const int max_passes = bucket_cost(seg_len, -1, fold_wide).passes;
+  std::vector<int32_t> lens(seg_len);
+  std::sort(lens.begin(), lens.end(), std::greater<int32_t>());
+  SegCost cost[6];
+  size_t best = ~(size_t)0;
+  for (int l = 0; l <= 5; l++) {
+    cost[l] = bucket_cost(lens, l, fold_wide);
+    if (cost[l].passes <= max_passes) best = std::min(best, cost[l].adds);
+  }
+  int pick = 5;
+  for (int l = 0; l <= 5; l++)
+    if (cost[l].passes <= max_passes && (double)cost[l].adds <= BUCKET_COST_TOL * (double)best) pick = l;
+  while (pick < 5 && cost[pick].waves < BUCKET_MIN_WAVES && cost[pick].chain > SEG_FOLD &&
+         cost[pick + 1].passes == cost[pick].passes)
+    pick++;
+  return pick;
+}
+inline SegPlan plan_buckets(std::vector<int32_t>& A, const std::vector<int32_t>& seg_off,
+                            const std::vector<int32_t>& seg_len, size_t idx_off, int fold_wide, int force_ips = -1) {
+  if (force_ips < 0) {
+    int32_t max_len = 0;
+    for (int32_t l : seg_len) max_len = std::max(max_len, l);
+    if (max_len <= SEG_FOLD) return plan_seg(A, 1, seg_off, seg_len, true, idx_off, 0, fold_wide);
+  }
+  const int pick = force_ips >= 0 ? std::min(force_ips, 5) : bucket_ips(seg_len, fold_wide);
+  return plan_seg(A, 1, seg_off, seg_len, true, idx_off, 0, fold_wide, pick);
 }
 
 // One RLC group: sets [first, first + len) (a contiguous range: the package group, one
@@ -310,7 +458,8 @@ inline void plan_phase(std::vector<int32_t>& A, const std::vector<uint64_t>& rnd
         }
       }
     }
-    Ph.buckets = plan_seg(A, 1, seg_off, seg_len, true, idx_off, 0, sw.seg_fold_wide);
+    Ph.buckets = sw.msm_fold ? plan_buckets(A, seg_off, seg_len, idx_off, sw.seg_fold_wide, sw.msm_ips)
+                             : plan_seg(A, 1, seg_off, seg_len, true, idx_off, 0, sw.seg_fold_wide);
     // bit (g, k = c w + j): the buckets (g, w, d) whose digit d has bit j set
     const size_t bidx = A.size();
     std::vector<int32_t> boff, blen;
